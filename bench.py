@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json's metric on BASELINE.json's configuration.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
 ``--gpus N`` with N > 1 needs one process per GPU: when this script is started
 plainly (no WORLD_SIZE in the environment) it re-executes itself under
@@ -51,6 +51,13 @@ strong_scaling  every run, any N: BASELINE configs[4]'s shape -- 9 fields x 5
               as passes between fences with the exchange inside; plus configs[3]
               sharded by field and configs[1]'s grid sharded by rows
 
+--dump-outputs DIR  after the K timed steps, what the last one computed -- the FULL packets a
+              caller receives (seg, op, status, fail_surf, pupil) at a fixed, seeded sample of
+              the grid's rays, with their indices (ray_index) and the segments each got (n_seg;
+              seg holds 0 past them, where the trace writes nothing) -- as DIR/<name>.npy,
+              float64 (34 MiB); the same arguments give the same inputs, so two builds can be
+              compared array for array
+
 N > 1: one rank per GPU.  The headline (`value`, `ms_per_step`, "scaling": "strong") is the
 path north_star describes: BASELINE configs[4]'s spot problem (188.7 M rays) cut by pupil rows
 over the ranks, packed hits gathered to rank 0 over RCCL and delivered to its host memory,
@@ -76,6 +83,8 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 
 SPOT_FLAGS = None       # set in main (abi constants)
+DUMP_RAYS = 32768       # --dump-outputs: rays sampled from the timed grid (34 MiB of float64)
+DUMP_SEED = 0
 
 
 def parse():
@@ -104,7 +113,15 @@ def parse():
     ap.add_argument('--ref-worker', default=None, help=argparse.SUPPRESS)
     ap.add_argument('--strong-num', type=int, default=2048,
                     help='pupil grid of the strong-scaling leg is num x num per (field, wvl)')
-    return ap.parse_args()
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one computed (a fixed, seeded '
+                         f'sample of {DUMP_RAYS} rays of the FULL packets) as DIR/<name>.npy')
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.dump_outputs and args.gpus > 1 and not args.no_strong:
+        ap.error('--dump-outputs writes the one-grid FULL step: with --gpus N > 1 it needs --no-strong')
+    return args
 
 
 def free_port():
@@ -264,6 +281,9 @@ def main():
     t_f = time.perf_counter()
     fence()
     fence_ms = (time.perf_counter() - t_f) * 1e3      # cost of one (idle) fence, for the record
+    if args.dump_outputs and rank == 0:
+        # `out` is traced into again by the legs below: what the last timed step left, now
+        dump_outputs(torch, args.dump_outputs, out, N, abi)
     if multi:
         t = torch.tensor([dt, cold_dt], dtype=torch.float64, device=eng.device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -592,6 +612,28 @@ def main():
 
 
 # ----------------------------------------------------------------------------- helpers
+def dump_outputs(torch, path, out, N, abi):
+    """--dump-outputs: the arrays a caller of the timed FULL-grid trace receives, at a fixed,
+    seeded sample of its rays, as float64 .npy files: seg [n_seg, 10, S] with the segments the
+    trace does not write (past a ray's failure) as 0, n_seg [S] the segments it wrote, op /
+    status / fail_surf [S], pupil [2, S], ray_index [S] the sampled rays' indices in the grid"""
+    R = out.R
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(R, size=min(R, DUMP_RAYS), replace=False))
+    it = torch.from_numpy(idx).to(out.op.device)
+    status, fail_surf = out.status[it], out.fail_surf[it]
+    n_seg = segments_written(status, fail_surf, N, abi)
+    seg = out.seg[..., it]
+    unwritten = torch.arange(seg.shape[0], device=seg.device)[:, None] >= n_seg[None, :]
+    seg = seg.masked_fill(unwritten[:, None, :], 0.0)
+    arrays = {'ray_index': idx, 'seg': seg, 'n_seg': n_seg, 'op': out.op[it], 'status': status,
+              'fail_surf': fail_surf, 'pupil': out.pupil[:, it]}
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        if isinstance(a, torch.Tensor):
+            a = a.cpu().numpy()
+        np.save(os.path.join(path, name + '.npy'), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def work_of(status, fail_surf, N, abi, full):
     """(intersections actually performed, algorithmic bytes) of one traced batch from its
     status / fail_surf arrays (torch, on the device): a ray that got through did N - 1
@@ -605,9 +647,17 @@ def work_of(status, fail_surf, N, abi, full):
     inters = n_ok * (N - 1) + int(fs[~ok].sum().item())
     if not full:
         return inters, R * 19
-    missed = status == abi.MISSED_SURFACE
-    nseg = n_ok * N + int(fs[missed].sum().item()) + int((fs[~ok & ~missed] + 1).sum().item())
+    nseg = int(segments_written(status, fail_surf, N, abi).sum().item())
     return inters, nseg * 80 + R * (8 + 1 + 2 + 16)
+
+
+def segments_written(status, fail_surf, N, abi):
+    """per ray (torch int64, on the device): the FULL packet segments the trace writes -- N for
+    a survivor, s for a ray that missed surface s, s + 1 for one blocked / TIR at s"""
+    import torch
+    fs = fail_surf.to(torch.int64)
+    return torch.where(status == abi.OK, torch.full_like(fs, N),
+                       torch.where(status == abi.MISSED_SURFACE, fs, fs + 1))
 
 
 def library_id():

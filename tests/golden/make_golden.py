@@ -452,6 +452,43 @@ def psf_cases():
     print(f'psf.npz: {os.path.getsize(path) / 1024:.0f} KiB, {sorted(set(k.split("/")[0] for k in out))}')
 
 
+def fuzz_paths():
+    """tests/golden/fuzz_paths.npz: the random paths of tests/test_oracle_fuzz_reference.py,
+    their rays and the reference's trace_raw packets in stored form (keys s<seed>_<name>)"""
+    sys.path.insert(0, os.path.join(HERE, '..'))
+    import test_oracle_fuzz_reference as fz
+    out = {f's{seed}_{k}': v for seed in fz.SEEDS for k, v in fz.stored_form(fz.reference_case(seed)).items()}
+    np.savez_compressed(fz.GOLDEN, **out)
+    print(f'fuzz_paths.npz: {os.path.getsize(fz.GOLDEN) / 1024:.0f} KiB')
+
+
+def phase_paths():
+    """tests/golden/phase_paths.npz: the random phase-element paths of
+    tests/test_oracle_phase_reference.py, their rays and the reference's trace_raw packets
+    in stored form (keys <kind><seed>_<name>)"""
+    sys.path.insert(0, os.path.join(HERE, '..'))
+    import test_oracle_phase_reference as ph
+    out = {f'{kind}{seed}_{k}': v for kind in ph.KINDS for seed in ph.SEEDS
+           for k, v in ph.stored_form(ph.reference_phase_case(kind, seed)).items()}
+    np.savez_compressed(ph.GOLDEN, **out)
+    print(f'phase_paths.npz: {os.path.getsize(ph.GOLDEN) / 1024:.0f} KiB')
+
+
+def ingest_reference_tables():
+    """tests/golden/ingest_reference_tables.json: the surface tables of the models the
+    reference's own importers build from the .zmx / .seq fixtures under tests/golden/ingest
+    (tests/test_ingest_reference.py), by file name"""
+    sys.path.insert(0, os.path.join(HERE, '..'))
+    import test_ingest_reference as ir
+    out = {}
+    for rel in ir.ZMX + ir.SEQ:
+        read = ir.reference_zmx_table if rel.endswith('.zmx') else ir.reference_seq_table
+        out[os.path.basename(rel)] = read(ir.fixture(rel)).to_dict()
+    with open(ir.REFERENCE_TABLES, 'w') as f:
+        json.dump(out, f)
+    print(f'ingest_reference_tables.json: {os.path.getsize(ir.REFERENCE_TABLES) / 1024:.0f} KiB, {list(out)}')
+
+
 def wideangle_cases():
     """tests/golden/wideangle.npz: wide-angle pupil searches (wideangle.find_real_enp,
     wideangle.py:86-427) of two models over random field angles -- the rox_enp problem of
@@ -660,6 +697,15 @@ def main():
         return
     if '--only-wideangle' in sys.argv:
         wideangle_cases()
+        return
+    if '--only-fuzz' in sys.argv:
+        fuzz_paths()
+        return
+    if '--only-phase' in sys.argv:
+        phase_paths()
+        return
+    if '--only-ingest-reference' in sys.argv:
+        ingest_reference_tables()
         return
     if '--only-c3-zmx' in sys.argv:
         workload_file(rm.zmx_evenasph_c3(), 'zmx_evenasph_c3', C3_ZMX_DESC)

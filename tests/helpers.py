@@ -1,4 +1,5 @@
 """shared test helpers: golden-fixture loading and SoA comparison"""
+import hashlib
 import json
 import os
 
@@ -304,3 +305,26 @@ def boundary_margin(tbl, wi, opts, seg, surf):
             n_in, n_out = tbl.n_table[wi][surf - 1], tbl.n_table[wi][surf]
             margins['tir'] = abs(n_out * n_out - n_in * n_in * (1.0 - cosI * cosI)) / (n_out * n_out)
     return margins
+
+
+def packet_digest(seg, op):
+    """64-bit digest of one ray's packet (seg [K, 10], op) that is equal exactly when
+    np.array_equal(..., equal_nan=True) calls two packets equal: every NaN hashed as one NaN
+    and -0.0 as 0.0.  The stored random-path cases (tests/test_oracle_*_reference.py) keep
+    the reference's packets in this form."""
+    a = np.append(np.asarray(seg, np.float64).ravel(), op) + 0.0
+    a[np.isnan(a)] = np.nan
+    return np.uint64(int.from_bytes(hashlib.blake2b(a.tobytes(), digest_size=8).digest(), 'little'))
+
+
+def packet_digests(seg, op, valid):
+    """packet_digest of every valid ray of SoA packets seg [K, 10, R], op [R] (0 elsewhere)"""
+    return np.array([packet_digest(seg[:, :, r], op[r]) if valid[r] else 0 for r in range(len(op))],
+                    np.uint64)
+
+
+def rng_from_state(state_json):
+    """a numpy Generator continuing from a bit-generator state stored as JSON"""
+    rng = np.random.default_rng()
+    rng.bit_generator.state = json.loads(str(state_json))
+    return rng

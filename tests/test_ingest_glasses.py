@@ -15,7 +15,8 @@ import pytest
 import rayoptics_amd  # noqa: F401
 from rayoptics_amd import ingest
 
-REF = '/root/reference/src/rayoptics'
+# the reference's rayoptics/codev/tests/ag_dblgauss.seq, stored as a fixture
+DBLGAUSS_SEQ = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'ingest', 'ag_dblgauss.seq')
 
 
 def test_every_formula_reproduces_its_catalogue_nd_and_vd():
@@ -95,10 +96,9 @@ def test_custom_lookup_is_used_as_given():
     assert seen == ['WHATEVER'] * 3 and tbl.n_table[1, 1] == 1.7 + 1e-5 * (600.0 - 587.5618)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason='reference tree not present')
 def test_double_gauss_seq_default_indices_match_the_codev_listing():
     """rayoptics/codev/tests/ag_dblgauss.lis:30-34 lists the indices CODE V used"""
-    pres = ingest.read_seq(os.path.join(REF, 'codev/tests/ag_dblgauss.seq'))
+    pres = ingest.read_seq(DBLGAUSS_SEQ)
     with warnings.catch_warnings():
         warnings.simplefilter('error')
         tbl = pres.to_table()

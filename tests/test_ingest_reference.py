@@ -33,63 +33,104 @@ def rows_equal(a, b, what):
     assert a.wvls == b.wvls and a.stop_idx == b.stop_idx, (what, a.wvls, b.wvls, a.stop_idx, b.stop_idx)
 
 
-@pytest.mark.needs_reference
-@pytest.mark.parametrize('rel', ['zemax/tests/US05831776-1.zmx', 'zemax/tests/354710-C-Zemax(ZMX).zmx',
-                                 'elem/tests/ACL3026U-Zemax(ZMX).zmx',
-                                 'zemax/tests/zmax_37992.zmx',          # a COORDBRK fold
-                                 'zemax/tests/HoO-V2C18Ex46.zmx'])      # 5 COORDBRK + a TOROIDAL
-def test_zmx_table_equals_reference_import(rel):
+ZMX = ['zemax/tests/US05831776-1.zmx', 'zemax/tests/354710-C-Zemax(ZMX).zmx',
+       'elem/tests/ACL3026U-Zemax(ZMX).zmx',
+       'zemax/tests/zmax_37992.zmx',          # a COORDBRK fold
+       'zemax/tests/HoO-V2C18Ex46.zmx']       # 5 COORDBRK + a TOROIDAL
+SEQ = ['codev/tests/ag_dblgauss.seq', 'codev/tests/rc_f16.seq',
+       'codev/tests/singlet.seq',
+       'codev/tests/threemir.seq',            # DAR decenters + tilts, REX/REY/ADY
+       'codev/tests/CODV_35571.seq']          # off-axis parabola, XDE..CDE, CIR
+# the reference's files above (by `rel`, its path under rayoptics/), stored as fixtures, and the
+# tables its own importers build from them (tests/golden/make_golden.py --only-ingest-reference)
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
+REFERENCE_TABLES = os.path.join(GOLDEN, 'ingest_reference_tables.json')
+
+
+def fixture(rel):
+    return os.path.join(GOLDEN, 'ingest', os.path.basename(rel))
+
+
+def reference_zmx_table(path):
+    """the table of the model the reference's own .zmx importer builds from `path`"""
     from oracle import refshim
     refshim.install()
     from rayoptics.zemax import zmxread
-    from rayoptics_amd import SurfaceTable, ingest
-    path = pathlib.Path(REF) / rel
+    from rayoptics_amd import SurfaceTable
     for enc in ('utf-16', 'utf-8', 'iso-8859-1'):
         try:
-            inpt = path.open(encoding=enc).read()
+            inpt = pathlib.Path(path).open(encoding=enc).read()
             break
         except UnicodeError:
             pass
     opm, _info = zmxread.read_lens(None, inpt, do_update=False)     # the reference's importer
     opm['seq_model'].update_model()
-    theirs = SurfaceTable.from_seq_model(opm['seq_model'])
-    ours = ingest.read_zmx(str(path)).to_table(index_of=ingest.reference_fallback_index)
-    rows_equal(ours, theirs, rel)
+    return SurfaceTable.from_seq_model(opm['seq_model'])
 
 
-@pytest.mark.needs_reference
-@pytest.mark.parametrize('rel', ['codev/tests/ag_dblgauss.seq', 'codev/tests/rc_f16.seq',
-                                 'codev/tests/singlet.seq',
-                                 'codev/tests/threemir.seq',            # DAR decenters + tilts, REX/REY/ADY
-                                 'codev/tests/CODV_35571.seq'])         # off-axis parabola, XDE..CDE, CIR
-def test_seq_table_equals_reference_import(rel):
+def reference_seq_table(path):
+    """the table of the model the reference's own .seq importer builds from `path`"""
     from oracle import refshim
     refshim.install()
     from rayoptics.codev import cmdproc
-    from rayoptics_amd import SurfaceTable, ingest
-    path = pathlib.Path(REF) / rel
+    from rayoptics_amd import SurfaceTable
     # files that carry aperture data make read_lens trace rays to size the *other* surfaces
     # (set_clear_apertures, cmdproc.py:89-95: control plane, it needs the element model);
-    # max_aperture is neutralised below, so that step is skipped
+    # max_aperture is neutralised by the callers, so that step is skipped
     from rayoptics.seq.sequential import SequentialModel
     from rayoptics.optical.opticalmodel import OpticalModel
     saved = SequentialModel.set_clear_apertures, OpticalModel.update_model
     SequentialModel.set_clear_apertures = lambda self, **kw: None
     OpticalModel.update_model = lambda self, **kw: None
     try:
-        opm, _info = cmdproc.read_lens(path, do_update=False)
+        opm, _info = cmdproc.read_lens(pathlib.Path(path), do_update=False)
     finally:
         SequentialModel.set_clear_apertures, OpticalModel.update_model = saved
     sm = opm['seq_model']
     sm.update_model()
-    theirs = SurfaceTable.from_seq_model(sm)
-    ours = ingest.read_seq(str(path)).to_table(index_of=ingest.reference_fallback_index)
+    return SurfaceTable.from_seq_model(sm)
+
+
+def stored_reference_table(rel):
+    import json
+    from rayoptics_amd import SurfaceTable
+    with open(REFERENCE_TABLES) as f:
+        return SurfaceTable.from_dict(json.load(f)[os.path.basename(rel)])
+
+
+def neutralise_max_aperture(*tables):
     # CODE V listings give max_aperture no value: the reference derives it later
     # from traced rays (set_clear_apertures, control plane); compare with it neutralised
-    for t in (ours, theirs):
+    for t in tables:
         for r in t.rows:
             r.max_aperture = 1.0
+
+
+@pytest.mark.parametrize('rel', ZMX)
+def test_zmx_table_equals_reference_import(rel):
+    from rayoptics_amd import ingest
+    theirs = stored_reference_table(rel)
+    ours = ingest.read_zmx(fixture(rel)).to_table(index_of=ingest.reference_fallback_index)
     rows_equal(ours, theirs, rel)
+
+
+@pytest.mark.parametrize('rel', SEQ)
+def test_seq_table_equals_reference_import(rel):
+    from rayoptics_amd import ingest
+    theirs = stored_reference_table(rel)
+    ours = ingest.read_seq(fixture(rel)).to_table(index_of=ingest.reference_fallback_index)
+    neutralise_max_aperture(ours, theirs)
+    rows_equal(ours, theirs, rel)
+
+
+@pytest.mark.needs_reference
+@pytest.mark.parametrize('rel', ZMX + SEQ)
+def test_stored_reference_tables_are_the_live_import(rel):
+    live = (reference_zmx_table if rel.endswith('.zmx') else reference_seq_table)(fixture(rel))
+    stored = stored_reference_table(rel)
+    if rel.endswith('.seq'):
+        neutralise_max_aperture(live, stored)
+    rows_equal(stored, live, rel)
 
 
 @pytest.mark.needs_reference

@@ -17,8 +17,61 @@ from test_ingest_reference import REF, rows_equal
 
 pytestmark = pytest.mark.needs_reference
 
-FILES = sorted(os.path.relpath(p, REF) for ext in ('zmx', 'seq')
-               for p in glob.glob(os.path.join(REF, '**', f'*.{ext}'), recursive=True))
+
+def tree_files(*exts):
+    """the files of the reference tree with these extensions, relative to REF"""
+    return sorted(os.path.relpath(p, REF) for ext in exts
+                  for p in glob.glob(os.path.join(REF, '**', f'*.{ext}'), recursive=True))
+
+
+# the reference tree's prescription files, listed here rather than globbed at collection so that
+# the test ids are the same whether or not the tree is present; test_file_lists_are_the_reference_tree
+# keeps the lists complete
+FILES = [
+    'codev/tests/CODV_32327.seq',
+    'codev/tests/CODV_35571.seq',
+    'codev/tests/CODV_49664.seq',
+    'codev/tests/CODV_65564.seq',
+    'codev/tests/CODV_65988.seq',
+    'codev/tests/CODV_65988_noDOE.seq',
+    'codev/tests/achroMangin.seq',
+    'codev/tests/achroMangin_ok.seq',
+    'codev/tests/ag_dblgauss.seq',
+    'codev/tests/asp46.seq',
+    'codev/tests/dar_test.seq',
+    'codev/tests/dec_rev_tilt_test.seq',
+    'codev/tests/dec_test.seq',
+    'codev/tests/dec_tilt_test.seq',
+    'codev/tests/folded_lenses.seq',
+    'codev/tests/landscape_lens.seq',
+    'codev/tests/lens_reflection_test.seq',
+    'codev/tests/mangin.seq',
+    'codev/tests/paraboloid.seq',
+    'codev/tests/paraboloid_f8.seq',
+    'codev/tests/questar35.seq',
+    'codev/tests/rc_f16.seq',
+    'codev/tests/schmidt.seq',
+    'codev/tests/schmidt_sph.seq',
+    'codev/tests/singlet.seq',
+    'codev/tests/test.seq',
+    'codev/tests/threemir.seq',
+    'codev/tests/tilt_test.seq',
+    'codev/tests/unfolded_lenses_w_ape.seq',
+    'elem/tests/ACL3026U-Zemax(ZMX).zmx',
+    'zemax/models/PhotoPrime/US05331467-1.zmx',
+    'zemax/tests/354710-C-Zemax(ZMX).zmx',
+    'zemax/tests/ASL5040-UV-Zemax(ZMX).zmx',
+    'zemax/tests/HoO-V2C18Ex03.zmx',
+    'zemax/tests/HoO-V2C18Ex27.zmx',
+    'zemax/tests/HoO-V2C18Ex46.zmx',
+    'zemax/tests/HoO-V2C18Ex66.zmx',
+    'zemax/tests/HoO-V2C18Ex66NEW.zmx',
+    'zemax/tests/US00583336-2-scaled.zmx',
+    'zemax/tests/US05831776-1.zmx',
+    'zemax/tests/US08011793-1.zmx',
+    'zemax/tests/zmax_37992.zmx',
+    'zemax/tests/zmax_55278.zmx',
+]
 # a Q-type asphere: the reference's importer keeps the base conic and drops the Q terms
 # (zmxread.py:295-333); the default ingest does the same, with a warning and a record
 UNMODELLED = {'zemax/tests/ASL5040-UV-Zemax(ZMX).zmx': 'QED_TYPE'}
@@ -102,7 +155,39 @@ def test_every_prescription_file_of_the_reference_tree(rel):
         logging.disable(logging.NOTSET)
 
 
-ROA_FILES = sorted(os.path.relpath(p, REF) for p in glob.glob(os.path.join(REF, '**', '*.roa'), recursive=True))
+ROA_FILES = [
+    'gui/tests/Sasian Triplet old.roa',
+    'gui/tests/cell_phone_camera_old.roa',
+    'models/Cassegrain.roa',
+    'models/Dall_Kirkham.roa',
+    'models/HybridAchromat.roa',
+    'models/Ritchey_Chretien.roa',
+    'models/Sasian Triplet.roa',
+    'models/TwoMirror.roa',
+    'models/TwoSphericalMirror.roa',
+    'models/collimator.roa',
+    'models/double2frelay.roa',
+    'models/f2 focuser.roa',
+    'models/galilean.roa',
+    'models/petzval.roa',
+    'models/singlet_f5.roa',
+    'models/telephoto.roa',
+    'models/thin_triplet.roa',
+    'models/thin_triplet_floating_stop.roa',
+    'models/thinlens.roa',
+    'models/thinlens_floating_stop.roa',
+    'optical/tests/Nikon Nikkor Z 14-30mm f-4 S.roa',
+    'optical/tests/US007277232_Example04P.roa',
+    'optical/tests/US007277232_Example04P_hikari_glasses.roa',
+    'optical/tests/cell_phone_camera.roa',
+    'optical/tests/singlet_f3.roa',
+    'zemax/models/PhotoPrime/US05331467-1_asm.roa',
+]
+
+
+def test_file_lists_are_the_reference_tree():
+    assert FILES == tree_files('zmx', 'seq')
+    assert ROA_FILES == tree_files('roa')
 
 
 @pytest.mark.parametrize('rel', ROA_FILES)

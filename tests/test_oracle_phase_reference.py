@@ -1,16 +1,30 @@
-"""Oracle vs the LIVE reference (build container only) for the rows added in
-round 2: phase elements (DiffractionGrating, DiffractiveElement with
-radial_phase_fct, HolographicElement) on surfaces, ThinLens interfaces
-(rayoptics/oprops/doe.py, thinlens.py; raytrace.py:41-48, 205-210), traced by
-the reference's own trace_raw at several wavelengths and by oracle/rox_oracle.c
--- bit for bit (segments, op incl. the accumulated phase, status incl.
-TraceEvanescentRayError, failing surface, partial packets)."""
+"""Oracle vs the reference for the rows added in round 2: phase elements
+(DiffractionGrating, DiffractiveElement with radial_phase_fct, HolographicElement) on
+surfaces, ThinLens interfaces (rayoptics/oprops/doe.py, thinlens.py; raytrace.py:41-48,
+205-210), traced by the reference's own trace_raw at several wavelengths and by
+oracle/rox_oracle.c -- bit for bit (segments, op incl. the accumulated phase, status incl.
+TraceEvanescentRayError, failing surface, partial packets).
+
+Where the reference is not importable the random paths are checked against the reference's
+side as stored in tests/golden/phase_paths.npz (tests/golden/make_golden.py --only-phase): each
+path's surface table, the generator state its rays are drawn from, and per ray the status,
+failing surface and a 64-bit digest of the packet (tests/helpers.py packet_digest).  Where it
+is importable, the live comparison also regenerates the stored case and requires it unchanged.
+The limit cases are built from the reference's classes and need it live."""
+import json
+import os
+
 import numpy as np
 import pytest
 
-pytestmark = pytest.mark.needs_reference
-
 WVLS = [486.1, 587.6, 656.3]
+KINDS = ['grating', 'doe', 'hologram', 'thinlens']
+# (range(8) was enough for everything but libm pow: `x**2` in the reference is pow(), one ulp off
+# x*x for about one argument in a thousand, and gcc folds pow(x, 2.0) into x*x unless told not to
+# -- oracle/Makefile's -fno-builtin-pow; seeds 17, 18, 26 ... of the grating case catch that)
+SEEDS = list(range(8)) + [17, 18, 26, 31, 34, 50]
+R = 120
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'phase_paths.npz')
 
 
 def random_phase_path(rng, kind):
@@ -79,13 +93,24 @@ def random_phase_path(rng, kind):
     return paths, k_phase
 
 
-# (range(8) was enough for everything but libm pow: `x**2` in the reference is pow(), one ulp off
-# x*x for about one argument in a thousand, and gcc folds pow(x, 2.0) into x*x unless told not to
-# -- oracle/Makefile's -fno-builtin-pow; seeds 17, 18, 26 ... of the grating case catch that)
-@pytest.mark.parametrize('kind', ['grating', 'doe', 'hologram', 'thinlens'])
-@pytest.mark.parametrize('seed', list(range(8)) + [17, 18, 26, 31, 34, 50])
-def test_phase_elements_oracle_equals_reference(kind, seed):
-    from oracle import oracle, refshim
+def random_phase_rays(rng, thi0):
+    """the R rays of a case and their wavelength indices, drawn after its paths"""
+    pt0 = np.stack([rng.uniform(-5, 5, R), rng.uniform(-5, 5, R), np.zeros(R)])
+    tgt = np.stack([rng.uniform(-9, 9, R), rng.uniform(-9, 9, R), np.full(R, thi0)])
+    d = tgt - pt0
+    d /= np.linalg.norm(d, axis=0)
+    wi = (np.arange(R) % len(WVLS)).astype(np.int32)
+    return pt0, d, wi
+
+
+def reference_phase_case(kind, seed):
+    """case (kind, seed) traced by the reference: the paths' surface table (JSON), the generator
+    state the rays are drawn from (JSON) with the object distance thi0, the rays and their
+    wavelength indices, and per ray the packet (seg [N, 10, R], NaN past its last segment), op,
+    status and failing surface; valid[r] is False where trace_raw raised a non-Trace exception
+    (degenerate geometry: no contract)"""
+    import warnings
+    from oracle import refshim
     refshim.install()
     from rayoptics.raytr.raytrace import trace_raw
     from rayoptics.raytr import traceerror as terr
@@ -94,43 +119,111 @@ def test_phase_elements_oracle_equals_reference(kind, seed):
     paths, k_phase = random_phase_path(rng, kind)
     N = len(paths[0])
     tbl = SurfaceTable.from_paths(paths, WVLS)
-    assert tbl.rows[k_phase].ph.kind != abi.PH_NONE
-    R = 120
     thi0 = paths[0][0][2][1][2]
-    pt0 = np.stack([rng.uniform(-5, 5, R), rng.uniform(-5, 5, R), np.zeros(R)])
-    tgt = np.stack([rng.uniform(-9, 9, R), rng.uniform(-9, 9, R), np.full(R, thi0)])
-    d = tgt - pt0
-    d /= np.linalg.norm(d, axis=0)
-    wi = (np.arange(R) % len(WVLS)).astype(np.int32)
+    state = json.dumps(rng.bit_generator.state)
+    pt0, d, wi = random_phase_rays(rng, thi0)
     kw = dict(first_surf=1, last_surf=N - 2, check_apertures=True)
-    opts = oracle.make_opts(flags=abi.INTERSECT_OBJ | abi.CHECK_APERTURES, first_surf=1, last_surf=N - 2)
-    with np.errstate(all='ignore'):
-        res = oracle.trace_rays(tbl, pt0, d, wi, opts)
     kinds = {terr.TraceMissedSurfaceError: abi.MISSED_SURFACE, terr.TraceTIRError: abi.TIR,
              terr.TraceRayBlockedError: abi.BLOCKED, terr.TraceEvanescentRayError: abi.EVANESCENT}
-    n_ok = n_checked = 0
-    import warnings
+    seg = np.full((N, 10, R), np.nan)
+    op = np.full(R, np.nan)
+    status = np.zeros(R, np.int64)
+    fail_surf = np.full(R, -1, np.int64)
+    valid = np.ones(R, bool)
     for r in range(R):
         try:
             with np.errstate(all='ignore'), warnings.catch_warnings():
                 warnings.simplefilter('ignore')
-                ray, op, _ = trace_raw(iter(paths[wi[r]]), pt0[:, r].copy(), d[:, r].copy(),
-                                       WVLS[wi[r]], **kw)
+                ray, op_r, _ = trace_raw(iter(paths[wi[r]]), pt0[:, r].copy(), d[:, r].copy(),
+                                         WVLS[wi[r]], **kw)
             st, surf = abi.OK, -1
         except terr.TraceError as e:
             st, surf = kinds[type(e)], e.surf
-            ray, op, _ = e.ray_pkg
+            ray, op_r, _ = e.ray_pkg
         except (ValueError, ZeroDivisionError, FloatingPointError):
+            valid[r] = False
             continue
+        status[r], fail_surf[r], op[r] = st, surf, op_r
+        seg[:len(ray), :, r] = np.array([np.concatenate([s[0], s[1], [s[2]], s[3]])
+                                         for s in ray]).reshape(-1, 10)
+    return {'table': np.array(json.dumps(tbl.to_dict())), 'k_phase': np.array(k_phase),
+            'rng': np.array(state), 'thi0': np.array(thi0), 'pt0': pt0, 'd': d, 'wi': wi,
+            'seg': seg, 'op': op, 'status': status, 'fail_surf': fail_surf, 'valid': valid}
+
+
+def stored_form(case):
+    """what tests/golden/phase_paths.npz keeps of a reference_phase_case(): the rays as the
+    generator state they are drawn from, the packets as one packet_digest per ray"""
+    import helpers as H
+    out = {k: case[k] for k in ('table', 'k_phase', 'rng', 'thi0', 'status', 'fail_surf', 'valid')}
+    out['status'] = out['status'].astype(np.int8)
+    out['fail_surf'] = out['fail_surf'].astype(np.int8)
+    out['digest'] = H.packet_digests(case['seg'], case['op'], case['valid'])
+    return out
+
+
+def stored_phase_case(kind, seed):
+    pre = f'{kind}{seed}_'
+    with np.load(GOLDEN) as z:
+        return {k[len(pre):]: z[k] for k in z.files if k.startswith(pre)}
+
+
+def trace_oracle(table_json, k_phase, pt0, d, wi):
+    from oracle import oracle
+    from rayoptics_amd import SurfaceTable, abi
+    tbl = SurfaceTable.from_dict(json.loads(str(table_json)))
+    assert tbl.rows[int(k_phase)].ph.kind != abi.PH_NONE
+    N = tbl.n_ifcs
+    opts = oracle.make_opts(flags=abi.INTERSECT_OBJ | abi.CHECK_APERTURES, first_surf=1, last_surf=N - 2)
+    with np.errstate(all='ignore'):
+        return N, oracle.trace_rays(tbl, pt0, d, wi, opts)
+
+
+def assert_oracle_equals(kind, seed, ref):
+    """the oracle on case (kind, seed) against the reference's packets (a reference_phase_case())"""
+    from rayoptics_amd import abi
+    N, res = trace_oracle(ref['table'], ref['k_phase'], ref['pt0'], ref['d'], ref['wi'])
+    rays = np.flatnonzero(ref['valid'])
+    for r in rays:
+        st, surf = ref['status'][r], ref['fail_surf'][r]
         assert res.status[r] == st and res.fail_surf[r] == surf, (kind, seed, r, st, surf,
                                                                  res.status[r], res.fail_surf[r])
-        ref = np.array([np.concatenate([s[0], s[1], [s[2]], s[3]]) for s in ray]).reshape(-1, 10)
-        got = res.seg[:len(ray), :, r]
-        assert np.array_equal(ref, got, equal_nan=True), (kind, seed, r, np.argwhere(ref != got)[:3].tolist())
-        assert op == res.op[r] or (np.isnan(op) and np.isnan(res.op[r])), (kind, seed, r, op, res.op[r])
-        n_checked += 1
-        n_ok += st == abi.OK
-    assert n_checked > R // 2 and n_ok > 0
+        want, got = ref['seg'][:, :, r], res.seg[:N, :, r]
+        assert np.array_equal(want, got, equal_nan=True), (kind, seed, r, np.argwhere(want != got)[:3].tolist())
+        assert np.array_equal(ref['op'][r], res.op[r], equal_nan=True), (kind, seed, r, ref['op'][r], res.op[r])
+    assert len(rays) > R // 2 and (ref['status'][rays] == abi.OK).any()
+
+
+@pytest.mark.needs_reference
+@pytest.mark.parametrize('kind', KINDS)
+@pytest.mark.parametrize('seed', SEEDS)
+def test_phase_elements_oracle_equals_reference(kind, seed):
+    live = reference_phase_case(kind, seed)
+    assert_oracle_equals(kind, seed, live)
+    # ... and the stored case is this one
+    stored, ref = stored_form(live), stored_phase_case(kind, seed)
+    assert sorted(stored) == sorted(ref)
+    for k in stored:
+        assert stored[k].shape == ref[k].shape and np.array_equal(stored[k], ref[k]), (kind, seed, k)
+
+
+@pytest.mark.parametrize('kind', KINDS)
+@pytest.mark.parametrize('seed', SEEDS)
+def test_phase_elements_oracle_equals_stored_reference(kind, seed):
+    """the same comparison against the stored case: every ray's status and failing surface,
+    and its packet (segments, op incl. the accumulated phase) bit for bit by digest"""
+    import helpers as H
+    from rayoptics_amd import abi
+    ref = stored_phase_case(kind, seed)
+    pt0, d, wi = random_phase_rays(H.rng_from_state(ref['rng']), float(ref['thi0']))
+    N, res = trace_oracle(ref['table'], ref['k_phase'], pt0, d, wi)
+    rays = np.flatnonzero(ref['valid'])
+    for r in rays:
+        st, surf = ref['status'][r], ref['fail_surf'][r]
+        assert res.status[r] == st and res.fail_surf[r] == surf, (kind, seed, r, st, surf,
+                                                                 res.status[r], res.fail_surf[r])
+        assert H.packet_digest(res.seg[:N, :, r], res.op[r]) == ref['digest'][r], (kind, seed, r)
+    assert len(rays) > R // 2 and (ref['status'][rays] == abi.OK).any()
 
 
 def limit_case_paths(kind):
@@ -158,6 +251,7 @@ def limit_case_paths(kind):
             for w in range(len(H.PHASE_LIMIT_WVLS))]
 
 
+@pytest.mark.needs_reference
 @pytest.mark.parametrize('kind', ['grating_nan', 'doe_tir', 'doe_evanescent', 'hologram_evanescent'])
 def test_phase_limits_oracle_equals_reference(kind):
     """the constructions of tests/test_gpu_r02.py::test_phase_elements_at_their_limits against the

@@ -25,7 +25,7 @@ def soak_tests():
     t0, bad, n = time.time(), [], 0
     for seed in range(30, 1530):
         try:
-            t.test_oracle_equals_reference_on_random_paths(seed)
+            t.assert_oracle_equals(seed, t.reference_case(seed))
             n += 1
         except AssertionError as e:
             bad.append((seed, str(e)[:120]))
@@ -35,7 +35,7 @@ def soak_tests():
     for kind in ('grating', 'doe', 'hologram', 'thinlens'):
         for seed in range(8, 308):
             try:
-                tp.test_phase_elements_oracle_equals_reference(kind, seed)
+                tp.assert_oracle_equals(kind, seed, tp.reference_phase_case(kind, seed))
                 n += 1
             except AssertionError as e:
                 if str(e):                      # (an empty message = too few rays got through)
