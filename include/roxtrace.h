@@ -510,6 +510,60 @@ int rox_spot_stats(const double *seg, int64_t ld, const uint8_t *status, const i
                    const double *y_edges, int32_t n_y_edges, rox_spot_summary *summary,
                    uint32_t *hist, void *stream);
 
+/* Through-focus scan: trace a pupil grid ONCE and evaluate every ray at n_planes focus
+ * positions in the same launch -- the refocus functions analyses.focus_wavefront /
+ * focus_fan / focus_pupil_coords (rayoptics/raytr/analyses.py:313-342, 561-580, 769-791),
+ * which re-evaluate traced rays at a new defocus `foc`, over a whole range of focus shifts.
+ * A plane carries what a ROX_OUT_FAN launch reads from rox_opts: foc, image_pt and wf.
+ *
+ *   rows   optional DEVICE array [n_planes][3][ld]: plane k's (x abr, y abr, OPD) of ray r at
+ *          rows[(k*3 + c)*ld + r].  Bit-identical to the seg[3][ld] that n_planes
+ *          rox_trace_pupil_grid calls with out_mode ROX_OUT_FAN and that plane's foc /
+ *          image_pt / wf write: every entry of a ray with status ROX_OK is the same IEEE
+ *          double; the entries of a ray that fails are not written, as a FAN launch leaves
+ *          them.  ld >= the number of rays of the grid.
+ *   status optional DEVICE array [rays]: the per-ray status (as rox_out.status).
+ *   stats  optional [n_planes] rox_focus_stats, host or device memory, over the rays with
+ *          status ROX_OK.  Reduced in the kernel (per-wave partial records, summed in a fixed
+ *          order by a finishing pass; no floating-point atomics): two identical calls give
+ *          bit-identical statistics.  A host destination makes the call synchronous.
+ *   rows and stats may not both be NULL.
+ *
+ * planes is HOST memory (copied before the call returns).
+ * opts supplies flags, first_surf / last_surf, eps and fuzz; its out_mode must be ROX_OUT_FAN,
+ * its foc / image_pt / wf are ignored in favour of planes[].  ROX_HOST_POINTERS is not
+ * accepted.  ROX_FAST_FP64 runs the tolerance-mode kernels: the rows then equal those of
+ * n_planes tolerance-mode FAN launches (within ~1e-13 relative of the exact values, the same
+ * per-ray status).  Pupil grids of kind ROX_GRID_PRODUCT and ROX_GRID_FAN at one wavelength,
+ * at most 2^28 rays.  Argument errors (n_planes outside [1, ROX_MAX_FOCUS_PLANES], NULL planes,
+ * ld below the ray count, both outputs NULL, another out_mode, a plane whose wf could not be
+ * traced by a FAN launch, a wvl_idx outside the system's wavelengths) return ROX_E_ARG before
+ * anything is enqueued.  Asynchronous on `stream` unless stats is host memory.           */
+#define ROX_MAX_FOCUS_PLANES 256
+typedef struct rox_focus_plane {
+    double foc;              /* defocus (rox_opts.foc of a FAN launch)                      */
+    double image_pt[2];      /* fld.ref_sphere[0][:2] (rox_opts.image_pt)                   */
+    double reserved;         /* 0                                                           */
+    rox_wavefront wf;        /* this focus's reference sphere (rox_opts.wf); kind per plane  */
+} rox_focus_plane;           /* 544 bytes */
+typedef struct rox_focus_stats {
+    int64_t n;               /* rays with status ROX_OK                                     */
+    double cx, cy;           /* centroid: sum x / n, sum y / n                              */
+    double rms_spot;         /* sqrt(sum((x - cx)^2 + (y - cy)^2) / n): about the centroid */
+    double rms_spot_image_pt;/* sqrt(sum(x^2 + y^2) / n): about image_pt                   */
+    double opd_mean;         /* sum OPD / n, system units (as rows)                        */
+    double opd_rms;          /* sqrt(sum((OPD - opd_mean)^2) / n): about the mean          */
+    double opd_min, opd_max; /* every field but n is NaN when n == 0.  Means and squared
+                                deviations are merged pairwise (Chan, Golub & LeVeque), not
+                                formed as sum(v^2)/n - mean^2: no cancellation on a large
+                                OPD piston                                                  */
+} rox_focus_stats;           /* 72 bytes */
+int rox_trace_through_focus(rox_system *sys, const rox_field *fld, const rox_grid *grid,
+                            int32_t wvl_idx, const rox_opts *opts,
+                            int32_t n_planes, const rox_focus_plane *planes,
+                            double *rows, int64_t ld, uint8_t *status,
+                            rox_focus_stats *stats, void *stream);
+
 /* chief-ray aiming ------------------------------------------------------- */
 /* One problem per (field, wavelength): trace.iterate_ray
  * (rayoptics/raytr/trace.py:313-415) as trace.aim_chief_ray calls it

@@ -153,6 +153,24 @@ class SpotSummary(C.Structure):
 SPOT_ROWS, SPOT_PAIRS = 0, 1
 
 
+class FocusPlane(C.Structure):
+    """rox_focus_plane: one focus position of rox_trace_through_focus (a FAN launch's foc /
+    image_pt / wf)"""
+    _fields_ = [('foc', C.c_double), ('image_pt', C.c_double * 2), ('reserved', C.c_double),
+                ('wf', Wavefront)]
+
+
+class FocusStats(C.Structure):
+    """rox_focus_stats: one plane's statistics over the rays with status OK"""
+    _fields_ = [('n', C.c_int64), ('cx', C.c_double), ('cy', C.c_double),
+                ('rms_spot', C.c_double), ('rms_spot_image_pt', C.c_double),
+                ('opd_mean', C.c_double), ('opd_rms', C.c_double),
+                ('opd_min', C.c_double), ('opd_max', C.c_double)]
+
+
+MAX_FOCUS_PLANES = 256      # include/roxtrace.h ROX_MAX_FOCUS_PLANES
+
+
 class Vig(C.Structure):
     _fields_ = [('fld', Field), ('start_dir', C.c_double * 2), ('unit_dir', C.c_double * 2),
                 ('xy', C.c_int32), ('wvl_idx', C.c_int32), ('stop_surf', C.c_int32),
@@ -175,6 +193,8 @@ assert C.sizeof(Grid) == 48
 assert C.sizeof(Out) == 56
 assert C.sizeof(Aim) == 80
 assert C.sizeof(Enp) == 136
+assert C.sizeof(FocusPlane) == 544
+assert C.sizeof(FocusStats) == 72
 
 # every symbol include/roxtrace.h declares (checked by tests/test_abi.py) ...
 EXPORTS = ('rox_abi_version', 'rox_device_count', 'rox_set_device',
@@ -184,7 +204,7 @@ EXPORTS = ('rox_abi_version', 'rox_device_count', 'rox_set_device',
            'rox_aim_chief_rays', 'rox_iterate_ray_raw', 'rox_find_real_enp', 'rox_calc_vignetting',
            'rox_iterate_pupil_rays', 'rox_calc_psf',
            'rox_pin_host_memory', 'rox_unpin_host_memory', 'rox_copy_async', 'rox_synchronize',
-           'rox_spot_stats')
+           'rox_spot_stats', 'rox_trace_through_focus')
 # ... and the measurement / self-test helpers of include/roxtrace_diag.h
 DIAG_EXPORTS = ('rox_time_pupil_grid', 'rox_selftest_fp64', 'rox_diag_pack_launches')
 
@@ -240,6 +260,9 @@ def declare(lib):
     lib.rox_synchronize.argtypes = [vp]
     lib.rox_spot_stats.restype = C.c_int
     lib.rox_spot_stats.argtypes = [vp, i64, vp, vp, i64, i32, vp, i32, vp, i32, P(SpotSummary), vp, vp]
+    lib.rox_trace_through_focus.restype = C.c_int
+    lib.rox_trace_through_focus.argtypes = [vp, P(Field), P(Grid), i32, P(Opts), i32, P(FocusPlane),
+                                            vp, i64, vp, vp, vp]
     lib.rox_time_pupil_grid.restype = C.c_int
     lib.rox_time_pupil_grid.argtypes = [vp, P(Field), P(Grid), i32, P(Opts),
                                         P(Out), vp, i32, P(dbl)]

@@ -9,6 +9,8 @@
   eval_wavefront     <- rayoptics/raytr/analyses.py:699-732 (OPD fused on device)
   trace_wavefront / focus_wavefront <- rayoptics/raytr/analyses.py:735-791 (RayGrid, PSF)
   trace_pupil_coords / focus_pupil_coords <- rayoptics/raytr/analyses.py:545-580 (RayList, RayGeoPSF)
+  through_focus      (new) the refocus functions over a range of focus shifts: one trace,
+                        K focus planes, per-plane statistics (rox_trace_through_focus)
 """
 import numpy as np
 
@@ -563,6 +565,118 @@ def focus_fan(opt_model, fan_pkg, fld, wvl, foc, image_pt_2d=None, image_delta=N
         else:
             out.append((px, py, np.nan))
     return out
+
+
+# ---- through focus -----------------------------------------------------------------
+def best_focus(focs, values):
+    """the focus at which a sampled curve is least: the vertex of the parabola through the
+    sampled minimum and its two neighbours -> (focus, 'vertex'); the end sample when the
+    minimum is the first or last sample -> (focus, 'end').  (The first minimum's parabola always
+    opens upwards; 'sample' -- the sample itself -- guards the degenerate arithmetic.)  NaN
+    samples (planes no ray reached) are skipped; none left -> (nan, 'none')."""
+    f = np.asarray(focs, dtype=np.float64)
+    v = np.asarray(values, dtype=np.float64)
+    ok = ~np.isnan(v)
+    if not ok.any():
+        return float('nan'), 'none'
+    f, v = f[ok], v[ok]
+    i = int(np.argmin(v))
+    if i == 0 or i == len(v) - 1:
+        return float(f[i]), 'end'
+    (x0, x1, x2), (y0, y1, y2) = f[i - 1:i + 2], v[i - 1:i + 2]
+    # divided differences: y = y1 + b (x - x1) + c (x - x1)(x - x0)
+    d01, d12 = (y1 - y0) / (x1 - x0), (y2 - y1) / (x2 - x1)
+    c = (d12 - d01) / (x2 - x0)
+    if not c > 0:
+        return float(f[i]), 'sample'
+    return float(0.5 * (x0 + x1) - 0.5 * d01 / c), 'vertex'
+
+
+class ThroughFocus:
+    """what :func:`through_focus` returns.
+
+    focs       the focus shifts, as given
+    stats      NumPy structured array [K] (engine.FOCUS_STATS_DTYPE): n, centroid (cx, cy),
+               rms_spot (about the centroid), rms_spot_image_pt, and the OPD's mean, rms about
+               the mean, min and max -- OPD in waves, converted as focus_fan converts
+    rows       [K, 3, R] (x abr, y abr, OPD in waves) per ray and plane, NaN where a ray
+               failed; ``status`` [R] -- with ``rows=True`` only, else None
+    best_focus_spot / best_focus_wavefront (+ ``_kind``): :func:`best_focus` of the RMS
+               spot radius / of the RMS wavefront error"""
+
+    def __init__(self, focs, stats, rows, status):
+        self.focs = np.asarray(focs, dtype=np.float64)
+        self.stats = stats
+        self.rows = rows
+        self.status = status
+        self.best_focus_spot, self.best_focus_spot_kind = best_focus(self.focs, stats['rms_spot'])
+        self.best_focus_wavefront, self.best_focus_wavefront_kind = best_focus(self.focs,
+                                                                               stats['opd_rms'])
+
+    @property
+    def rms_spot(self):
+        return self.stats['rms_spot']
+
+    @property
+    def rms_wavefront(self):
+        return self.stats['opd_rms']
+
+
+def through_focus(opt_model, fld, wvl, focs, num_rays=21, xy=None, image_pt_2d=None,
+                  image_delta=None, rows=False, **kwargs):
+    """A through-focus scan on the device: the pupil grid is traced once and evaluated at
+    every focus shift in ``focs`` (rox_trace_through_focus).  Each plane is built exactly as
+    focus_wavefront / focus_fan build their one focus (rayoptics/raytr/analyses.py:313-342,
+    769-791): setup_pupil_coords at that foc, its reference sphere as rox_wavefront (the
+    pre-calc / calc split on an infinite sphere, :352-357).  ``xy=None`` traces the square
+    pupil grid trace_wavefront does (the field's vignetting box, apertures checked), ``xy=0``
+    / ``1`` the fan trace_fan does.  A focus whose reference sphere the device cannot express
+    raises UnsupportedModelError for the whole call."""
+    from .engine import grid_rays
+    from .table import wavefront_from_model
+    focs = [float(f) for f in np.atleast_1d(focs)]
+    if not 1 <= len(focs) <= abi.MAX_FOCUS_PLANES:
+        raise ValueError(f'through_focus: 1 to {abi.MAX_FOCUS_PLANES} focus values, got {len(focs)}')
+    planes = []
+    for foc in focs:
+        ref_sphere, cr_pkg = _setup_pupil_coords(opt_model, fld, wvl, foc, image_pt_2d, image_delta)
+        own = getattr(fld, 'rox_wavefront', None)       # table-backed models: prebuilt
+        wf = own if own is not None else wavefront_from_model(opt_model, fld, cr_pkg, ref_sphere)
+        wf = abi.Wavefront.from_buffer_copy(bytes(wf))
+        if wf.kind == abi.WF_INF_FULL:                  # as focus_wavefront / focus_fan
+            wf.kind = abi.WF_INF_SPLIT
+        p = abi.FocusPlane()
+        p.foc = foc
+        p.image_pt[0], p.image_pt[1] = float(ref_sphere[0][0]), float(ref_sphere[0][1])
+        p.wf = wf
+        planes.append(p)
+    fld.chief_ray, fld.ref_sphere = cr_pkg, ref_sphere
+    kw = dict(kwargs)
+    for k in ('output_filter', 'rayerr_filter'):
+        kw.pop(k, None)
+    if xy is None:                                      # trace_wavefront's grid (:735-766)
+        oversize = kw.pop('oversize', 1.)
+        vig_bbox = fld.vignetting_bbox(opt_model['osp']['pupil'], oversize=oversize)
+        kw['check_apertures'] = kw.get('check_apertures', True)
+        kw['apply_vignetting'] = kw.get('apply_vignetting', False)
+        grid = make_grid(vig_bbox[0], vig_bbox[1], num_rays)
+    else:                                               # trace_fan's fan (:277-314)
+        fan_def = _fan_def(xy, num_rays)
+        kw['apply_vignetting'] = kw.get('apply_vignetting', True)
+        grid = make_grid(fan_def[0], fan_def[1], fan_def[2], abi.GRID_FAN)
+    eng, f, wi, opts = _launch_setup(opt_model, fld, wvl, kw, abi.OUT_FAN)
+    out = eng.trace_pupil_grid_focus(f, grid, wi, opts, planes, want_rows=rows)
+    stats, dev_rows = out if rows else (out, None)
+    convert_to_opd = 1 / opt_model.nm_to_sys_units(wvl)
+    stats = stats.copy()
+    for k in ('opd_mean', 'opd_rms', 'opd_min', 'opd_max'):
+        stats[k] = convert_to_opd * stats[k]
+    host_rows = status = None
+    if dev_rows is not None:
+        host_rows, status = dev_rows.to_host()
+        host_rows = np.array(host_rows[:, :, :grid_rays(grid)])
+        host_rows[:, 2] = convert_to_opd * host_rows[:, 2]
+    return ThroughFocus(focs, stats, host_rows, status)
 
 
 # ---- point spread function ------------------------------------------------------

@@ -9,4 +9,5 @@ void launch_even_fast_batch(const LaunchCfg &k, const TraceArgs *items)
 {
     launch_instance_batch<(F_EVEN) | F_FAST>(k, items);
 }
+void launch_even_fast_focus(const LaunchCfg &k, const FocusArgs &a) { launch_instance_focus<(F_EVEN) | F_FAST>(k, a); }
 }  // namespace rox

@@ -9,4 +9,5 @@ void launch_general_fast_batch(const LaunchCfg &k, const TraceArgs *items)
 {
     launch_instance_batch<(F_ALL) | F_FAST>(k, items);
 }
+void launch_general_fast_focus(const LaunchCfg &k, const FocusArgs &a) { launch_instance_focus<(F_ALL) | F_FAST>(k, a); }
 }  // namespace rox

@@ -9,4 +9,5 @@ void launch_lean_fast_batch(const LaunchCfg &k, const TraceArgs *items)
 {
     launch_instance_batch<(0) | F_FAST>(k, items);
 }
+void launch_lean_fast_focus(const LaunchCfg &k, const FocusArgs &a) { launch_instance_focus<(0) | F_FAST>(k, a); }
 }  // namespace rox

@@ -9,4 +9,5 @@ void launch_poly_fast_batch(const LaunchCfg &k, const TraceArgs *items)
 {
     launch_instance_batch<(F_POLY) | F_FAST>(k, items);
 }
+void launch_poly_fast_focus(const LaunchCfg &k, const FocusArgs &a) { launch_instance_focus<(F_POLY) | F_FAST>(k, a); }
 }  // namespace rox

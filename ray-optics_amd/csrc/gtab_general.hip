@@ -13,4 +13,5 @@ void launch_general_gtab_batch(const LaunchCfg &k, const TraceArgs *items)
 {
     launch_instance_batch<F_ALL | F_GTAB>(k, items);
 }
+void launch_general_gtab_focus(const LaunchCfg &k, const FocusArgs &a) { launch_instance_focus<F_ALL | F_GTAB>(k, a); }
 }  // namespace rox

@@ -9,4 +9,5 @@ void launch_evenap_batch(const LaunchCfg &k, const TraceArgs *items)
 {
     launch_instance_batch<F_EVEN | F_APLIST>(k, items);
 }
+void launch_evenap_focus(const LaunchCfg &k, const FocusArgs &a) { launch_instance_focus<F_EVEN | F_APLIST>(k, a); }
 }  // namespace rox

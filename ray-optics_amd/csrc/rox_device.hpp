@@ -211,6 +211,9 @@ enum { AXIS_LIST = 0, AXIS_PRODUCT = 1 };
 // internal output mode of the aiming kernel: no packet stores, the intercept
 // at TraceArgs.probe_surf is kept
 constexpr int MODE_PROBE = 100;
+// internal output mode of the through-focus kernel (rox_trace_through_focus): the ray is traced
+// as for ROX_OUT_FAN, then evaluated at every focus plane of FocusArgs (focus_planes() below)
+constexpr int MODE_FOCUS = 101;
 
 // system features a launch needs; the host picks the leanest instance
 enum { F_EVEN = 1,      // some interface is an EvenPolynomial (Newton code)
@@ -306,6 +309,14 @@ struct TraceArgs {
     rox_field fld;
     rox_opts opts;
     rox_out out;
+};
+
+// the through-focus launch (MODE_FOCUS): a pupil-grid launch plus its focus planes and outputs
+struct FocusArgs : TraceArgs {
+    const rox_focus_plane *planes;  // [n_planes], device memory, read through scalar loads
+    int32_t n_planes;
+    double *focus_rows;             // [n_planes][3][out.ld] or nullptr
+    double *partial;                // FocusAcc [gridDim.x][waves per workgroup][n_planes] or nullptr
 };
 
 // ---------------------------------------------------------------- arithmetic
@@ -2320,6 +2331,112 @@ __host__ __device__ inline int64_t compact_tiles(int64_t n_rays, int32_t want_sm
     return s + (n_rays - s * kSmallTile + kB - 1) / kB;
 }
 
+// ------------------------------------------------------------------ through focus
+// rox_trace_through_focus: a lane has traced its ray once (as for ROX_OUT_FAN) and evaluates it
+// at every focus plane with the very expressions of the FAN epilogue in trace_tiles() -- the
+// same helpers, the same IEEE operations, a plane's foc / image_pt / wf in place of rox_opts':
+// the rows are bit-identical to one FAN launch per plane.
+// Statistics: a wave forms its own (count, means, sums of squared deviations from its means) in
+// two passes over its lanes (butterfly sums), and one lane merges that into the wave's partial
+// record of the plane (Chan, Golub & LeVeque's pairwise update): an OPD of -472 waves that
+// varies by 0.02 keeps its RMS, which sum(w^2)/n - mean^2 loses in cancellation.  No atomics, a
+// fixed order of merges -- the finishing pass (roxtrace.hip) merges the records in index order
+// -- so two identical calls give bit-identical statistics.
+struct FocusAcc {
+    double n;               // rays with status OK
+    double mx, my;          // centroid
+    double m2xy;            // sum of (x - mx)^2 + (y - my)^2
+    double sr2;             // sum of x^2 + y^2 (about image_pt)
+    double mw, m2w;         // OPD mean and sum of (w - mw)^2
+    double wmin, wmax;      // (records start zeroed, n = 0: focus_merge never reads them then)
+};
+constexpr int kFocusStat = sizeof(FocusAcc) / sizeof(double);
+
+__host__ __device__ inline FocusAcc focus_merge(const FocusAcc &a, const FocusAcc &b)
+{
+    if (b.n == 0)
+        return a;
+    if (a.n == 0)
+        return b;
+    FocusAcc r;
+    r.n = a.n + b.n;
+    const double f = b.n / r.n, g = a.n * b.n / r.n;
+    const double dx = b.mx - a.mx, dy = b.my - a.my, dw = b.mw - a.mw;
+    r.mx = a.mx + dx * f;
+    r.my = a.my + dy * f;
+    r.m2xy = (a.m2xy + b.m2xy) + (dx * dx + dy * dy) * g;
+    r.sr2 = a.sr2 + b.sr2;
+    r.mw = a.mw + dw * f;
+    r.m2w = (a.m2w + b.m2w) + dw * dw * g;
+    r.wmin = fmin(a.wmin, b.wmin);
+    r.wmax = fmax(a.wmax, b.wmax);
+    return r;
+}
+
+typedef const __attribute__((address_space(4))) rox_focus_plane *ConstPlanes;
+
+__device__ __forceinline__ double wave_sum(double v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1)
+        v += __shfl_xor(v, o);
+    return v;
+}
+
+template <bool FAST, int kB, class ARGS>
+__device__ __forceinline__ void focus_planes(ARGS &a, const RayEnd &e, const v3 &dir0, bool ok,
+                                             uint32_t voff)
+{
+    const ConstPlanes planes = (ConstPlanes)a.planes;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t row_bytes = a.out.ld * 8;
+    const double op = e.phs + e.opl;
+    const double n_ok = (double)__popcll(__ballot(ok));
+    for (int k = 0; k < a.n_planes; ++k) {
+        const auto &pl = planes[k];
+        double x = 0.0, y = 0.0, w = 0.0;
+        if (ok) {                                   // trace_tiles, ROX_OUT_FAN (analyses.py:258-262)
+            w = pl.wf.kind == ROX_WF_FINITE         // (wave-uniform)
+                ? wave_abr_finite_pup<FAST>(pl.wf, e.ray1_p, dir0, e.rayk_p, e.rayk_d, op)
+                : wave_abr_inf_ref<FAST>(pl.wf, e.ray1_p, dir0, e.rayk_p, e.rayk_d, e.inc, e.ad, op);
+            const double dist = FAST ? pl.foc * rcp_f(e.ad.z) : pl.foc / e.ad.z;
+            x = (e.inc.x + dist * e.ad.x) - pl.image_pt[0];
+            y = (e.inc.y + dist * e.ad.y) - pl.image_pt[1];
+            if (a.focus_rows) {
+                const SegOut so{reinterpret_cast<char *>(a.focus_rows) + (int64_t)k * 3 * row_bytes,
+                                row_bytes, voff};
+                so.put(0, 0, x);
+                so.put(0, 1, y);
+                so.put(0, 2, w);
+            }
+        }
+        if (a.partial && n_ok > 0) {                // (wave-uniform)
+            FocusAcc s;
+            s.n = n_ok;
+            s.mx = wave_sum(x) / n_ok;
+            s.my = wave_sum(y) / n_ok;
+            s.mw = wave_sum(w) / n_ok;
+            s.sr2 = wave_sum(x * x + y * y);
+            const double dx = ok ? x - s.mx : 0.0, dy = ok ? y - s.my : 0.0, dw = ok ? w - s.mw : 0.0;
+            s.m2xy = wave_sum(dx * dx + dy * dy);
+            s.m2w = wave_sum(dw * dw);
+            double lo = ok ? w : __builtin_inf(), hi = ok ? w : -__builtin_inf();
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                lo = fmin(lo, __shfl_xor(lo, o));
+                hi = fmax(hi, __shfl_xor(hi, o));
+            }
+            s.wmin = lo;
+            s.wmax = hi;
+            if (lane == 0) {
+                FocusAcc *rec = reinterpret_cast<FocusAcc *>(a.partial) +
+                                ((size_t)blockIdx.x * (kB / 64) + wave) * a.n_planes + k;
+                *rec = focus_merge(*rec, s);        // (the host zeroes the records: n = 0)
+            }
+        }
+    }
+}
+
 // ------------------------------------------------------------------ the kernel
 // the work of one workgroup on one launch item: its share of the item's ray tiles
 template <int OUT_MODE, int GEN, bool PER_RAY_WVL, int FEAT, bool SMALL, class ARGS>
@@ -2327,6 +2444,7 @@ __device__ __forceinline__ void trace_tiles(ARGS &a)
 {
     constexpr bool kCompact = (OUT_MODE == ROX_OUT_HITS_COMPACT);
     constexpr int kB = block_of(OUT_MODE, FEAT, SMALL);     // threads per workgroup = rays per tile
+    constexpr int kTrace = OUT_MODE == MODE_FOCUS ? ROX_OUT_FAN : OUT_MODE;     // what the trace keeps
 
     const int N = a.n_ifcs;
     extern __shared__ __attribute__((aligned(16))) double lds[];
@@ -2497,11 +2615,11 @@ __device__ __forceinline__ void trace_tiles(ARGS &a)
             }
         }
         if constexpr (kFast)
-            trace_ray_fast<OUT_MODE, PER_RAY_WVL, FEAT>(c, so, pt0, dir0, wi, active, e);
+            trace_ray_fast<kTrace, PER_RAY_WVL, FEAT>(c, so, pt0, dir0, wi, active, e);
         else if constexpr (ROX_REDUCED_STRAIGHT && OUT_MODE != ROX_OUT_FULL)
-            trace_ray_reduced<OUT_MODE, PER_RAY_WVL, FEAT>(c, pt0, dir0, wi, active, e);
+            trace_ray_reduced<kTrace, PER_RAY_WVL, FEAT>(c, pt0, dir0, wi, active, e);
         else
-            trace_ray<OUT_MODE, PER_RAY_WVL, FEAT>(c, so, pt0, dir0, wi, active, e);
+            trace_ray<kTrace, PER_RAY_WVL, FEAT>(c, so, pt0, dir0, wi, active, e);
         if (active) {
             if (PER_RAY_WVL && !wi_ok) {
                 // reported as a miss at the object surface; no packet
@@ -2542,6 +2660,8 @@ __device__ __forceinline__ void trace_tiles(ARGS &a)
             if (a.out.status)
                 a.out.status[r] = (uint8_t)e.status;
         }
+        if constexpr (OUT_MODE == MODE_FOCUS)       // (every lane of the workgroup: wave reductions)
+            focus_planes<kFast, kB>(a, e, dir0, active && e.status == ROX_OK, so.voff);
 
         if (kCompact) {
             // ---- stable compaction of the hits: ballot ranks within the wave, wave counts
@@ -2639,6 +2759,14 @@ ROX_KERNEL_ALIGNED trace_kernel_batch(const BatchArgs b)
     trace_tiles<OUT_MODE, GEN_PUPIL, false, FEAT, SMALL>(items[blockIdx.y]);
 }
 
+// the through-focus kernel: pupil grids at one wavelength, regular workgroups only
+template <int FEAT>
+__global__ void __launch_bounds__(block_of(MODE_FOCUS, FEAT), min_waves_of(MODE_FOCUS, FEAT))
+ROX_KERNEL_ALIGNED focus_kernel(const FocusArgs a)
+{
+    trace_tiles<MODE_FOCUS, GEN_PUPIL, false, FEAT, false>(a);
+}
+
 // ------------------------------------------------------------------ launching
 struct LaunchCfg {
     int gen;            // GEN_*
@@ -2712,6 +2840,18 @@ inline void launch_instance(const LaunchCfg &k, const TraceArgs &a)
         launch_mode<GEN_RAYS, true, FEAT>(k, a);
     else
         launch_mode<GEN_RAYS, false, FEAT>(k, a);
+}
+
+// the through-focus kernel of one feature instance (the table source of its reduced-output modes)
+template <int FEAT>
+inline void launch_instance_focus(const LaunchCfg &k, const FocusArgs &a)
+{
+    constexpr int FR = FEAT | gtab_of(FEAT, (FEAT & F_FAST) != 0, ROX_OUT_HITS);
+    auto kern = focus_kernel<FR>;
+    if (k.lds > kDefaultDynLds)
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds);
+    hipLaunchKernelGGL(kern, k.grid, dim3(block_of(MODE_FOCUS, FR)), k.lds, k.stream, a);
 }
 
 // the batched form (trace_kernel_batch): pupil grids, one wavelength per item
@@ -2807,6 +2947,23 @@ void launch_poly_fast_batch(const LaunchCfg &, const TraceArgs *);
 void launch_aplist_fast_batch(const LaunchCfg &, const TraceArgs *);
 void launch_evenap_fast_batch(const LaunchCfg &, const TraceArgs *);
 void launch_general_fast_batch(const LaunchCfg &, const TraceArgs *);
+
+// ... and their through-focus kernels (rox_trace_through_focus; same translation units)
+void launch_lean_focus(const LaunchCfg &, const FocusArgs &);
+void launch_even_focus(const LaunchCfg &, const FocusArgs &);
+void launch_radial_focus(const LaunchCfg &, const FocusArgs &);
+void launch_poly_focus(const LaunchCfg &, const FocusArgs &);
+void launch_aplist_focus(const LaunchCfg &, const FocusArgs &);
+void launch_evenap_focus(const LaunchCfg &, const FocusArgs &);
+void launch_general_focus(const LaunchCfg &, const FocusArgs &);
+void launch_general_gtab_focus(const LaunchCfg &, const FocusArgs &);
+void launch_lean_fast_focus(const LaunchCfg &, const FocusArgs &);
+void launch_even_fast_focus(const LaunchCfg &, const FocusArgs &);
+void launch_radial_fast_focus(const LaunchCfg &, const FocusArgs &);
+void launch_poly_fast_focus(const LaunchCfg &, const FocusArgs &);
+void launch_aplist_fast_focus(const LaunchCfg &, const FocusArgs &);
+void launch_evenap_fast_focus(const LaunchCfg &, const FocusArgs &);
+void launch_general_fast_focus(const LaunchCfg &, const FocusArgs &);
 
 // the pack pass of two-pass packed hits (csrc/pack.hip): a plain ROX_OUT_HITS launch has left
 // (x, y)[2][ld] and status[n_rays]; survivors go to dst in ray order, exactly where the fused

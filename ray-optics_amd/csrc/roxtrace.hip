@@ -218,6 +218,15 @@ struct StreamCtx {
     uint64_t *d_btiles = nullptr;       // ... and [items][tiles] look-back states
     int64_t btickets_cap = 0, btiles_cap = 0;
     uint32_t bepoch = 0;
+    // rox_trace_through_focus: planes, partial records and statistics of a call (grow-only)
+    char *d_focus = nullptr;
+    size_t focus_cap = 0;
+    // ... and the pinned block the planes are copied from (the caller's array may be pageable
+    // and is free to go when the call returns): rewritten only after the copy that last read
+    // it has completed (focus_ev)
+    rox_focus_plane *h_focus = nullptr;
+    int32_t h_focus_cap = 0;
+    hipEvent_t focus_ev = nullptr;
     // Everything a pupil-grid call does between reading / rewriting the cached axes
     // (prepare_grid) and handing its launches to the stream is one critical section per
     // stream: two host threads enqueueing on the SAME stream take turns (their launches run
@@ -1135,6 +1144,78 @@ int prepare_grid(rox_system *sys, const rox_field *fld, const rox_grid *grid, in
     return 0;
 }
 
+// ---- rox_trace_through_focus
+void launch_focus_feat(int inst, const LaunchCfg &k, const FocusArgs &a)
+{
+    typedef void (*fn)(const LaunchCfg &, const FocusArgs &);
+    static const fn fns[] = {launch_lean_focus, launch_even_focus, launch_radial_focus, launch_poly_focus,
+                             launch_aplist_focus, launch_evenap_focus, launch_general_focus};
+    static const fn fast[] = {launch_lean_fast_focus, launch_even_fast_focus, launch_radial_fast_focus,
+                              launch_poly_fast_focus, launch_aplist_fast_focus, launch_evenap_fast_focus,
+                              launch_general_fast_focus};
+    if (k.gtab)
+        launch_general_gtab_focus(k, a);
+    else
+        (k.fast ? fast : fns)[inst](k, a);
+}
+
+// Workgroups per CU of a through-focus launch: its 512-thread workgroups hold 4 waves per SIMD
+// (two per CU) and grid-stride over the tiles, so that the partial records -- one per
+// (wave, plane) -- stay few: 2 x 256 x 8 x 72 B = 288 KiB per plane on 256 CUs.
+constexpr int kFocusBlocksPerCu = 2;
+constexpr int kFocusFinishBlock = 256;
+
+// the finishing pass: block k merges plane k's partial records -- thread t the records t, t + 256,
+// ... in turn, then the lanes pairwise (the lower lane's first), then the four waves in order --
+// and forms its statistics
+__device__ inline FocusAcc shfl_xor_acc(const FocusAcc &a, int o)
+{
+    FocusAcc r;
+    const double *s = &a.n;
+    double *d = &r.n;
+    for (int j = 0; j < kFocusStat; ++j)
+        d[j] = __shfl_xor(s[j], o);
+    return r;
+}
+
+__global__ void __launch_bounds__(kFocusFinishBlock)
+focus_finish_kernel(const FocusAcc *partial, int64_t n_rec, int32_t n_planes, rox_focus_stats *out)
+{
+    const int k = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    FocusAcc v{};
+    for (int64_t i = threadIdx.x; i < n_rec; i += kFocusFinishBlock)
+        v = focus_merge(v, partial[(size_t)i * n_planes + k]);
+    for (int o = 1; o < 64; o <<= 1) {
+        const FocusAcc p = shfl_xor_acc(v, o);
+        v = (lane & o) ? focus_merge(p, v) : focus_merge(v, p);
+    }
+    __shared__ FocusAcc s[kFocusFinishBlock / 64];
+    if (lane == 0)
+        s[wave] = v;
+    __syncthreads();
+    if (threadIdx.x != 0)
+        return;
+    for (int w = 1; w < kFocusFinishBlock / 64; ++w)
+        v = focus_merge(v, s[w]);
+    rox_focus_stats r;
+    r.n = (int64_t)v.n;
+    if (v.n > 0) {
+        r.cx = v.mx;
+        r.cy = v.my;
+        r.rms_spot = sqrt(v.m2xy / v.n);
+        r.rms_spot_image_pt = sqrt(v.sr2 / v.n);
+        r.opd_mean = v.mw;
+        r.opd_rms = sqrt(v.m2w / v.n);
+        r.opd_min = v.wmin;
+        r.opd_max = v.wmax;
+    } else {
+        const double q = __builtin_nan("");
+        r.cx = r.cy = r.rms_spot = r.rms_spot_image_pt = q;
+        r.opd_mean = r.opd_rms = r.opd_min = r.opd_max = q;
+    }
+    out[k] = r;
+}
+
 // DiffractionGrating constants per (wavelength, interface), doe.py:138-143,
 // with libm pow() for `mu**2` and `T**2` as CPython / NumPy scalars evaluate them.
 // (Called through a volatile pointer: the compiler folds a direct pow(x, 2.0) into x * x,
@@ -1369,6 +1450,10 @@ int rox_system_destroy(rox_system *sys)
         (void)hipHostFree(c->h_items);
         (void)hipFree(c->d_btickets);
         (void)hipFree(c->d_btiles);
+        (void)hipFree(c->d_focus);
+        (void)hipHostFree(c->h_focus);
+        if (c->focus_ev)
+            (void)hipEventDestroy(c->focus_ev);
         for (hipEvent_t ev : c->item_ev)
             if (ev)
                 (void)hipEventDestroy(ev);
@@ -1453,6 +1538,143 @@ int rox_trace_pupil_grid(rox_system *sys, const rox_field *fld, const rox_grid *
     a.out = s.dev;
     rc = launch(sys, a, GEN_PUPIL, st);
     return rc ? rc : unstage_out(s, st);
+}
+
+// One trace of a pupil grid, evaluated at n_planes focus positions (include/roxtrace.h).
+int rox_trace_through_focus(rox_system *sys, const rox_field *fld, const rox_grid *grid,
+                            int32_t wvl_idx, const rox_opts *opts, int32_t n_planes,
+                            const rox_focus_plane *planes, double *rows, int64_t ld, uint8_t *status,
+                            rox_focus_stats *stats, void *stream)
+{
+    // every argument check comes before anything touches a device
+    if (!fld || !grid || !opts)
+        return fail(ROX_E_ARG, "rox_trace_through_focus: null argument");
+    if (n_planes <= 0 || n_planes > ROX_MAX_FOCUS_PLANES)
+        return fail(ROX_E_ARG, "rox_trace_through_focus: n_planes %d outside [1, %d]", n_planes,
+                    ROX_MAX_FOCUS_PLANES);
+    if (!planes)
+        return fail(ROX_E_ARG, "rox_trace_through_focus: planes is null");
+    if (!rows && !stats)
+        return fail(ROX_E_ARG, "rox_trace_through_focus: rows and stats are both null");
+    if (opts->out_mode != ROX_OUT_FAN)
+        return fail(ROX_E_ARG, "rox_trace_through_focus: out_mode must be ROX_OUT_FAN (got %d)", opts->out_mode);
+    if (opts->flags & (ROX_HOST_POINTERS | ROX_HITS_APPEND))
+        return fail(ROX_E_ARG, "rox_trace_through_focus: device pointers only, no ROX_HOST_POINTERS / "
+                               "ROX_HITS_APPEND");
+    if (grid->num < 1)
+        return fail(ROX_E_ARG, "rox_trace_through_focus: grid.num must be >= 1");
+    const int64_t R = grid->kind == ROX_GRID_FAN ? grid->num
+                    : (int64_t)(grid->row_count > 0 ? grid->row_count : grid->num) * grid->num;
+    if (rows && ld < R)
+        return fail(ROX_E_ARG, "rox_trace_through_focus: ld (%lld) < rays (%lld)", (long long)ld, (long long)R);
+    if (R > (int64_t(1) << 28))
+        return fail(ROX_E_UNSUPPORTED, "rox_trace_through_focus: %lld rays (max 2^28 per call)", (long long)R);
+    for (int32_t p = 0; p < n_planes; ++p) {
+        const rox_wavefront &w = planes[p].wf;
+        if (!(w.ref_radius != 0.0) || w.kind < ROX_WF_FINITE || w.kind > ROX_WF_INF_SPLIT)
+            return fail(ROX_E_ARG, "rox_trace_through_focus: plane %d: bad wf (ref_radius %g, kind %d)", p,
+                        w.ref_radius, w.kind);
+    }
+    if (!sys)
+        return fail(ROX_E_ARG, "rox_trace_through_focus: null system");
+    if (wvl_idx < 0 || wvl_idx >= sys->n_wvls)
+        return fail(ROX_E_ARG, "rox_trace_through_focus: wvl_idx %d out of range", wvl_idx);
+
+    hipStream_t st = (hipStream_t)stream;
+    auto enq = enqueue_lock(sys, st);
+    StreamCtx *cx = ctx_for(sys, st);
+    if (!cx)
+        return fail(ROX_E_NOMEM, "out of host memory");
+    // planes, then the partial records, then the statistics (when they go to host memory)
+    const int bs_max = block_of(MODE_FOCUS, F_ALL) > block_of(MODE_FOCUS, 0) ? block_of(MODE_FOCUS, F_ALL)
+                                                                               : block_of(MODE_FOCUS, 0);
+    const int64_t cap_blocks = (int64_t)sys->num_cus * kFocusBlocksPerCu;
+    const size_t b_planes = ((size_t)n_planes * sizeof(rox_focus_plane) + 255) & ~size_t(255);
+    const size_t b_part = stats ? (size_t)cap_blocks * (bs_max / 64) * n_planes * sizeof(FocusAcc) : 0;
+    const size_t b_stats = ((size_t)n_planes * sizeof(rox_focus_stats) + 255) & ~size_t(255);
+    const size_t need = b_planes + b_part + b_stats;
+    if (need > cx->focus_cap) {
+        if (cx->d_focus)
+            HIP_TRY(hipFree(cx->d_focus));          // synchronises: no launch still uses it
+        cx->d_focus = nullptr;
+        cx->focus_cap = 0;
+        HIP_TRY(hipMalloc(&cx->d_focus, need));
+        cx->focus_cap = need;
+    }
+    rox_focus_plane *d_planes = (rox_focus_plane *)cx->d_focus;
+    double *d_part = (double *)(cx->d_focus + b_planes);
+    rox_focus_stats *d_stats = (rox_focus_stats *)(cx->d_focus + b_planes + b_part);
+
+    // a FAN launch's arguments (plane 0 in rox_opts: prepare_grid validates them as such; the
+    // kernel reads planes[]); a stats-only call names the scratch as seg, which is never written
+    rox_opts o = *opts;
+    o.foc = planes[0].foc;
+    o.image_pt[0] = planes[0].image_pt[0];
+    o.image_pt[1] = planes[0].image_pt[1];
+    o.wf = planes[0].wf;
+    rox_out out{};
+    out.seg = rows ? rows : d_part;
+    out.ld = rows ? ld : R;
+    out.status = status;
+    FocusArgs f;
+    int rc = prepare_grid(sys, fld, grid, wvl_idx, &o, &out, st, f);
+    if (rc)
+        return rc;
+    LaunchCfg k;
+    int inst;
+    rc = launch_setup(sys, f, GEN_PUPIL, false, st, k, inst);
+    if (rc)
+        return rc;
+    f.out.seg = nullptr;
+    f.ray_base = 0;
+    f.in_ld = R;
+    f.planes = d_planes;
+    f.n_planes = n_planes;
+    f.focus_rows = rows;
+    f.partial = stats ? d_part : nullptr;
+    const int bs = block_of(MODE_FOCUS, kInstances[inst]);
+    int64_t blocks = (R + bs - 1) / bs;
+    if (blocks > cap_blocks)
+        blocks = cap_blocks;
+    k.grid = dim3((unsigned)blocks);
+    if (!cx->focus_ev)
+        HIP_TRY(hipEventCreateWithFlags(&cx->focus_ev, hipEventDisableTiming));
+    else
+        HIP_TRY(hipEventSynchronize(cx->focus_ev));     // the previous call's copy has read h_focus
+    if (n_planes > cx->h_focus_cap) {
+        if (cx->h_focus)
+            HIP_TRY(hipHostFree(cx->h_focus));
+        cx->h_focus = nullptr;
+        cx->h_focus_cap = 0;
+        HIP_TRY(hipHostMalloc((void **)&cx->h_focus, sizeof(rox_focus_plane) * ROX_MAX_FOCUS_PLANES));
+        cx->h_focus_cap = ROX_MAX_FOCUS_PLANES;
+    }
+    memcpy(cx->h_focus, planes, sizeof(rox_focus_plane) * (size_t)n_planes);
+    HIP_TRY(hipMemcpyAsync(d_planes, cx->h_focus, sizeof(rox_focus_plane) * (size_t)n_planes,
+                           hipMemcpyHostToDevice, st));
+    HIP_TRY(hipEventRecord(cx->focus_ev, st));
+    if (stats)      // every wave merges into its records: they start at n = 0
+        HIP_TRY(hipMemsetAsync(d_part, 0, (size_t)blocks * (bs / 64) * n_planes * sizeof(FocusAcc), st));
+    launch_focus_feat(inst, k, f);
+    HIP_TRY(hipGetLastError());
+    if (!stats)
+        return 0;
+    hipPointerAttribute_t at;
+    bool dev_dst = false;
+    if (hipPointerGetAttributes(&at, stats) == hipSuccess)
+        dev_dst = at.type == hipMemoryTypeDevice;
+    else
+        (void)hipGetLastError();
+    hipLaunchKernelGGL(focus_finish_kernel, dim3((unsigned)n_planes), dim3(kFocusFinishBlock), 0, st,
+                       (const FocusAcc *)d_part,
+                       blocks * (bs / 64), n_planes, dev_dst ? stats : d_stats);
+    HIP_TRY(hipGetLastError());
+    if (dev_dst)
+        return 0;
+    HIP_TRY(hipMemcpyAsync(stats, d_stats, sizeof(rox_focus_stats) * (size_t)n_planes, hipMemcpyDeviceToHost, st));
+    enq.unlock();
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
 }
 
 // Several pupil grids of one system in ONE launch: item i traces `grid` for field flds[i]

@@ -132,6 +132,25 @@ def _np_dtypes(torch):
                            torch.int64: np.int64})
 
 
+# rox_focus_stats (include/roxtrace.h) as a NumPy record: what trace_pupil_grid_focus returns
+FOCUS_STATS_DTYPE = np.dtype([(name, np.int64 if name == 'n' else np.float64)
+                              for name, _t in abi.FocusStats._fields_])
+assert FOCUS_STATS_DTYPE.itemsize == C.sizeof(abi.FocusStats)
+
+
+class FocusRows:
+    """the per-ray rows of a through-focus launch on the device: ``rows`` [K, 3, R] (x abr,
+    y abr, OPD in system units; rays that fail keep NaN) and ``status`` [R]"""
+
+    def __init__(self, rows, status):
+        self.rows = rows
+        self.status = status
+
+    def to_host(self):
+        """(rows, status) as NumPy arrays"""
+        return self.rows.cpu().numpy(), self.status.cpu().numpy()
+
+
 def padded_ld(R):
     """row pitch (in doubles) of the SoA packet buffer.  Rows exactly 2^k bytes
     apart put one ray's 130 packet components on the same HBM channel; a pitch
@@ -827,6 +846,37 @@ class TraceEngine:
             raise EngineError('spot_stats reads the rows of a ROX_OUT_HITS launch')
         return self._spot_stats(res.seg.data_ptr(), res.ld, res.status.data_ptr(), None, res.R,
                                 abi.SPOT_ROWS, x_edges, y_edges)
+
+    @_in_flight
+    def trace_pupil_grid_focus(self, fld, grid, wvl_idx, opts, planes, want_rows=False,
+                               want_stats=True):
+        """rox_trace_through_focus: trace the pupil grid once and evaluate it at every focus
+        plane (``planes``: a sequence of abi.FocusPlane, a FAN launch's foc / image_pt / wf
+        each).  ``opts.out_mode`` must be OUT_FAN.  Returns the per-plane statistics as a
+        NumPy structured array of FOCUS_STATS_DTYPE (None with ``want_stats=False``) and,
+        with ``want_rows``, ``(stats, FocusRows)`` -- rows bit-identical to one
+        ``trace_pupil_grid`` FAN launch per plane."""
+        t = self.torch
+        planes = list(planes)
+        K = len(planes)
+        p_arr = (abi.FocusPlane * max(K, 1))(*planes)
+        R = grid_rays(grid)
+        ld = padded_ld(R)
+        rows = status = None
+        if want_rows:
+            rows = t.full((max(K, 1), 3, ld), float('nan'), dtype=t.float64, device=self.device)
+            status = t.empty((R,), dtype=t.uint8, device=self.device)
+        stats = np.empty(max(K, 1), dtype=FOCUS_STATS_DTYPE) if want_stats else None
+        with t.cuda.device(self.device):
+            _check(self.lib.rox_trace_through_focus(
+                self._handle, C.byref(fld), C.byref(grid), int(wvl_idx), C.byref(opts), K, p_arr,
+                rows.data_ptr() if rows is not None else None, ld,
+                status.data_ptr() if status is not None else None,
+                stats.ctypes.data if stats is not None else None, self._stream()),
+                'rox_trace_through_focus')
+        if not want_rows:
+            return stats
+        return stats, FocusRows(rows[:, :, :R], status)
 
     def _spot_stats(self, seg_ptr, ld, status_ptr, n_hits_ptr, n, layout, x_edges, y_edges):
         summ = abi.SpotSummary()
