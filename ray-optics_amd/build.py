@@ -67,6 +67,15 @@ def hipcc():
     raise RuntimeError('hipcc not found')
 
 
+def jobs():
+    """compiler processes at once: MAX_JOBS when set, else one per CPU up to 16 (os.cpu_count()
+    counts the whole host, not the CPUs a shared build machine grants a command)"""
+    env = os.environ.get('MAX_JOBS', '').strip()
+    if env.isdigit() and int(env) > 0:
+        return int(env)
+    return min(16, os.cpu_count() or 4)
+
+
 def sources():
     return sorted(glob.glob(os.path.join(CSRC, '*.hip')))
 
@@ -122,7 +131,7 @@ def build(force=False, extra=(), out=None):
             os.replace(tmp, obj)
         return obj
 
-    with concurrent.futures.ThreadPoolExecutor(max_workers=os.cpu_count() or 4) as ex:
+    with concurrent.futures.ThreadPoolExecutor(max_workers=jobs()) as ex:
         objs = list(ex.map(compile_one, sources()))
     tmp = lib + f'.tmp{os.getpid()}'
     subprocess.check_call([cc, '--offload-arch=gfx950', '-shared', '-fPIC',

@@ -4,10 +4,5 @@
 #include "rox_device.hpp"
 
 namespace rox {
-void launch_even_fast(const LaunchCfg &k, const TraceArgs &a) { launch_instance<(F_EVEN) | F_FAST>(k, a); }
-void launch_even_fast_batch(const LaunchCfg &k, const TraceArgs *items)
-{
-    launch_instance_batch<(F_EVEN) | F_FAST>(k, items);
-}
-void launch_even_fast_focus(const LaunchCfg &k, const FocusArgs &a) { launch_instance_focus<(F_EVEN) | F_FAST>(k, a); }
+ROX_TRACE_INSTANCE(even_fast, F_EVEN | F_FAST)
 }  // namespace rox

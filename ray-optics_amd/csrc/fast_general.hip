@@ -4,10 +4,5 @@
 #include "rox_device.hpp"
 
 namespace rox {
-void launch_general_fast(const LaunchCfg &k, const TraceArgs &a) { launch_instance<(F_ALL) | F_FAST>(k, a); }
-void launch_general_fast_batch(const LaunchCfg &k, const TraceArgs *items)
-{
-    launch_instance_batch<(F_ALL) | F_FAST>(k, items);
-}
-void launch_general_fast_focus(const LaunchCfg &k, const FocusArgs &a) { launch_instance_focus<(F_ALL) | F_FAST>(k, a); }
+ROX_TRACE_INSTANCE(general_fast, F_ALL | F_FAST)
 }  // namespace rox

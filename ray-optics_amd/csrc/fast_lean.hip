@@ -4,10 +4,5 @@
 #include "rox_device.hpp"
 
 namespace rox {
-void launch_lean_fast(const LaunchCfg &k, const TraceArgs &a) { launch_instance<(0) | F_FAST>(k, a); }
-void launch_lean_fast_batch(const LaunchCfg &k, const TraceArgs *items)
-{
-    launch_instance_batch<(0) | F_FAST>(k, items);
-}
-void launch_lean_fast_focus(const LaunchCfg &k, const FocusArgs &a) { launch_instance_focus<(0) | F_FAST>(k, a); }
+ROX_TRACE_INSTANCE(lean_fast, F_FAST)
 }  // namespace rox

@@ -8,10 +8,5 @@
 #include "rox_device.hpp"
 
 namespace rox {
-void launch_general_gtab(const LaunchCfg &k, const TraceArgs &a) { launch_instance<F_ALL | F_GTAB>(k, a); }
-void launch_general_gtab_batch(const LaunchCfg &k, const TraceArgs *items)
-{
-    launch_instance_batch<F_ALL | F_GTAB>(k, items);
-}
-void launch_general_gtab_focus(const LaunchCfg &k, const FocusArgs &a) { launch_instance_focus<F_ALL | F_GTAB>(k, a); }
+ROX_TRACE_INSTANCE(general_gtab, F_ALL | F_GTAB)
 }  // namespace rox

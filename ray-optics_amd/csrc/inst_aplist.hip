@@ -3,7 +3,5 @@
 #include "rox_device.hpp"
 
 namespace rox {
-void launch_aplist(const LaunchCfg &k, const TraceArgs &a) { launch_instance<F_APLIST>(k, a); }
-void launch_aplist_batch(const LaunchCfg &k, const TraceArgs *items) { launch_instance_batch<F_APLIST>(k, items); }
-void launch_aplist_focus(const LaunchCfg &k, const FocusArgs &a) { launch_instance_focus<F_APLIST>(k, a); }
+ROX_TRACE_INSTANCE(aplist, F_APLIST)
 }  // namespace rox

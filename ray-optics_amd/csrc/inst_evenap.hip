@@ -4,10 +4,5 @@
 #include "rox_device.hpp"
 
 namespace rox {
-void launch_evenap(const LaunchCfg &k, const TraceArgs &a) { launch_instance<F_EVEN | F_APLIST>(k, a); }
-void launch_evenap_batch(const LaunchCfg &k, const TraceArgs *items)
-{
-    launch_instance_batch<F_EVEN | F_APLIST>(k, items);
-}
-void launch_evenap_focus(const LaunchCfg &k, const FocusArgs &a) { launch_instance_focus<F_EVEN | F_APLIST>(k, a); }
+ROX_TRACE_INSTANCE(evenap, F_EVEN | F_APLIST)
 }  // namespace rox

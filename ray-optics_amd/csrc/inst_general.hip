@@ -3,7 +3,5 @@
 #include "rox_device.hpp"
 
 namespace rox {
-void launch_general(const LaunchCfg &k, const TraceArgs &a) { launch_instance<F_ALL>(k, a); }
-void launch_general_batch(const LaunchCfg &k, const TraceArgs *items) { launch_instance_batch<F_ALL>(k, items); }
-void launch_general_focus(const LaunchCfg &k, const FocusArgs &a) { launch_instance_focus<F_ALL>(k, a); }
+ROX_TRACE_INSTANCE(general, F_ALL)
 }  // namespace rox

@@ -3,7 +3,5 @@
 #include "rox_device.hpp"
 
 namespace rox {
-void launch_poly(const LaunchCfg &k, const TraceArgs &a) { launch_instance<F_POLY>(k, a); }
-void launch_poly_batch(const LaunchCfg &k, const TraceArgs *items) { launch_instance_batch<F_POLY>(k, items); }
-void launch_poly_focus(const LaunchCfg &k, const FocusArgs &a) { launch_instance_focus<F_POLY>(k, a); }
+ROX_TRACE_INSTANCE(poly, F_POLY)
 }  // namespace rox

@@ -26,18 +26,12 @@
 
 #include <cfloat>
 #include <cstdint>
-#include <cstdio>
-#include <mutex>
-#include <new>
-#include <vector>
 
-#include "../../include/roxtrace.h"
-
-namespace rox {
-int host_fail(int code, const char *msg);     // roxtrace.hip: sets rox_last_error()
-}
+#include "rox_host.hpp"
 
 namespace {
+
+constexpr char kHipWhere[] = "rox_calc_psf: ";
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 
@@ -182,44 +176,11 @@ __global__ void psf_scale(double *ap, int64_t count, const unsigned long long *m
 
 // grow-only workspace per (device, stream)
 struct Workspace {
-    int device = 0;
-    hipStream_t stream = nullptr;
     char *buf = nullptr;
     size_t cap = 0;
     int64_t zeroed_for[3] = {0, 0, 0};      // (n, M, bytes) the padded planes were last zeroed for
-    std::mutex mu;          // one call at a time builds / enqueues on this workspace
 };
-std::mutex g_mu;
-std::vector<Workspace *> g_ws;
-
-Workspace *workspace_for(int device, hipStream_t st)
-{
-    std::lock_guard<std::mutex> lock(g_mu);
-    for (Workspace *w : g_ws)
-        if (w->device == device && w->stream == st)
-            return w;
-    Workspace *w = new (std::nothrow) Workspace;
-    if (w) {
-        w->device = device;
-        w->stream = st;
-        g_ws.push_back(w);
-    }
-    return w;
-}
-
-int hip_fail(const char *what, hipError_t e)
-{
-    char msg[256];
-    snprintf(msg, sizeof msg, "rox_calc_psf: %s: %s", what, hipGetErrorString(e));
-    return rox::host_fail(ROX_E_HIP, msg);
-}
-
-#define PSF_TRY(expr)                                   \
-    do {                                                \
-        hipError_t e_ = (expr);                         \
-        if (e_ != hipSuccess)                           \
-            return hip_fail(#expr, e_);                 \
-    } while (0)
+rox::PerStream<Workspace> g_ws;
 
 }  // namespace
 
@@ -242,13 +203,14 @@ extern "C" int rox_calc_psf(const double *opd, int32_t ndim, int32_t maxdim, dou
         return rox::host_fail(ROX_E_ARG, "rox_calc_psf: maxdim > 32768");
     hipStream_t st = (hipStream_t)stream;
     int device = 0;
-    PSF_TRY(hipGetDevice(&device));
-    Workspace *ws = workspace_for(device, st);
-    if (!ws)
+    HIP_TRY(hipGetDevice(&device));
+    auto *slot = g_ws.get(device, st);
+    if (!slot)
         return rox::host_fail(ROX_E_NOMEM, "rox_calc_psf: out of host memory");
     // calls on one stream share the workspace: enqueue them whole, one after the other
     // (stream order then keeps their kernels apart); host-pointer calls hold it until done
-    std::lock_guard<std::mutex> turn(ws->mu);
+    std::lock_guard<std::mutex> turn(slot->mu);
+    Workspace *ws = &slot->data;
 
     const bool host = (flags & ROX_HOST_POINTERS) != 0;
     const int64_t kp = round_up(n, kKBlock), mp = round_up(M, kTile), np_ = round_up(n, kTile);
@@ -258,12 +220,7 @@ extern "C" int rox_calc_psf(const double *opd, int32_t ndim, int32_t maxdim, dou
     const size_t zeroed = 4 * pl_f + 2 * pl_p + 64;         // F, T, P^T planes + the maximum
     const size_t total = zeroed + b_opd + b_psf + 64;
     if (ws->cap < total) {
-        if (ws->buf)
-            PSF_TRY(hipFree(ws->buf));
-        ws->buf = nullptr;
-        ws->cap = 0;
-        PSF_TRY(hipMalloc((void **)&ws->buf, total));
-        ws->cap = total;
+        HIP_TRY(rox::regrow(ws->buf, ws->cap, total, total));
         ws->zeroed_for[0] = ws->zeroed_for[1] = ws->zeroed_for[2] = 0;
     }
     char *p = ws->buf;
@@ -285,13 +242,13 @@ extern "C" int rox_calc_psf(const double *opd, int32_t ndim, int32_t maxdim, dou
     const bool new_shape = ws->zeroed_for[0] != n || ws->zeroed_for[1] != M ||
                            ws->zeroed_for[2] != (int64_t)zeroed;
     if (new_shape) {
-        PSF_TRY(hipMemsetAsync(ws->buf, 0, zeroed, st));
+        HIP_TRY(hipMemsetAsync(ws->buf, 0, zeroed, st));
         ws->zeroed_for[0] = n; ws->zeroed_for[1] = M; ws->zeroed_for[2] = (int64_t)zeroed;
     }
     const double *src = opd;
     double *dst = psf;
     if (host) {
-        PSF_TRY(hipMemcpyAsync(d_opd, opd, b_opd, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_opd, opd, b_opd, hipMemcpyHostToDevice, st));
         src = d_opd;
         dst = d_psf;
     }
@@ -314,10 +271,10 @@ extern "C" int rox_calc_psf(const double *opd, int32_t ndim, int32_t maxdim, dou
                            tr, ti, fr, fi, (int)kp, M, M, dst, (double *)nullptr, M, maxbits);
     }
     hipLaunchKernelGGL(psf_scale, dim3(1024), dim3(256), 0, st, dst, (int64_t)M * M, maxbits);
-    PSF_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     if (host) {
-        PSF_TRY(hipMemcpyAsync(psf, d_psf, b_psf, hipMemcpyDeviceToHost, st));
-        PSF_TRY(hipStreamSynchronize(st));
+        HIP_TRY(hipMemcpyAsync(psf, d_psf, b_psf, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
     }
     return 0;
 }

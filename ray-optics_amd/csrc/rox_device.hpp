@@ -2909,61 +2909,36 @@ inline void launch_instance_batch(const LaunchCfg &k, const TraceArgs *items)
     }
 }
 
-// the feature instances that are compiled (one translation unit each,
-// csrc/inst_*.hip); the host launches the first one that covers the need
+// The host entry points of one trace instance: the plain, batched and through-focus launches
+// of launch_instance*<FEAT>.  ROX_TRACE_INSTANCE defines them as one table entry trace_<name>
+// in the instance's own translation unit.  (The entries are not const: clang would emit a const
+// namespace-scope object into the device code object as well.)
+struct TraceInstanceFns {
+    void (*launch)(const LaunchCfg &, const TraceArgs &);
+    void (*batch)(const LaunchCfg &, const TraceArgs *);
+    void (*focus)(const LaunchCfg &, const FocusArgs &);
+};
+#define ROX_TRACE_INSTANCE(name, FEAT)                                                          \
+    TraceInstanceFns trace_##name = {launch_instance<FEAT>, launch_instance_batch<FEAT>, \
+                                     launch_instance_focus<FEAT>};
+
+// The feature instances that are compiled, X(name, FEAT) in kInstances order: one translation
+// unit each, csrc/inst_<name>.hip (trace_<name>), and a tolerance-mode twin csrc/fast_<name>.hip
+// (trace_<name>_fast: FEAT | F_FAST).  The host launches the first one that covers the need.
 // (F_EVEN | F_APLIST: what a Zemax import with an EVENASPH surface needs -- every .zmx interface
 // carries a clear-aperture list.  BASELINE configs[2]'s file ran on the general instance until
 // round 5: 392 wave-VALU per wave-surface against 300 lean, profiles/r05_valu_account.json.)
-constexpr int kInstances[] = {0, F_EVEN, F_RADIAL, F_POLY, F_APLIST, F_EVEN | F_APLIST, F_ALL};
-void launch_lean(const LaunchCfg &, const TraceArgs &);
-void launch_even(const LaunchCfg &, const TraceArgs &);
-void launch_radial(const LaunchCfg &, const TraceArgs &);
-void launch_poly(const LaunchCfg &, const TraceArgs &);
-void launch_aplist(const LaunchCfg &, const TraceArgs &);
-void launch_evenap(const LaunchCfg &, const TraceArgs &);
-void launch_general(const LaunchCfg &, const TraceArgs &);
-void launch_lean_batch(const LaunchCfg &, const TraceArgs *);
-void launch_even_batch(const LaunchCfg &, const TraceArgs *);
-void launch_radial_batch(const LaunchCfg &, const TraceArgs *);
-void launch_poly_batch(const LaunchCfg &, const TraceArgs *);
-void launch_aplist_batch(const LaunchCfg &, const TraceArgs *);
-void launch_evenap_batch(const LaunchCfg &, const TraceArgs *);
-void launch_general_batch(const LaunchCfg &, const TraceArgs *);
-// the general instance over a table left in global memory (csrc/gtab_general.hip)
-void launch_general_gtab(const LaunchCfg &, const TraceArgs &);
-void launch_general_gtab_batch(const LaunchCfg &, const TraceArgs *);
-// ... and their tolerance-mode twins (csrc/fast_*.hip: kInstances[i] | F_FAST)
-void launch_lean_fast(const LaunchCfg &, const TraceArgs &);
-void launch_even_fast(const LaunchCfg &, const TraceArgs &);
-void launch_radial_fast(const LaunchCfg &, const TraceArgs &);
-void launch_poly_fast(const LaunchCfg &, const TraceArgs &);
-void launch_aplist_fast(const LaunchCfg &, const TraceArgs &);
-void launch_evenap_fast(const LaunchCfg &, const TraceArgs &);
-void launch_general_fast(const LaunchCfg &, const TraceArgs &);
-void launch_lean_fast_batch(const LaunchCfg &, const TraceArgs *);
-void launch_even_fast_batch(const LaunchCfg &, const TraceArgs *);
-void launch_radial_fast_batch(const LaunchCfg &, const TraceArgs *);
-void launch_poly_fast_batch(const LaunchCfg &, const TraceArgs *);
-void launch_aplist_fast_batch(const LaunchCfg &, const TraceArgs *);
-void launch_evenap_fast_batch(const LaunchCfg &, const TraceArgs *);
-void launch_general_fast_batch(const LaunchCfg &, const TraceArgs *);
-
-// ... and their through-focus kernels (rox_trace_through_focus; same translation units)
-void launch_lean_focus(const LaunchCfg &, const FocusArgs &);
-void launch_even_focus(const LaunchCfg &, const FocusArgs &);
-void launch_radial_focus(const LaunchCfg &, const FocusArgs &);
-void launch_poly_focus(const LaunchCfg &, const FocusArgs &);
-void launch_aplist_focus(const LaunchCfg &, const FocusArgs &);
-void launch_evenap_focus(const LaunchCfg &, const FocusArgs &);
-void launch_general_focus(const LaunchCfg &, const FocusArgs &);
-void launch_general_gtab_focus(const LaunchCfg &, const FocusArgs &);
-void launch_lean_fast_focus(const LaunchCfg &, const FocusArgs &);
-void launch_even_fast_focus(const LaunchCfg &, const FocusArgs &);
-void launch_radial_fast_focus(const LaunchCfg &, const FocusArgs &);
-void launch_poly_fast_focus(const LaunchCfg &, const FocusArgs &);
-void launch_aplist_fast_focus(const LaunchCfg &, const FocusArgs &);
-void launch_evenap_fast_focus(const LaunchCfg &, const FocusArgs &);
-void launch_general_fast_focus(const LaunchCfg &, const FocusArgs &);
+// Besides these, csrc/gtab_general.hip: the general instance over a table left in global memory
+// (trace_general_gtab).
+#define ROX_TRACE_INSTANCES(X)                                                                 \
+    X(lean, 0) X(even, F_EVEN) X(radial, F_RADIAL) X(poly, F_POLY) X(aplist, F_APLIST)        \
+    X(evenap, F_EVEN | F_APLIST) X(general, F_ALL)
+#define ROX_INSTANCE_FEAT(name, FEAT) FEAT,
+#define ROX_TRACE_DECL(name, FEAT) extern TraceInstanceFns trace_##name, trace_##name##_fast;
+constexpr int kInstances[] = {ROX_TRACE_INSTANCES(ROX_INSTANCE_FEAT)};
+ROX_TRACE_INSTANCES(ROX_TRACE_DECL)
+extern TraceInstanceFns trace_general_gtab;
+#undef ROX_TRACE_DECL
 
 // the pack pass of two-pass packed hits (csrc/pack.hip): a plain ROX_OUT_HITS launch has left
 // (x, y)[2][ld] and status[n_rays]; survivors go to dst in ray order, exactly where the fused
@@ -3022,20 +2997,26 @@ struct VigArgs {
     int32_t wave_per_problem;  // 1: one wave (block) per problem; 0: one lane per problem
 };
 
-// the feature instances the search kernels are compiled for (csrc/search_*.hip, rox_search.hpp);
-// the host launches the first one that covers the system's features
-constexpr int kSearchInstances[] = {0, F_EVEN, F_RADIAL, F_APLIST, F_EVEN | F_APLIST, F_ALL};
-#define ROX_SEARCH_DECL(name)                                          \
-    void launch_aim_##name(const AimArgs &, size_t lds, hipStream_t); \
-    void launch_enp_##name(const EnpArgs &, size_t lds, hipStream_t); \
-    void launch_vig_##name(const VigArgs &, size_t lds, hipStream_t);
-ROX_SEARCH_DECL(lean)
-ROX_SEARCH_DECL(even)
-ROX_SEARCH_DECL(radial)
-ROX_SEARCH_DECL(aplist)
-ROX_SEARCH_DECL(evenap)
-ROX_SEARCH_DECL(general)
-ROX_SEARCH_DECL(general_gtab)
+// The host entry points of one search instance (rox_search.hpp launch_*_instance<FEAT>), defined
+// as one table entry search_<name> by ROX_SEARCH_INSTANCE in csrc/search_<name>.hip (not const,
+// as TraceInstanceFns)
+struct SearchInstanceFns {
+    void (*aim)(const AimArgs &, size_t lds, hipStream_t);
+    void (*enp)(const EnpArgs &, size_t lds, hipStream_t);
+    void (*vig)(const VigArgs &, size_t lds, hipStream_t);
+};
+
+// the feature instances the search kernels are compiled for, X(name, FEAT) in kSearchInstances
+// order; the host launches the first one that covers the system's features.  Besides these,
+// csrc/search_general_gtab.hip: the general instance over a table in global memory.
+#define ROX_SEARCH_INSTANCES(X)                                                                \
+    X(lean, 0) X(even, F_EVEN) X(radial, F_RADIAL) X(aplist, F_APLIST) X(evenap, F_EVEN | F_APLIST) \
+    X(general, F_ALL)
+#define ROX_SEARCH_DECL(name, FEAT) extern SearchInstanceFns search_##name;
+constexpr int kSearchInstances[] = {ROX_SEARCH_INSTANCES(ROX_INSTANCE_FEAT)};
+ROX_SEARCH_INSTANCES(ROX_SEARCH_DECL)
+extern SearchInstanceFns search_general_gtab;
 #undef ROX_SEARCH_DECL
+#undef ROX_INSTANCE_FEAT
 
 }  // namespace rox

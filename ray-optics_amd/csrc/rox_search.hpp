@@ -968,10 +968,10 @@ void launch_aim_instance(const AimArgs &a, size_t lds, hipStream_t st)
     hipLaunchKernelGGL(aim_kernel<FEAT>, dim3(a.wave_per_problem ? a.n : (a.n + 63) / 64), dim3(64), lds, st, a);
 }
 
-// what a translation unit csrc/search_<name>.hip defines for its instance
+// what a translation unit csrc/search_<name>.hip defines for its instance (rox_device.hpp
+// SearchInstanceFns)
 #define ROX_SEARCH_INSTANCE(name, FEAT)                                                          \
-    void launch_aim_##name(const AimArgs &a, size_t lds, hipStream_t st) { launch_aim_instance<FEAT>(a, lds, st); } \
-    void launch_enp_##name(const EnpArgs &a, size_t lds, hipStream_t st) { launch_enp_instance<FEAT>(a, lds, st); } \
-    void launch_vig_##name(const VigArgs &a, size_t lds, hipStream_t st) { launch_vig_instance<FEAT>(a, lds, st); }
+    SearchInstanceFns search_##name = {launch_aim_instance<FEAT>, launch_enp_instance<FEAT>, \
+                                       launch_vig_instance<FEAT>};
 
 }  // namespace rox

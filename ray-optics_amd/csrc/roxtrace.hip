@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "rox_device.hpp"
+#include "rox_host.hpp"
 #include "../../include/roxtrace_diag.h"
 
 #pragma clang fp contract(off)
@@ -159,22 +160,8 @@ __global__ void __launch_bounds__(kBlock) selftest_kernel(uint64_t n, uint64_t s
 
 // ------------------------------------------------------------------ host side
 thread_local char g_err[512] = "";
-
-int fail(int code, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                    \
-    do {                                                                                 \
-        hipError_t e_ = (expr);                                                          \
-        if (e_ != hipSuccess)                                                            \
-            return fail(ROX_E_HIP, "%s: %s", #expr, hipGetErrorString(e_));              \
-    } while (0)
+constexpr char kHipWhere[] = "";        // (HIP_TRY: the messages of the trace entries name no entry)
+int (&fail)(int code, const char *fmt, ...) = rox::host_fail;
 
 // Per-stream launch scratch.  Launches on one stream run in stream order, so
 // they may share it; two streams (or two host threads on two streams) get two
@@ -240,9 +227,13 @@ struct StreamCtx {
 
 }  // namespace
 
-namespace rox {
-// for the other translation units of the library (psf.hip)
-int host_fail(int code, const char *msg) { return fail(code, "%s", msg); }
+int rox::host_fail(int code, const char *fmt, ...)
+{
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_err, sizeof g_err, fmt, ap);
+    va_end(ap);
+    return code;
 }
 
 struct rox_system {
@@ -298,15 +289,10 @@ std::unique_lock<std::mutex> enqueue_lock(rox_system *sys, hipStream_t st)
 int search_block(rox_system *sys, size_t bytes, char *&base)
 {
     if (sys->h_search_cap < bytes) {
-        if (sys->h_search)
-            HIP_TRY(hipHostFree(sys->h_search));
-        sys->h_search = nullptr;
-        sys->h_search_cap = 0;
         size_t cap = size_t(16) << 10;
         while (cap < bytes)
             cap *= 2;
-        HIP_TRY(hipHostMalloc((void **)&sys->h_search, cap, hipHostMallocMapped));
-        sys->h_search_cap = cap;
+        HIP_TRY(regrow(sys->h_search, sys->h_search_cap, cap, cap, hipHostMallocMapped));
     }
     base = sys->h_search;
     return 0;
@@ -581,53 +567,27 @@ int search_lds(const rox_system *sys, size_t &lds, bool &gtab)
     return 0;
 }
 
-#define ROX_SEARCH_DISPATCH(kind, Args)                                              \
-    void launch_##kind(const rox_system *sys, const Args &a, size_t lds, bool gtab, hipStream_t st) \
-    {                                                                                \
-        if (gtab) {                                                                  \
-            launch_##kind##_general_gtab(a, lds, st);                                \
-            return;                                                                  \
-        }                                                                            \
-        switch (pick_search_instance(sys)) {                                         \
-        case 0: launch_##kind##_lean(a, lds, st); break;                             \
-        case 1: launch_##kind##_even(a, lds, st); break;                             \
-        case 2: launch_##kind##_radial(a, lds, st); break;                           \
-        case 3: launch_##kind##_aplist(a, lds, st); break;                           \
-        case 4: launch_##kind##_evenap(a, lds, st); break;                           \
-        default: launch_##kind##_general(a, lds, st); break;                         \
-        }                                                                            \
-    }
-ROX_SEARCH_DISPATCH(aim, AimArgs)
-ROX_SEARCH_DISPATCH(enp, EnpArgs)
-ROX_SEARCH_DISPATCH(vig, VigArgs)
-#undef ROX_SEARCH_DISPATCH
-
-void launch_feat(int inst, const LaunchCfg &k, const TraceArgs &a)
+// the entry points of the search instance a launch takes (gtab: search_lds found the table too
+// large for the LDS)
+const SearchInstanceFns &search_fns(const rox_system *sys, bool gtab)
 {
-    typedef void (*fn)(const LaunchCfg &, const TraceArgs &);
-    static const fn fns[] = {launch_lean, launch_even, launch_radial, launch_poly,
-                             launch_aplist, launch_evenap, launch_general};
-    static const fn fast[] = {launch_lean_fast, launch_even_fast, launch_radial_fast, launch_poly_fast,
-                              launch_aplist_fast, launch_evenap_fast, launch_general_fast};
-    if (k.gtab)
-        launch_general_gtab(k, a);
-    else
-        (k.fast ? fast : fns)[inst](k, a);
+#define ROX_SEARCH_FNS(name, FEAT) &search_##name,
+    static const SearchInstanceFns *const fns[] = {ROX_SEARCH_INSTANCES(ROX_SEARCH_FNS)};
+#undef ROX_SEARCH_FNS
+    return gtab ? search_general_gtab : *fns[pick_search_instance(sys)];
 }
 
-void launch_feat_batch(int inst, const LaunchCfg &k, const TraceArgs *items)
+// the entry points of trace instance kInstances[inst] -- or of its tolerance-mode twin, or of the
+// general instance over a table in global memory -- as launch_setup chose in k
+const TraceInstanceFns &trace_fns(int inst, const LaunchCfg &k)
 {
-    typedef void (*fn)(const LaunchCfg &, const TraceArgs *);
-    static const fn fns[] = {launch_lean_batch, launch_even_batch, launch_radial_batch,
-                             launch_poly_batch, launch_aplist_batch, launch_evenap_batch,
-                             launch_general_batch};
-    static const fn fast[] = {launch_lean_fast_batch, launch_even_fast_batch, launch_radial_fast_batch,
-                              launch_poly_fast_batch, launch_aplist_fast_batch, launch_evenap_fast_batch,
-                              launch_general_fast_batch};
-    if (k.gtab)
-        launch_general_gtab_batch(k, items);
-    else
-        (k.fast ? fast : fns)[inst](k, items);
+#define ROX_TRACE_FNS(name, FEAT) &trace_##name,
+#define ROX_TRACE_FAST_FNS(name, FEAT) &trace_##name##_fast,
+    static const TraceInstanceFns *const fns[] = {ROX_TRACE_INSTANCES(ROX_TRACE_FNS)};
+    static const TraceInstanceFns *const fast[] = {ROX_TRACE_INSTANCES(ROX_TRACE_FAST_FNS)};
+#undef ROX_TRACE_FNS
+#undef ROX_TRACE_FAST_FNS
+    return k.gtab ? trace_general_gtab : *(k.fast ? fast : fns)[inst];
 }
 
 // (initialisations are enqueued on the launch stream itself: a stream created with
@@ -656,13 +616,7 @@ int ensure_compact(StreamCtx *cx, int64_t tiles, hipStream_t st)
     if (rc)
         return rc;
     if (tiles > cx->tiles_cap) {
-        if (cx->d_tiles)
-            HIP_TRY(hipFree(cx->d_tiles));      // synchronises: no launch is still reading it
-        cx->d_tiles = nullptr;
-        cx->tiles_cap = 0;
-        HIP_TRY(hipMalloc(&cx->d_tiles, sizeof(uint64_t) * (size_t)tiles));
-        HIP_TRY(hipMemsetAsync(cx->d_tiles, 0, sizeof(uint64_t) * (size_t)tiles, st));
-        cx->tiles_cap = tiles;
+        HIP_TRY(regrow_zeroed(cx->d_tiles, cx->tiles_cap, tiles, sizeof(uint64_t) * (size_t)tiles, st));
         cx->epoch = 0;
     }
     return 0;
@@ -702,15 +656,8 @@ int ensure_pack_scratch(StreamCtx *cx, int64_t rays, bool need_status)
 {
     const int64_t want = (rays + 511) & ~int64_t(511);
     if (want > cx->pack_cap) {
-        if (cx->d_pack_xy)
-            HIP_TRY(hipFree(cx->d_pack_xy));        // synchronises: no launch still uses it
-        if (cx->d_pack_status)
-            HIP_TRY(hipFree(cx->d_pack_status));
-        cx->d_pack_xy = nullptr;
-        cx->d_pack_status = nullptr;
-        cx->pack_cap = 0;
-        HIP_TRY(hipMalloc(&cx->d_pack_xy, sizeof(double) * 2 * (size_t)want));
-        cx->pack_cap = want;
+        HIP_TRY(release(cx->d_pack_status, cx->pack_cap));      // (made again below, on demand)
+        HIP_TRY(regrow(cx->d_pack_xy, cx->pack_cap, want, sizeof(double) * 2 * (size_t)want));
     }
     if (need_status && !cx->d_pack_status)
         HIP_TRY(hipMalloc(&cx->d_pack_status, (size_t)cx->pack_cap));
@@ -875,7 +822,7 @@ int launch(rox_system *sys, TraceArgs &a, int gen, hipStream_t st)
             int64_t hblocks = (a.n_rays + hb - 1) / hb;
             const int64_t hcap = (int64_t)sys->num_cus * blocks_per_cu(hb);
             kh.grid = dim3((unsigned)(hblocks > hcap ? hcap : hblocks));
-            launch_feat(inst, kh, h);
+            trace_fns(inst, kh).launch(kh, h);
             // pass 2: survivors to their final place, in ray order
             PackArgs p;
             p.status = h.out.status;
@@ -901,7 +848,7 @@ int launch(rox_system *sys, TraceArgs &a, int gen, hipStream_t st)
         if (blocks > cap)
             blocks = cap;
         k.grid = dim3((unsigned)blocks);
-        launch_feat(inst, k, a);
+        trace_fns(inst, k).launch(k, a);
     }
     a.n_rays = total;
     a.out = out0;
@@ -981,26 +928,16 @@ int stage_out(Staged &s, rox_system *sys, hipStream_t st, const rox_opts *o, con
     char *base;
     if (s.bounce) {
         if (cx->h_stage_cap < total) {
-            if (cx->h_stage)
-                HIP_TRY(hipHostFree(cx->h_stage));
-            cx->h_stage = nullptr;
-            cx->h_stage_cap = 0;
             size_t cap = size_t(64) << 10;
             while (cap < total)
                 cap *= 2;
-            HIP_TRY(hipHostMalloc((void **)&cx->h_stage, cap, hipHostMallocMapped));
-            cx->h_stage_cap = cap;
+            HIP_TRY(regrow(cx->h_stage, cx->h_stage_cap, cap, cap, hipHostMallocMapped));
         }
         base = cx->h_stage;
     } else {
         if (cx->d_stage_cap < total) {
-            if (cx->d_stage)
-                HIP_TRY(hipFree(cx->d_stage));
-            cx->d_stage = nullptr;
-            cx->d_stage_cap = 0;
             const size_t cap = total + total / 8;
-            HIP_TRY(hipMalloc((void **)&cx->d_stage, cap));
-            cx->d_stage_cap = cap;
+            HIP_TRY(regrow(cx->d_stage, cx->d_stage_cap, cap, cap));
         }
         base = cx->d_stage;
     }
@@ -1070,13 +1007,8 @@ int ensure_axes(StreamCtx *cx, int32_t num)
 {
     if (num <= cx->axes_cap)
         return 0;
-    if (cx->d_axes)
-        HIP_TRY(hipFree(cx->d_axes));       // synchronises with the launches reading it
-    cx->d_axes = nullptr;
-    cx->axes_cap = 0;
     cx->axes_num = 0;
-    HIP_TRY(hipMalloc(&cx->d_axes, sizeof(double) * 2 * (size_t)num));
-    cx->axes_cap = num;
+    HIP_TRY(regrow(cx->d_axes, cx->axes_cap, num, sizeof(double) * 2 * (size_t)num));
     return 0;
 }
 
@@ -1145,20 +1077,6 @@ int prepare_grid(rox_system *sys, const rox_field *fld, const rox_grid *grid, in
 }
 
 // ---- rox_trace_through_focus
-void launch_focus_feat(int inst, const LaunchCfg &k, const FocusArgs &a)
-{
-    typedef void (*fn)(const LaunchCfg &, const FocusArgs &);
-    static const fn fns[] = {launch_lean_focus, launch_even_focus, launch_radial_focus, launch_poly_focus,
-                             launch_aplist_focus, launch_evenap_focus, launch_general_focus};
-    static const fn fast[] = {launch_lean_fast_focus, launch_even_fast_focus, launch_radial_fast_focus,
-                              launch_poly_fast_focus, launch_aplist_fast_focus, launch_evenap_fast_focus,
-                              launch_general_fast_focus};
-    if (k.gtab)
-        launch_general_gtab_focus(k, a);
-    else
-        (k.fast ? fast : fns)[inst](k, a);
-}
-
 // Workgroups per CU of a through-focus launch: its 512-thread workgroups hold 4 waves per SIMD
 // (two per CU) and grid-stride over the tiles, so that the partial records -- one per
 // (wave, plane) -- stay few: 2 x 256 x 8 x 72 B = 288 KiB per plane on 256 CUs.
@@ -1593,14 +1511,8 @@ int rox_trace_through_focus(rox_system *sys, const rox_field *fld, const rox_gri
     const size_t b_part = stats ? (size_t)cap_blocks * (bs_max / 64) * n_planes * sizeof(FocusAcc) : 0;
     const size_t b_stats = ((size_t)n_planes * sizeof(rox_focus_stats) + 255) & ~size_t(255);
     const size_t need = b_planes + b_part + b_stats;
-    if (need > cx->focus_cap) {
-        if (cx->d_focus)
-            HIP_TRY(hipFree(cx->d_focus));          // synchronises: no launch still uses it
-        cx->d_focus = nullptr;
-        cx->focus_cap = 0;
-        HIP_TRY(hipMalloc(&cx->d_focus, need));
-        cx->focus_cap = need;
-    }
+    if (need > cx->focus_cap)
+        HIP_TRY(regrow(cx->d_focus, cx->focus_cap, need, need));
     rox_focus_plane *d_planes = (rox_focus_plane *)cx->d_focus;
     double *d_part = (double *)(cx->d_focus + b_planes);
     rox_focus_stats *d_stats = (rox_focus_stats *)(cx->d_focus + b_planes + b_part);
@@ -1641,21 +1553,16 @@ int rox_trace_through_focus(rox_system *sys, const rox_field *fld, const rox_gri
         HIP_TRY(hipEventCreateWithFlags(&cx->focus_ev, hipEventDisableTiming));
     else
         HIP_TRY(hipEventSynchronize(cx->focus_ev));     // the previous call's copy has read h_focus
-    if (n_planes > cx->h_focus_cap) {
-        if (cx->h_focus)
-            HIP_TRY(hipHostFree(cx->h_focus));
-        cx->h_focus = nullptr;
-        cx->h_focus_cap = 0;
-        HIP_TRY(hipHostMalloc((void **)&cx->h_focus, sizeof(rox_focus_plane) * ROX_MAX_FOCUS_PLANES));
-        cx->h_focus_cap = ROX_MAX_FOCUS_PLANES;
-    }
+    if (n_planes > cx->h_focus_cap)
+        HIP_TRY(regrow(cx->h_focus, cx->h_focus_cap, ROX_MAX_FOCUS_PLANES,
+                       sizeof(rox_focus_plane) * ROX_MAX_FOCUS_PLANES, hipHostMallocDefault));
     memcpy(cx->h_focus, planes, sizeof(rox_focus_plane) * (size_t)n_planes);
     HIP_TRY(hipMemcpyAsync(d_planes, cx->h_focus, sizeof(rox_focus_plane) * (size_t)n_planes,
                            hipMemcpyHostToDevice, st));
     HIP_TRY(hipEventRecord(cx->focus_ev, st));
     if (stats)      // every wave merges into its records: they start at n = 0
         HIP_TRY(hipMemsetAsync(d_part, 0, (size_t)blocks * (bs / 64) * n_planes * sizeof(FocusAcc), st));
-    launch_focus_feat(inst, k, f);
+    trace_fns(inst, k).focus(k, f);
     HIP_TRY(hipGetLastError());
     if (!stats)
         return 0;
@@ -1734,28 +1641,17 @@ int rox_trace_pupil_grids(rox_system *sys, int32_t n_grids, const rox_field *fld
     int64_t blocks = (R + bs - 1) / bs;
     if (compact) {
         // per-item tickets
-        if ((int64_t)n_grids > cx->btickets_cap) {
-            if (cx->d_btickets)
-                HIP_TRY(hipFree(cx->d_btickets));
-            cx->d_btickets = nullptr;
-            cx->btickets_cap = 0;
-            HIP_TRY(hipMalloc(&cx->d_btickets, sizeof(uint32_t) * 2 * (size_t)n_grids));
-            HIP_TRY(hipMemsetAsync(cx->d_btickets, 0, sizeof(uint32_t) * 2 * (size_t)n_grids, st));
-            cx->btickets_cap = n_grids;
-        }
+        if ((int64_t)n_grids > cx->btickets_cap)
+            HIP_TRY(regrow_zeroed(cx->d_btickets, cx->btickets_cap, n_grids,
+                                  sizeof(uint32_t) * 2 * (size_t)n_grids, st));
         // per-item look-back states; small tiles when the whole batch is small
         const int32_t small = ((int64_t)n_grids * R <= (int64_t)sys->num_cus * kSmallTile)
                                   ? compact_small_want(sys, R) : 0;
         const int64_t tiles = compact_tiles(R, small, bs);
         blocks = tiles;
         if ((int64_t)n_grids * tiles > cx->btiles_cap) {
-            if (cx->d_btiles)
-                HIP_TRY(hipFree(cx->d_btiles));
-            cx->d_btiles = nullptr;
-            cx->btiles_cap = 0;
-            HIP_TRY(hipMalloc(&cx->d_btiles, sizeof(uint64_t) * (size_t)(n_grids * tiles)));
-            HIP_TRY(hipMemsetAsync(cx->d_btiles, 0, sizeof(uint64_t) * (size_t)(n_grids * tiles), st));
-            cx->btiles_cap = n_grids * tiles;
+            HIP_TRY(regrow_zeroed(cx->d_btiles, cx->btiles_cap, n_grids * tiles,
+                                  sizeof(uint64_t) * (size_t)(n_grids * tiles), st));
             cx->bepoch = 0;
         }
         ++cx->bepoch;
@@ -1785,23 +1681,17 @@ int rox_trace_pupil_grids(rox_system *sys, int32_t n_grids, const rox_field *fld
     }();
     if (n_grids <= kInlineItems && !no_inline) {
         k.n_inline = n_grids;
-        launch_feat_batch(inst, k, items.data());
+        trace_fns(inst, k).batch(k, items.data());
         HIP_TRY(hipGetLastError());
         return 0;
     }
     // items -> pinned slot -> device, in stream order
     if (n_grids > cx->items_cap) {
-        if (cx->d_items)
-            HIP_TRY(hipFree(cx->d_items));      // synchronises with the launches reading it
-        if (cx->h_items)
-            HIP_TRY(hipHostFree(cx->h_items));
-        cx->d_items = cx->h_items = nullptr;
-        cx->items_cap = 0;
         const int32_t want = n_grids < 64 ? 64 : n_grids;
-        HIP_TRY(hipMalloc(&cx->d_items, sizeof(TraceArgs) * (size_t)want));
-        HIP_TRY(hipHostMalloc(&cx->h_items, sizeof(TraceArgs) * (size_t)want * StreamCtx::kItemSlots,
-                              hipHostMallocDefault));
-        cx->items_cap = want;
+        HIP_TRY(release(cx->d_items, cx->items_cap));   // synchronises: the copies from h_items are done
+        HIP_TRY(regrow(cx->h_items, cx->items_cap, want,
+                       sizeof(TraceArgs) * (size_t)want * StreamCtx::kItemSlots, hipHostMallocDefault));
+        HIP_TRY(regrow(cx->d_items, cx->items_cap, want, sizeof(TraceArgs) * (size_t)want));
         cx->items_last.clear();
         for (bool &live : cx->item_ev_live)
             live = false;
@@ -1834,7 +1724,7 @@ int rox_trace_pupil_grids(rox_system *sys, int32_t n_grids, const rox_field *fld
         cx->items_last.assign(reinterpret_cast<const char *>(items.data()),
                               reinterpret_cast<const char *>(items.data()) + items_bytes);
     }
-    launch_feat_batch(inst, k, cx->d_items);
+    trace_fns(inst, k).batch(k, cx->d_items);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1925,7 +1815,7 @@ int rox_iterate_ray_raw(rox_system *sys, int32_t n, const rox_aim *probs, double
     a.last_status = last_xy ? (int32_t *)(d + pb + 2 * yb + rb) : nullptr;
     a.eps = eps;
     a.wave_per_problem = n <= kWavePerProblemMax;
-    launch_aim(sys, a, lds, gtab, st);
+    search_fns(sys, gtab).aim(a, lds, st);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess)
         e = hipStreamSynchronize(st);
@@ -1981,7 +1871,7 @@ int rox_find_real_enp(rox_system *sys, int32_t n, const rox_enp *probs, double e
     a.z_out = (double *)(d + pb);
     a.result = (int32_t *)(d + pb + zb);
     a.eps = eps;
-    launch_enp(sys, a, lds, gtab, st);
+    search_fns(sys, gtab).enp(a, lds, st);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess)
         e = hipStreamSynchronize(st);
@@ -2031,7 +1921,7 @@ int rox_iterate_pupil_rays(rox_system *sys, int32_t n, const rox_pupil_iter *pro
     a.vig = (double *)(d + pb);
     a.eps = eps;
     a.wave_per_problem = n <= kWavePerProblemMax;
-    launch_vig(sys, a, lds, gtab, st);
+    search_fns(sys, gtab).vig(a, lds, st);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess)
         e = hipStreamSynchronize(st);
@@ -2080,7 +1970,7 @@ int rox_calc_vignetting(rox_system *sys, int32_t n, const rox_vig *probs, double
     a.clip = (int32_t *)(d + pb + vb);
     a.eps = eps;
     a.wave_per_problem = n <= kWavePerProblemMax;
-    launch_vig(sys, a, lds, gtab, st);
+    search_fns(sys, gtab).vig(a, lds, st);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess)
         e = hipStreamSynchronize(st);

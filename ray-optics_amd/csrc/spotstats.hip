@@ -17,14 +17,14 @@
 
 #include <cstdint>
 #include <cstring>
-#include <mutex>
 
 #include "rox_device.hpp"
+#include "rox_host.hpp"
 
 namespace rox {
-int host_fail(int code, const char *msg);
-
 namespace {
+
+constexpr char kHipWhere[] = "rox_spot_stats: ";
 
 constexpr int kStatBlock = 256;
 constexpr int kCopies = 32;
@@ -164,14 +164,14 @@ __global__ void __launch_bounds__(kStatBlock) spot_finish_kernel(const double *p
         }
 }
 
-// per-process scratch (grow-only), one call at a time
+// grow-only scratch per (device, stream)
 struct StatScratch {
-    std::mutex mu;
     char *d = nullptr;          // device: edges, copies, partials
     size_t d_cap = 0;
     char *h = nullptr;          // device-mapped pinned: summary, histogram for host destinations
     size_t h_cap = 0;
-} g_scratch;
+};
+PerStream<StatScratch> g_scratch;
 
 }  // namespace
 }  // namespace rox
@@ -210,30 +210,19 @@ extern "C" int rox_spot_stats(const double *seg, int64_t ld, const uint8_t *stat
     const size_t d_need = (want_hist ? b_edges + b_copies : 0) + b_part;
     const size_t h_hist = (((size_t)bins * 4) + 255) & ~size_t(255);
     const size_t h_need = 256 + h_hist + (want_hist ? b_edges : 0);
-    std::lock_guard<std::mutex> lock(g_scratch.mu);
-#define SPOT_TRY(expr)                                                                   \
-    do {                                                                                 \
-        hipError_t e_ = (expr);                                                          \
-        if (e_ != hipSuccess)                                                            \
-            return host_fail(ROX_E_HIP, hipGetErrorString(e_));                          \
-    } while (0)
-    if (g_scratch.d_cap < d_need) {
-        if (g_scratch.d)
-            SPOT_TRY(hipFree(g_scratch.d));
-        g_scratch.d = nullptr;
-        g_scratch.d_cap = 0;
-        SPOT_TRY(hipMalloc((void **)&g_scratch.d, d_need + d_need / 4));
-        g_scratch.d_cap = d_need + d_need / 4;
-    }
-    if (g_scratch.h_cap < h_need) {
-        if (g_scratch.h)
-            SPOT_TRY(hipHostFree(g_scratch.h));
-        g_scratch.h = nullptr;
-        g_scratch.h_cap = 0;
-        SPOT_TRY(hipHostMalloc((void **)&g_scratch.h, h_need + h_need / 4, hipHostMallocMapped));
-        g_scratch.h_cap = h_need + h_need / 4;
-    }
-    char *d = g_scratch.d;
+    int device = 0;
+    HIP_TRY(hipGetDevice(&device));
+    auto *slot = g_scratch.get(device, st);
+    if (!slot)
+        return host_fail(ROX_E_NOMEM, "rox_spot_stats: out of host memory");
+    // calls on one stream take turns: the scratch is theirs until the results are read back
+    std::lock_guard<std::mutex> turn(slot->mu);
+    StatScratch &sc = slot->data;
+    if (sc.d_cap < d_need)
+        HIP_TRY(regrow(sc.d, sc.d_cap, d_need + d_need / 4, d_need + d_need / 4));
+    if (sc.h_cap < h_need)
+        HIP_TRY(regrow(sc.h, sc.h_cap, h_need + h_need / 4, h_need + h_need / 4, hipHostMallocMapped));
+    char *d = sc.d;
     StatArgs a{};
     a.n = n;
     a.n_dev = n_hits;
@@ -247,26 +236,26 @@ extern "C" int rox_spot_stats(const double *seg, int64_t ld, const uint8_t *stat
         // caller's pageable arrays would be staged by the runtime, synchronously)
         double *xe = (double *)d;
         double *ye = xe + n_x_edges;
-        double *he = (double *)(g_scratch.h + 256 + h_hist);
+        double *he = (double *)(sc.h + 256 + h_hist);
         memcpy(he, x_edges, sizeof(double) * n_x_edges);
         memcpy(he + n_x_edges, y_edges, sizeof(double) * n_y_edges);
-        SPOT_TRY(hipMemcpyAsync(xe, he, sizeof(double) * (n_x_edges + n_y_edges), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(xe, he, sizeof(double) * (n_x_edges + n_y_edges), hipMemcpyHostToDevice, st));
         a.xe = xe; a.ye = ye; a.nx = nx; a.ny = ny;
         a.copies = (uint32_t *)(d + b_edges);
-        SPOT_TRY(hipMemsetAsync(a.copies, 0, (size_t)kCopies * bins * 4, st));
+        HIP_TRY(hipMemsetAsync(a.copies, 0, (size_t)kCopies * bins * 4, st));
         d += b_edges + b_copies;
     }
     a.partial = (double *)d;
-    double *summ = (double *)g_scratch.h;               // device-mapped: the finishing pass writes it
-    uint32_t *hist_h = (uint32_t *)(g_scratch.h + 256);
+    double *summ = (double *)sc.h;      // device-mapped: the finishing pass writes it
+    uint32_t *hist_h = (uint32_t *)(sc.h + 256);
     hipLaunchKernelGGL(spot_stats_kernel, dim3(blocks), dim3(kStatBlock), 0, st, a);
     const int fblocks = want_hist ? (int)((bins + kStatBlock - 1) / kStatBlock > 1024 ? 1024
                                                                                      : (bins + kStatBlock - 1) / kStatBlock)
                                   : 1;
     hipLaunchKernelGGL(spot_finish_kernel, dim3(fblocks < 1 ? 1 : fblocks), dim3(kStatBlock), 0, st, a.partial,
                        blocks, summ, a.copies, bins, want_hist ? hist_h : nullptr);
-    SPOT_TRY(hipGetLastError());
-    SPOT_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
     summary->n = (int64_t)summ[0];
     summary->sum[0] = summ[1]; summary->sum[1] = summ[2];
     summary->sum_sq[0] = summ[3]; summary->sum_sq[1] = summ[4];
@@ -274,6 +263,5 @@ extern "C" int rox_spot_stats(const double *seg, int64_t ld, const uint8_t *stat
     summary->min[1] = summ[7]; summary->max[1] = summ[8];
     if (want_hist)
         memcpy(hist, hist_h, (size_t)bins * 4);
-#undef SPOT_TRY
     return 0;
 }

@@ -2,6 +2,7 @@
 in global memory, read with scalar loads: rox_device.hpp F_GTAB) -- a SequentialModel has no
 size limit (rayoptics/seq/sequential.py:167-202), round 5 returned ROX_E_UNSUPPORTED beyond
 ~220 interfaces -- and the same instance forced onto the regular fixtures."""
+import ctypes as C
 import os
 import subprocess
 import sys
@@ -183,6 +184,97 @@ def test_spot_statistics_on_the_device(name, num):
     assert s3['n'] == len(x) and s3['min'] == summ['min'] and s3['max'] == summ['max']
     np.testing.assert_array_equal(h3.astype(np.float64), np.histogram2d(x, y, bins=[xe, ye])[0])
     eng.close()
+
+
+def _spot_rows(torch, device, n, seed):
+    """n random ROX_OUT_HITS rows on `device` (about a fifth not OK) and NumPy's summary and
+    histogram over the OK ones; edges of a size that differs with the seed"""
+    rng = np.random.default_rng(seed)
+    ld = n + 64
+    seg = np.zeros((2, ld))
+    seg[:, :n] = rng.normal(scale=1.0 + seed % 5, size=(2, n))
+    status = np.where(rng.random(n) < 0.8, abi.OK, abi.BLOCKED).astype(np.uint8)
+    ok = status == abi.OK
+    x, y = seg[0, :n][ok], seg[1, :n][ok]
+    xe = np.linspace(x.min() * 0.9, x.max() * 0.9, 20 + 37 * (seed % 7))
+    ye = np.linspace(y.min(), y.max(), 11 + 53 * (seed % 3))
+    want = dict(n=int(ok.sum()), sum=(x.sum(), y.sum()), min=(x.min(), y.min()), max=(x.max(), y.max()),
+                hist=np.histogram2d(x, y, bins=[xe, ye])[0])
+    return (torch.from_numpy(seg).to(device), torch.from_numpy(status).to(device), ld, n, xe, ye), want
+
+
+def _spot_call(lib, rows, stream):
+    """rox_spot_stats over device rows -> (summary, histogram) or the error message"""
+    seg, status, ld, n, xe, ye = rows
+    summ = abi.SpotSummary()
+    hist = np.empty((len(xe) - 1, len(ye) - 1), dtype=np.uint32)
+    rc = lib.rox_spot_stats(seg.data_ptr(), ld, status.data_ptr(), None, n, abi.SPOT_ROWS, xe.ctypes.data, len(xe),
+                            ye.ctypes.data, len(ye), C.byref(summ), hist.ctypes.data, stream)
+    return (summ, hist) if rc == 0 else lib.rox_last_error().decode()
+
+
+def _spot_mismatch(got, want):
+    """what differs between a rox_spot_stats result and NumPy's (None: nothing)"""
+    if isinstance(got, str):
+        return got
+    summ, hist = got
+    if summ.n != want['n'] or (summ.min[0], summ.min[1]) != want['min'] or (summ.max[0], summ.max[1]) != want['max']:
+        return 'count / min / max'
+    if not np.allclose((summ.sum[0], summ.sum[1]), want['sum'], rtol=1e-11, atol=1e-9):
+        return 'sums'
+    if not np.array_equal(hist.astype(np.float64), want['hist']):
+        return 'histogram'
+    return None
+
+
+def test_spot_stats_on_two_streams_at_once():
+    """rox_spot_stats keeps its scratch per (device, stream): two host threads, each on a stream of
+    its own, call it at the same time on rows of changing sizes and histogram shapes (the scratch
+    grows under them); every result == NumPy over the same rows"""
+    import threading
+    import torch
+    from rayoptics_amd.engine import load_library
+    lib = load_library()
+    abi.declare(lib)
+    dev = torch.device('cuda:0')
+    sizes = (5000, 200_000, 30_000, 600_000, 1000)
+    cases = [[_spot_rows(torch, dev, n, 10 * t + i) for i, n in enumerate(sizes)] for t in range(2)]
+    streams = [torch.cuda.Stream(dev) for _ in range(2)]
+    torch.cuda.synchronize(dev)
+    start = threading.Barrier(2)
+    bad = []
+
+    def run(t):
+        start.wait(timeout=120)
+        for rnd in range(4):
+            for i, (rows, want) in enumerate(cases[t]):
+                why = _spot_mismatch(_spot_call(lib, rows, streams[t].cuda_stream), want)
+                if why:
+                    bad.append((t, rnd, i, why))
+
+    threads = [threading.Thread(target=run, args=(t,)) for t in range(2)]
+    for th in threads:
+        th.start()
+    for th in threads:
+        th.join()
+    assert not bad, bad
+
+
+def test_spot_stats_on_a_second_device():
+    """rox_spot_stats on device 1 after device 0 has made its scratch (both on the null stream,
+    one handle for the two devices): device 1 gets scratch of its own, the result == NumPy"""
+    import torch
+    from rayoptics_amd.engine import load_library
+    if torch.cuda.device_count() < 2:
+        pytest.skip('one device on this host: there is no second device to run on')
+    lib = load_library()
+    abi.declare(lib)
+    for d, n in ((0, 400_000), (1, 300_000), (0, 1000), (1, 500_000)):
+        with torch.cuda.device(d):
+            rows, want = _spot_rows(torch, torch.device('cuda', d), n, 40 + d)
+            torch.cuda.synchronize()
+            why = _spot_mismatch(_spot_call(lib, rows, None), want)
+        assert why is None, (d, n, why)
 
 
 def test_spot_stats_product_call_and_its_wall_clock():
