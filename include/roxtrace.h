@@ -564,6 +564,34 @@ int rox_trace_through_focus(rox_system *sys, const rox_field *fld, const rox_gri
                             double *rows, int64_t ld, uint8_t *status,
                             rox_focus_stats *stats, void *stream);
 
+/* n_items through-focus scans in ONE launch -- the (field x wavelength) loops of
+ * SequentialModel.trace_grid / trace_wavefront (rayoptics/seq/sequential.py:1058-1114) over the
+ * refocus functions above: field curvature, focal shift and a white-light best focus from one
+ * call.  Item i is exactly
+ *   rox_trace_through_focus(sys, &flds[i], &grids[i], wvl_idx[i], &opts[i],
+ *                           n_planes, planes + i*n_planes, ...)
+ * with its rows at rows + i*n_planes*3*ld, its status at status + i*ld and its statistics at
+ * stats + i*n_planes: rows, status and statistics are bit-identical to that single call (the
+ * same workgroup size, workgroup count and merge order per item).
+ *   grids  per item: start / stop may differ (each field's vignetting box, trace_wavefront);
+ *          kind, num and row_begin / row_count must be the same, so every item has R rays.
+ *   opts   per item: out_mode ROX_OUT_FAN; ROX_FILTER_PHANTOMS, ROX_FAST_FP64, first_surf and
+ *          last_surf the same for every item.  ROX_HOST_POINTERS / ROX_HITS_APPEND are refused.
+ *   planes HOST [n_items][n_planes]; rows DEVICE [n_items][n_planes][3][ld] or NULL; status
+ *          DEVICE [n_items][ld] or NULL; stats host or device [n_items][n_planes] or NULL (not
+ *          both rows and stats NULL).
+ * Argument errors (n_items outside [1, ROX_MAX_FOCUS_ITEMS], n_planes outside
+ * [1, ROX_MAX_FOCUS_PLANES], NULL arrays, ld < R, a grid or options mismatch, a bad plane wf,
+ * a wvl_idx outside the system) return ROX_E_ARG naming the item and plane before anything is
+ * enqueued.  Asynchronous on `stream` unless stats is host memory.                            */
+#define ROX_MAX_FOCUS_ITEMS 1024
+int rox_trace_through_focus_grids(rox_system *sys, int32_t n_items, const rox_field *flds,
+                                  const int32_t *wvl_idx, const rox_grid *grids,
+                                  const rox_opts *opts, int32_t n_planes,
+                                  const rox_focus_plane *planes,
+                                  double *rows, int64_t ld, uint8_t *status,
+                                  rox_focus_stats *stats, void *stream);
+
 /* chief-ray aiming ------------------------------------------------------- */
 /* One problem per (field, wavelength): trace.iterate_ray
  * (rayoptics/raytr/trace.py:313-415) as trace.aim_chief_ray calls it

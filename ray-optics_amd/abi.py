@@ -169,6 +169,7 @@ class FocusStats(C.Structure):
 
 
 MAX_FOCUS_PLANES = 256      # include/roxtrace.h ROX_MAX_FOCUS_PLANES
+MAX_FOCUS_ITEMS = 1024      # include/roxtrace.h ROX_MAX_FOCUS_ITEMS
 
 
 class Vig(C.Structure):
@@ -204,7 +205,7 @@ EXPORTS = ('rox_abi_version', 'rox_device_count', 'rox_set_device',
            'rox_aim_chief_rays', 'rox_iterate_ray_raw', 'rox_find_real_enp', 'rox_calc_vignetting',
            'rox_iterate_pupil_rays', 'rox_calc_psf',
            'rox_pin_host_memory', 'rox_unpin_host_memory', 'rox_copy_async', 'rox_synchronize',
-           'rox_spot_stats', 'rox_trace_through_focus')
+           'rox_spot_stats', 'rox_trace_through_focus', 'rox_trace_through_focus_grids')
 # ... and the measurement / self-test helpers of include/roxtrace_diag.h
 DIAG_EXPORTS = ('rox_time_pupil_grid', 'rox_selftest_fp64', 'rox_diag_pack_launches')
 
@@ -263,6 +264,9 @@ def declare(lib):
     lib.rox_trace_through_focus.restype = C.c_int
     lib.rox_trace_through_focus.argtypes = [vp, P(Field), P(Grid), i32, P(Opts), i32, P(FocusPlane),
                                             vp, i64, vp, vp, vp]
+    lib.rox_trace_through_focus_grids.restype = C.c_int
+    lib.rox_trace_through_focus_grids.argtypes = [vp, i32, P(Field), P(i32), P(Grid), P(Opts), i32,
+                                                  P(FocusPlane), vp, i64, vp, vp, vp]
     lib.rox_time_pupil_grid.restype = C.c_int
     lib.rox_time_pupil_grid.argtypes = [vp, P(Field), P(Grid), i32, P(Opts),
                                         P(Out), vp, i32, P(dbl)]

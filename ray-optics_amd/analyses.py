@@ -11,6 +11,9 @@
   trace_pupil_coords / focus_pupil_coords <- rayoptics/raytr/analyses.py:545-580 (RayList, RayGeoPSF)
   through_focus      (new) the refocus functions over a range of focus shifts: one trace,
                         K focus planes, per-plane statistics (rox_trace_through_focus)
+  through_focus_map  (new) through_focus for every field and wavelength in one launch, with
+                        polychromatic statistics, field curvature and the white-light best
+                        focus (rox_trace_through_focus_grids)
 """
 import numpy as np
 
@@ -622,21 +625,19 @@ class ThroughFocus:
         return self.stats['opd_rms']
 
 
-def through_focus(opt_model, fld, wvl, focs, num_rays=21, xy=None, image_pt_2d=None,
-                  image_delta=None, rows=False, **kwargs):
-    """A through-focus scan on the device: the pupil grid is traced once and evaluated at
-    every focus shift in ``focs`` (rox_trace_through_focus).  Each plane is built exactly as
-    focus_wavefront / focus_fan build their one focus (rayoptics/raytr/analyses.py:313-342,
-    769-791): setup_pupil_coords at that foc, its reference sphere as rox_wavefront (the
-    pre-calc / calc split on an infinite sphere, :352-357).  ``xy=None`` traces the square
-    pupil grid trace_wavefront does (the field's vignetting box, apertures checked), ``xy=0``
-    / ``1`` the fan trace_fan does.  A focus whose reference sphere the device cannot express
-    raises UnsupportedModelError for the whole call."""
-    from .engine import grid_rays
-    from .table import wavefront_from_model
+def _check_focs(focs, what):
     focs = [float(f) for f in np.atleast_1d(focs)]
     if not 1 <= len(focs) <= abi.MAX_FOCUS_PLANES:
-        raise ValueError(f'through_focus: 1 to {abi.MAX_FOCUS_PLANES} focus values, got {len(focs)}')
+        raise ValueError(f'{what}: 1 to {abi.MAX_FOCUS_PLANES} focus values, got {len(focs)}')
+    return focs
+
+
+def _focus_planes(opt_model, fld, wvl, focs, image_pt_2d=None, image_delta=None):
+    """the rox_focus_plane of every focus shift, each built as focus_wavefront / focus_fan build
+    their one focus (rayoptics/raytr/analyses.py:313-342, 769-791): setup_pupil_coords at that
+    foc, its reference sphere as rox_wavefront (the pre-calc / calc split on an infinite sphere,
+    :352-357).  The field keeps the last focus's chief ray and reference sphere."""
+    from .table import wavefront_from_model
     planes = []
     for foc in focs:
         ref_sphere, cr_pkg = _setup_pupil_coords(opt_model, fld, wvl, foc, image_pt_2d, image_delta)
@@ -651,32 +652,229 @@ def through_focus(opt_model, fld, wvl, focs, num_rays=21, xy=None, image_pt_2d=N
         p.wf = wf
         planes.append(p)
     fld.chief_ray, fld.ref_sphere = cr_pkg, ref_sphere
-    kw = dict(kwargs)
+    return planes
+
+
+def _focus_grid(opt_model, fld, xy, num_rays, kw):
+    """the pupil grid of a scan (and its trace options into ``kw``): ``xy=None`` the square grid
+    trace_wavefront traces (:735-766), ``xy=0`` / ``1`` trace_fan's fan (:277-314)"""
     for k in ('output_filter', 'rayerr_filter'):
         kw.pop(k, None)
-    if xy is None:                                      # trace_wavefront's grid (:735-766)
+    if xy is None:
         oversize = kw.pop('oversize', 1.)
         vig_bbox = fld.vignetting_bbox(opt_model['osp']['pupil'], oversize=oversize)
         kw['check_apertures'] = kw.get('check_apertures', True)
         kw['apply_vignetting'] = kw.get('apply_vignetting', False)
-        grid = make_grid(vig_bbox[0], vig_bbox[1], num_rays)
-    else:                                               # trace_fan's fan (:277-314)
-        fan_def = _fan_def(xy, num_rays)
-        kw['apply_vignetting'] = kw.get('apply_vignetting', True)
-        grid = make_grid(fan_def[0], fan_def[1], fan_def[2], abi.GRID_FAN)
-    eng, f, wi, opts = _launch_setup(opt_model, fld, wvl, kw, abi.OUT_FAN)
-    out = eng.trace_pupil_grid_focus(f, grid, wi, opts, planes, want_rows=rows)
-    stats, dev_rows = out if rows else (out, None)
+        return make_grid(vig_bbox[0], vig_bbox[1], num_rays)
+    fan_def = _fan_def(xy, num_rays)
+    kw['apply_vignetting'] = kw.get('apply_vignetting', True)
+    return make_grid(fan_def[0], fan_def[1], fan_def[2], abi.GRID_FAN)
+
+
+def _stats_in_waves(stats, opt_model, wvl):
+    """the device statistics with the OPD in waves, converted as focus_fan converts"""
     convert_to_opd = 1 / opt_model.nm_to_sys_units(wvl)
     stats = stats.copy()
     for k in ('opd_mean', 'opd_rms', 'opd_min', 'opd_max'):
         stats[k] = convert_to_opd * stats[k]
+    return stats
+
+
+def through_focus(opt_model, fld, wvl, focs, num_rays=21, xy=None, image_pt_2d=None,
+                  image_delta=None, rows=False, **kwargs):
+    """A through-focus scan on the device: the pupil grid is traced once and evaluated at
+    every focus shift in ``focs`` (rox_trace_through_focus).  Each plane is built exactly as
+    focus_wavefront / focus_fan build their one focus (rayoptics/raytr/analyses.py:313-342,
+    769-791): setup_pupil_coords at that foc, its reference sphere as rox_wavefront (the
+    pre-calc / calc split on an infinite sphere, :352-357).  ``xy=None`` traces the square
+    pupil grid trace_wavefront does (the field's vignetting box, apertures checked), ``xy=0``
+    / ``1`` the fan trace_fan does.  A focus whose reference sphere the device cannot express
+    raises UnsupportedModelError for the whole call."""
+    from .engine import grid_rays
+    focs = _check_focs(focs, 'through_focus')
+    planes = _focus_planes(opt_model, fld, wvl, focs, image_pt_2d, image_delta)
+    kw = dict(kwargs)
+    grid = _focus_grid(opt_model, fld, xy, num_rays, kw)
+    eng, f, wi, opts = _launch_setup(opt_model, fld, wvl, kw, abi.OUT_FAN)
+    out = eng.trace_pupil_grid_focus(f, grid, wi, opts, planes, want_rows=rows)
+    stats, dev_rows = out if rows else (out, None)
+    stats = _stats_in_waves(stats, opt_model, wvl)
     host_rows = status = None
     if dev_rows is not None:
+        convert_to_opd = 1 / opt_model.nm_to_sys_units(wvl)
         host_rows, status = dev_rows.to_host()
         host_rows = np.array(host_rows[:, :, :grid_rays(grid)])
         host_rows[:, 2] = convert_to_opd * host_rows[:, 2]
     return ThroughFocus(focs, stats, host_rows, status)
+
+
+# polychromatic statistics per field and plane (through_focus_map): the weighted ray count,
+# the weighted centroid in image coordinates, the RMS spot radius about it and about the
+# reference wavelength's image point, and the RMS wavefront error (each wavelength about its own
+# mean, in its own waves)
+POLY_STATS_DTYPE = np.dtype([('n', np.float64), ('cx', np.float64), ('cy', np.float64),
+                             ('rms_spot', np.float64), ('rms_spot_ref_pt', np.float64),
+                             ('rms_wavefront', np.float64)])
+
+
+def poly_merge(stats, image_pts, spectral_wts, ref_index):
+    """the polychromatic statistics [K] of one field from its per-wavelength records.
+
+    stats       [W, K] FOCUS_STATS_DTYPE, OPD in waves of each wavelength
+    image_pts   [W, K, 2] each plane's image point (ref_sphere[0][:2] at that wavelength)
+    spectral_wts  [W] weights s_w
+    ref_index   the wavelength whose image point rms_spot_ref_pt is measured about
+
+    With c_w = image_pt_w + (cx, cy) and M2_w = n_w rms_spot_w^2 (positions in absolute image
+    coordinates, so lateral colour counts -- as the reference's spot diagram measures every
+    wavelength against the central wavelength's image point, rayoptics/seq/sequential.py:1058-1085):
+    N = sum s_w n_w, C = sum s_w n_w c_w / N, rms_spot = sqrt(sum s_w (M2_w + n_w |c_w - C|^2) / N),
+    rms_spot_ref_pt the same about the reference image point, rms_wavefront =
+    sqrt(sum s_w n_w opd_rms_w^2 / N).  Records with n = 0 are skipped; none left -> NaN."""
+    stats = np.asarray(stats)
+    W, K = stats.shape
+    ip = np.asarray(image_pts, dtype=np.float64).reshape(W, K, 2)
+    s = np.asarray(spectral_wts, dtype=np.float64).reshape(W, 1)
+    n = stats['n'].astype(np.float64)
+    use = n > 0
+    sn = np.where(use, s * n, 0.0)
+    c = ip + np.stack([stats['cx'], stats['cy']], axis=-1)
+    c = np.where(use[..., None], c, 0.0)
+    m2 = np.where(use, n * np.where(use, stats['rms_spot'], 0.0) ** 2, 0.0)
+    w2 = np.where(use, np.where(use, stats['opd_rms'], 0.0) ** 2, 0.0)
+    N = sn.sum(axis=0)
+    out = np.full(K, np.nan, dtype=POLY_STATS_DTYPE)
+    out['n'] = N
+    ok = N > 0
+    with np.errstate(invalid='ignore', divide='ignore'):
+        C = (sn[..., None] * c).sum(axis=0) / N[:, None]
+        d2 = ((c - C[None]) ** 2).sum(axis=-1)
+        d2r = ((c - ip[ref_index][None]) ** 2).sum(axis=-1)
+        sm2 = np.where(use, s * m2, 0.0)
+        out['cx'] = np.where(ok, C[:, 0], np.nan)
+        out['cy'] = np.where(ok, C[:, 1], np.nan)
+        out['rms_spot'] = np.where(ok, np.sqrt((sm2 + sn * d2).sum(axis=0) / N), np.nan)
+        out['rms_spot_ref_pt'] = np.where(ok, np.sqrt((sm2 + sn * d2r).sum(axis=0) / N), np.nan)
+        out['rms_wavefront'] = np.where(ok, np.sqrt((sn * w2).sum(axis=0) / N), np.nan)
+    return out
+
+
+class ThroughFocusMap:
+    """what :func:`through_focus_map` returns.
+
+    focs, wvls, field_wts, spectral_wts, ref_wvl   as used
+    stats       [F, W, K] FOCUS_STATS_DTYPE, each [f, w] what through_focus(flds[f], wvls[w])
+                returns (OPD in waves of that wavelength)
+    image_pts   [F, W, K, 2] each plane's image point
+    rows        [F, W, K, 3, R] and ``status`` [F, W, R] with ``rows=True``, else None
+    best_focus_spot / best_focus_wavefront [F, W] (+ ``_kind``): :func:`best_focus` per curve
+    poly        [F, K] POLY_STATS_DTYPE: :func:`poly_merge` of each field's wavelengths
+    best_focus_field [F] (+ ``_kind``): the best focus of each field's polychromatic RMS spot --
+                the through-focus field curvature
+    best_focus (+ ``_kind``): the best focus of the field-weighted mean polychromatic RMS spot"""
+
+    def __init__(self, focs, wvls, field_wts, spectral_wts, ref_wvl, stats, image_pts, rows, status):
+        self.focs = np.asarray(focs, dtype=np.float64)
+        self.wvls = list(wvls)
+        self.field_wts = np.asarray(field_wts, dtype=np.float64)
+        self.spectral_wts = np.asarray(spectral_wts, dtype=np.float64)
+        self.ref_wvl = ref_wvl
+        self.stats = stats
+        self.image_pts = image_pts
+        self.rows = rows
+        self.status = status
+        F, W, _K = stats.shape
+        self.best_focus_spot = np.empty((F, W))
+        self.best_focus_wavefront = np.empty((F, W))
+        self.best_focus_spot_kind = np.empty((F, W), dtype=object)
+        self.best_focus_wavefront_kind = np.empty((F, W), dtype=object)
+        for f in range(F):
+            for w in range(W):
+                self.best_focus_spot[f, w], self.best_focus_spot_kind[f, w] = best_focus(
+                    self.focs, stats[f, w]['rms_spot'])
+                self.best_focus_wavefront[f, w], self.best_focus_wavefront_kind[f, w] = best_focus(
+                    self.focs, stats[f, w]['opd_rms'])
+        ref = self.wvls.index(ref_wvl)
+        self.poly = np.stack([poly_merge(stats[f], image_pts[f], self.spectral_wts, ref) for f in range(F)])
+        self.best_focus_field, self.best_focus_field_kind = field_best_focus(self.focs, self.poly['rms_spot'])
+        self.best_focus, self.best_focus_kind = overall_best_focus(self.focs, self.poly['rms_spot'],
+                                                                   self.field_wts)
+
+
+def field_best_focus(focs, curves):
+    """:func:`best_focus` of each field's curve [F, K] -> (focus [F], kind [F])"""
+    res = [best_focus(focs, c) for c in np.asarray(curves, dtype=np.float64)]
+    return np.array([r[0] for r in res]), np.array([r[1] for r in res], dtype=object)
+
+
+def overall_best_focus(focs, curves, field_wts):
+    """:func:`best_focus` of sum_f wt_f curves[f] / sum_f wt_f"""
+    wt = np.asarray(field_wts, dtype=np.float64)
+    return best_focus(focs, (wt[:, None] * np.asarray(curves, dtype=np.float64)).sum(axis=0) / wt.sum())
+
+
+def through_focus_map(opt_model, focs, flds=None, wvls=None, num_rays=21, xy=None, field_wts=None,
+                      spectral_wts=None, ref_wvl=None, rows=False, **kwargs):
+    """Through-focus scans of every field at every wavelength in ONE device call
+    (rox_trace_through_focus_grids): item (f, w) is through_focus(opt_model, flds[f], wvls[w],
+    focs, num_rays, xy, ...) -- the same planes, grid and statistics, bit for bit -- and the
+    per-field polychromatic statistics, field curvature and white-light best focus follow on the
+    host (:class:`ThroughFocusMap`).  Defaults: the fields of osp['fov'] with their ``wt``, the
+    wavelengths of osp['wvls'] with its spectral_wts, ref_wvl = its central_wvl (a
+    workloads.TableModel has no osp: pass them).  A focus whose reference sphere the device
+    cannot express raises UnsupportedModelError for the whole call."""
+    from .engine import grid_rays
+    focs = _check_focs(focs, 'through_focus_map')
+    osp = opt_model['osp'] if flds is None or wvls is None or ref_wvl is None else None
+    if flds is None:
+        flds = list(osp['fov'].fields)
+        if field_wts is None:
+            field_wts = [f.wt for f in flds]
+    if wvls is None:
+        wvls = list(osp['wvls'].wavelengths)
+        if spectral_wts is None:
+            spectral_wts = list(osp['wvls'].spectral_wts)
+    flds, wvls = list(flds), [float(w) for w in wvls]
+    if field_wts is None:
+        field_wts = [getattr(f, 'wt', 1.0) for f in flds]
+    if spectral_wts is None:
+        spectral_wts = [1.0] * len(wvls)
+    if ref_wvl is None:
+        ref_wvl = osp['wvls'].central_wvl
+    ref_wvl = float(ref_wvl)
+    if ref_wvl not in wvls:
+        raise ValueError(f'through_focus_map: ref_wvl {ref_wvl} is not one of the wavelengths {wvls}')
+    F, W, K = len(flds), len(wvls), len(focs)
+    if not 1 <= F * W <= abi.MAX_FOCUS_ITEMS:
+        raise ValueError(f'through_focus_map: 1 to {abi.MAX_FOCUS_ITEMS} (field, wavelength) items, got {F * W}')
+    if len(field_wts) != F or len(spectral_wts) != W:
+        raise ValueError('through_focus_map: one weight per field and per wavelength')
+    planes, grids, fs, wis, opts_list = [], [], [], [], []
+    eng = None
+    for fld in flds:
+        for wvl in wvls:                                # each item as through_focus builds it
+            planes.append(_focus_planes(opt_model, fld, wvl, focs))
+            kw = dict(kwargs)
+            grids.append(_focus_grid(opt_model, fld, xy, num_rays, kw))
+            eng, f, wi, opts = _launch_setup(opt_model, fld, wvl, kw, abi.OUT_FAN)
+            fs.append(f)
+            wis.append(wi)
+            opts_list.append(opts)
+    out = eng.trace_pupil_grids_focus(fs, wis, grids, opts_list, planes, want_rows=rows)
+    stats, dev_rows = out if rows else (out, None)
+    stats = np.stack([_stats_in_waves(stats[i], opt_model, wvls[i % W]) for i in range(F * W)])
+    image_pts = np.array([[(p.image_pt[0], p.image_pt[1]) for p in ps] for ps in planes])
+    host_rows = status = None
+    if dev_rows is not None:
+        R = grid_rays(grids[0])
+        host_rows, status = dev_rows.to_host()
+        host_rows = np.array(host_rows[:, :, :, :R])
+        for i in range(F * W):
+            host_rows[i, :, 2] = (1 / opt_model.nm_to_sys_units(wvls[i % W])) * host_rows[i, :, 2]
+        host_rows = host_rows.reshape(F, W, K, 3, R)
+        status = np.asarray(status)[:, :R].reshape(F, W, R)
+    return ThroughFocusMap(focs, wvls, field_wts, spectral_wts, ref_wvl, stats.reshape(F, W, K),
+                           image_pts.reshape(F, W, K, 2), host_rows, status)
 
 
 # ---- point spread function ------------------------------------------------------

@@ -48,6 +48,24 @@ __global__ void pupil_axes_kernel(double x0, double y0, double sx, double sy, in
     }
 }
 
+// ... the axes of several grid definitions at once (rox_trace_through_focus_grids): thread 2 s
+// walks slot s's x axis and thread 2 s + 1 its y axis, prm[s] = (x0, y0, sx, sy), into
+// axes[s][2][num] -- each value the same repeated `+=` as pupil_axes_kernel's
+__global__ void pupil_axes_slots_kernel(const double *prm, int n_slots, int num, double *axes)
+{
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= 2 * n_slots)
+        return;
+    const int s = t >> 1, ax = t & 1;
+    double v = prm[4 * s + ax];
+    const double step = prm[4 * s + 2 + ax];
+    double *out = axes + ((size_t)s * 2 + ax) * num;
+    for (int k = 0; k < num; ++k) {
+        out[k] = v;
+        v += step;
+    }
+}
+
 // Diagnostic: the slim fp64 paths against the plain operators on pseudo-random
 // operands spanning the whole exponent range (zeros, denormals, band edges,
 // inf and nan included).  counts[0] = sqrt mismatches, counts[1] = division
@@ -214,6 +232,13 @@ struct StreamCtx {
     rox_focus_plane *h_focus = nullptr;
     int32_t h_focus_cap = 0;
     hipEvent_t focus_ev = nullptr;
+    // rox_trace_through_focus_grids (grow-only): the device block -- items, planes and axis
+    // parameters (copied in one transfer from the pinned block h_fbatch, rewritten only after
+    // that copy has completed: fbatch_ev), then the pupil axes, the statistics and the partial
+    // records of one launch
+    char *d_fbatch = nullptr, *h_fbatch = nullptr;
+    size_t d_fbatch_cap = 0, h_fbatch_cap = 0;
+    hipEvent_t fbatch_ev = nullptr;
     // Everything a pupil-grid call does between reading / rewriting the cached axes
     // (prepare_grid) and handing its launches to the stream is one critical section per
     // stream: two host threads enqueueing on the SAME stream take turns (their launches run
@@ -1021,8 +1046,9 @@ int check_field(const rox_field *fld)
     return 0;
 }
 
-int prepare_grid(rox_system *sys, const rox_field *fld, const rox_grid *grid, int32_t wvl_idx,
-                 const rox_opts *opts, const rox_out *out, hipStream_t st, TraceArgs &a)
+// the checks of a pupil-grid launch and its arguments, the pupil axes aside (nothing enqueued)
+int grid_args(rox_system *sys, const rox_field *fld, const rox_grid *grid, int32_t wvl_idx,
+              const rox_opts *opts, const rox_out *out, TraceArgs &a)
 {
     if (!grid)
         return fail(ROX_E_ARG, "null argument");
@@ -1044,6 +1070,24 @@ int prepare_grid(rox_system *sys, const rox_field *fld, const rox_grid *grid, in
     rc = check_opts(sys, opts, out, R);
     if (rc)
         return rc;
+    a = TraceArgs{};
+    a.n_rays = R;
+    a.axis_kind = grid->kind == ROX_GRID_FAN ? AXIS_LIST : AXIS_PRODUCT;
+    a.axis_num = grid->num;
+    a.row_begin = row0;
+    a.wvl_idx_all = wvl_idx;
+    a.fld = *fld;
+    a.opts = *opts;
+    a.out = *out;
+    return 0;
+}
+
+int prepare_grid(rox_system *sys, const rox_field *fld, const rox_grid *grid, int32_t wvl_idx,
+                 const rox_opts *opts, const rox_out *out, hipStream_t st, TraceArgs &a)
+{
+    int rc = grid_args(sys, fld, grid, wvl_idx, opts, out, a);
+    if (rc)
+        return rc;
     StreamCtx *cx = ctx_for(sys, st);
     if (!cx)
         return fail(ROX_E_NOMEM, "out of host memory");
@@ -1062,17 +1106,8 @@ int prepare_grid(rox_system *sys, const rox_field *fld, const rox_grid *grid, in
         memcpy(cx->axes_key, key, sizeof key);
         cx->axes_num = grid->num;
     }
-    a = TraceArgs{};
-    a.n_rays = R;
     a.px = px;
     a.py = py;
-    a.axis_kind = grid->kind == ROX_GRID_FAN ? AXIS_LIST : AXIS_PRODUCT;
-    a.axis_num = grid->num;
-    a.row_begin = row0;
-    a.wvl_idx_all = wvl_idx;
-    a.fld = *fld;
-    a.opts = *opts;
-    a.out = *out;
     return 0;
 }
 
@@ -1096,9 +1131,17 @@ __device__ inline FocusAcc shfl_xor_acc(const FocusAcc &a, int o)
     return r;
 }
 
+// BATCH (rox_trace_through_focus_grids): block (k, i) merges plane k of item i = blockIdx.y, whose
+// n_rec x n_planes records follow item i - 1's and whose statistics go to out[i][n_planes] --
+// within an item the very merges of a single call
+template <bool BATCH>
 __global__ void __launch_bounds__(kFocusFinishBlock)
 focus_finish_kernel(const FocusAcc *partial, int64_t n_rec, int32_t n_planes, rox_focus_stats *out)
 {
+    if (BATCH) {
+        partial += (size_t)blockIdx.y * n_rec * n_planes;
+        out += (size_t)blockIdx.y * n_planes;
+    }
     const int k = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     FocusAcc v{};
     for (int64_t i = threadIdx.x; i < n_rec; i += kFocusFinishBlock)
@@ -1372,6 +1415,10 @@ int rox_system_destroy(rox_system *sys)
         (void)hipHostFree(c->h_focus);
         if (c->focus_ev)
             (void)hipEventDestroy(c->focus_ev);
+        (void)hipFree(c->d_fbatch);
+        (void)hipHostFree(c->h_fbatch);
+        if (c->fbatch_ev)
+            (void)hipEventDestroy(c->fbatch_ev);
         for (hipEvent_t ev : c->item_ev)
             if (ev)
                 (void)hipEventDestroy(ev);
@@ -1572,13 +1619,211 @@ int rox_trace_through_focus(rox_system *sys, const rox_field *fld, const rox_gri
         dev_dst = at.type == hipMemoryTypeDevice;
     else
         (void)hipGetLastError();
-    hipLaunchKernelGGL(focus_finish_kernel, dim3((unsigned)n_planes), dim3(kFocusFinishBlock), 0, st,
+    hipLaunchKernelGGL(focus_finish_kernel<false>, dim3((unsigned)n_planes), dim3(kFocusFinishBlock), 0, st,
                        (const FocusAcc *)d_part,
                        blocks * (bs / 64), n_planes, dev_dst ? stats : d_stats);
     HIP_TRY(hipGetLastError());
     if (dev_dst)
         return 0;
     HIP_TRY(hipMemcpyAsync(stats, d_stats, sizeof(rox_focus_stats) * (size_t)n_planes, hipMemcpyDeviceToHost, st));
+    enq.unlock();
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+// Partial records of one batched through-focus launch stay under this many bytes: an item of a
+// large grid at K = 256 holds 512 workgroups x 8 waves x 256 planes x 72 B = 75 MB of them, so
+// the host splits a batch into consecutive launches of whole items (each item's workgroups,
+// records and merges are the same either way).
+constexpr size_t kFocusBatchPartialBytes = size_t(256) << 20;
+
+// n_items through-focus scans in one launch (include/roxtrace.h): item i is rox_trace_through_focus
+// with flds[i], grids[i], wvl_idx[i], opts[i] and planes[i][n_planes].
+int rox_trace_through_focus_grids(rox_system *sys, int32_t n_items, const rox_field *flds,
+                                  const int32_t *wvl_idx, const rox_grid *grids, const rox_opts *opts,
+                                  int32_t n_planes, const rox_focus_plane *planes, double *rows,
+                                  int64_t ld, uint8_t *status, rox_focus_stats *stats, void *stream)
+{
+    static const char kE[] = "rox_trace_through_focus_grids";
+    // every argument check comes before anything touches a device
+    if (n_items < 1 || n_items > ROX_MAX_FOCUS_ITEMS)
+        return fail(ROX_E_ARG, "%s: n_items %d outside [1, %d]", kE, n_items, ROX_MAX_FOCUS_ITEMS);
+    if (n_planes < 1 || n_planes > ROX_MAX_FOCUS_PLANES)
+        return fail(ROX_E_ARG, "%s: n_planes %d outside [1, %d]", kE, n_planes, ROX_MAX_FOCUS_PLANES);
+    if (!flds || !wvl_idx || !grids || !opts || !planes)
+        return fail(ROX_E_ARG, "%s: null array (flds, wvl_idx, grids, opts or planes)", kE);
+    if (!rows && !stats)
+        return fail(ROX_E_ARG, "%s: rows and stats are both null", kE);
+    const rox_grid &g0 = grids[0];
+    if (g0.num < 1)
+        return fail(ROX_E_ARG, "%s: item 0: grid.num must be >= 1", kE);
+    const bool fan = g0.kind == ROX_GRID_FAN;
+    const int64_t R = fan ? g0.num : (int64_t)(g0.row_count > 0 ? g0.row_count : g0.num) * g0.num;
+    if ((rows || status) && ld < R)
+        return fail(ROX_E_ARG, "%s: ld (%lld) < rays (%lld)", kE, (long long)ld, (long long)R);
+    if (R > (int64_t(1) << 28))
+        return fail(ROX_E_UNSUPPORTED, "%s: %lld rays (max 2^28 per item)", kE, (long long)R);
+    const rox_opts &o0 = opts[0];
+    for (int32_t i = 0; i < n_items; ++i) {
+        const rox_grid &g = grids[i];
+        if (g.kind != g0.kind || g.num != g0.num ||
+            (!fan && (g.row_begin != g0.row_begin || g.row_count != g0.row_count)))
+            return fail(ROX_E_ARG, "%s: item %d: grid kind, num and row block must match item 0's", kE, i);
+        const rox_opts &o = opts[i];
+        if (o.out_mode != ROX_OUT_FAN)
+            return fail(ROX_E_ARG, "%s: item %d: out_mode must be ROX_OUT_FAN (got %d)", kE, i, o.out_mode);
+        if (o.flags & (ROX_HOST_POINTERS | ROX_HITS_APPEND))
+            return fail(ROX_E_ARG, "%s: item %d: device pointers only, no ROX_HOST_POINTERS / "
+                                   "ROX_HITS_APPEND", kE, i);
+        if (((o.flags ^ o0.flags) & (ROX_FILTER_PHANTOMS | ROX_FAST_FP64)) ||
+            o.first_surf != o0.first_surf || o.last_surf != o0.last_surf)
+            return fail(ROX_E_ARG, "%s: item %d: ROX_FILTER_PHANTOMS, ROX_FAST_FP64, first_surf and "
+                                   "last_surf must match item 0's", kE, i);
+        for (int32_t p = 0; p < n_planes; ++p) {
+            const rox_wavefront &w = planes[(size_t)i * n_planes + p].wf;
+            if (!(w.ref_radius != 0.0) || w.kind < ROX_WF_FINITE || w.kind > ROX_WF_INF_SPLIT)
+                return fail(ROX_E_ARG, "%s: item %d plane %d: bad wf (ref_radius %g, kind %d)", kE, i, p,
+                            w.ref_radius, w.kind);
+        }
+    }
+    if (!sys)
+        return fail(ROX_E_ARG, "%s: null system", kE);
+    for (int32_t i = 0; i < n_items; ++i)
+        if (wvl_idx[i] < 0 || wvl_idx[i] >= sys->n_wvls)
+            return fail(ROX_E_ARG, "%s: item %d: wvl_idx %d out of range", kE, i, wvl_idx[i]);
+
+    // the items, validated one by one as the single call validates its launch (plane 0 in
+    // rox_opts; a stats-only item names a dummy seg, which the kernel never writes)
+    std::vector<FocusArgs> items((size_t)n_items);
+    double dummy = 0.0;
+    for (int32_t i = 0; i < n_items; ++i) {
+        const rox_focus_plane &p0 = planes[(size_t)i * n_planes];
+        rox_opts o = opts[i];
+        o.foc = p0.foc;
+        o.image_pt[0] = p0.image_pt[0];
+        o.image_pt[1] = p0.image_pt[1];
+        o.wf = p0.wf;
+        rox_out out{};
+        out.seg = rows ? rows + (size_t)i * n_planes * 3 * ld : &dummy;
+        out.ld = rows ? ld : R;
+        out.status = status ? status + (size_t)i * ld : nullptr;
+        const int rc = grid_args(sys, &flds[i], &grids[i], wvl_idx[i], &o, &out, items[i]);
+        if (rc) {
+            char msg[sizeof g_err];
+            memcpy(msg, g_err, sizeof msg);
+            return fail(rc, "%s: item %d: %s", kE, i, msg);
+        }
+    }
+
+    hipStream_t st = (hipStream_t)stream;
+    auto enq = enqueue_lock(sys, st);
+    StreamCtx *cx = ctx_for(sys, st);
+    if (!cx)
+        return fail(ROX_E_NOMEM, "out of host memory");
+    LaunchCfg k;
+    int inst = 0;
+    for (int32_t i = 0; i < n_items; ++i) {     // (the same instance for every item: same flags)
+        const int rc = launch_setup(sys, items[i], GEN_PUPIL, false, st, k, inst);
+        if (rc)
+            return rc;
+    }
+    const int bs = block_of(MODE_FOCUS, kInstances[inst]);
+    const int64_t blocks = std::min<int64_t>((R + bs - 1) / bs, (int64_t)sys->num_cus * kFocusBlocksPerCu);
+    const int64_t n_rec = blocks * (bs / 64);                   // partial records per (item, plane)
+    const size_t item_part = stats ? (size_t)n_rec * n_planes * sizeof(FocusAcc) : 0;
+    const int32_t per_launch = item_part ? (int32_t)std::max<size_t>(
+                                               1, std::min<size_t>(n_items, kFocusBatchPartialBytes / item_part))
+                                         : n_items;
+
+    // pupil axes: one slot per distinct (start, step) -- trace.py:566-570 step = (stop - start)/(num - 1)
+    std::vector<double> prm;
+    std::vector<int32_t> slot_of((size_t)n_items);
+    for (int32_t i = 0; i < n_items; ++i) {
+        const rox_grid &g = grids[i];
+        const double key[4] = {g.start[0], g.start[1], (g.stop[0] - g.start[0]) / (g.num - 1),
+                               (g.stop[1] - g.start[1]) / (g.num - 1)};
+        size_t s = 0;
+        while (s < prm.size() / 4 && memcmp(&prm[4 * s], key, sizeof key) != 0)
+            ++s;
+        if (s == prm.size() / 4)
+            prm.insert(prm.end(), key, key + 4);
+        slot_of[i] = (int32_t)s;
+    }
+    const int32_t n_slots = (int32_t)(prm.size() / 4);
+
+    // device block: [items][planes][axis parameters] (staged) [axes][statistics][partial records]
+    auto up256 = [](size_t b) { return (b + 255) & ~size_t(255); };
+    const size_t b_items = up256(sizeof(FocusArgs) * (size_t)n_items);
+    const size_t b_planes = up256(sizeof(rox_focus_plane) * (size_t)n_items * n_planes);
+    const size_t b_prm = up256(sizeof(double) * prm.size());
+    const size_t b_axes = up256(sizeof(double) * 2 * (size_t)n_slots * g0.num);
+    const size_t b_stats = stats ? up256(sizeof(rox_focus_stats) * (size_t)n_items * n_planes) : 0;
+    const size_t staged = b_items + b_planes + b_prm;
+    const size_t need = staged + b_axes + b_stats + item_part * (size_t)per_launch;
+    if (need > cx->d_fbatch_cap)
+        HIP_TRY(regrow(cx->d_fbatch, cx->d_fbatch_cap, need, need));
+    FocusArgs *d_items = (FocusArgs *)cx->d_fbatch;
+    rox_focus_plane *d_planes = (rox_focus_plane *)(cx->d_fbatch + b_items);
+    double *d_prm = (double *)(cx->d_fbatch + b_items + b_planes);
+    double *d_axes = (double *)(cx->d_fbatch + staged);
+    rox_focus_stats *d_stats = (rox_focus_stats *)(cx->d_fbatch + staged + b_axes);
+    char *d_part = cx->d_fbatch + staged + b_axes + b_stats;
+
+    for (int32_t i = 0; i < n_items; ++i) {
+        FocusArgs &f = items[i];
+        f.px = d_axes + (size_t)slot_of[i] * 2 * g0.num;
+        f.py = f.px + g0.num;
+        f.out.seg = nullptr;
+        f.ray_base = 0;
+        f.in_ld = R;
+        f.planes = d_planes + (size_t)i * n_planes;
+        f.n_planes = n_planes;
+        f.focus_rows = rows ? rows + (size_t)i * n_planes * 3 * ld : nullptr;
+        f.partial = stats ? (double *)(d_part + (size_t)(i % per_launch) * item_part) : nullptr;
+    }
+
+    // stage through the pinned block (once the previous call's copy has read it), one copy
+    if (!cx->fbatch_ev)
+        HIP_TRY(hipEventCreateWithFlags(&cx->fbatch_ev, hipEventDisableTiming));
+    else
+        HIP_TRY(hipEventSynchronize(cx->fbatch_ev));
+    if (staged > cx->h_fbatch_cap)
+        HIP_TRY(regrow(cx->h_fbatch, cx->h_fbatch_cap, staged, staged, hipHostMallocDefault));
+    memcpy(cx->h_fbatch, items.data(), sizeof(FocusArgs) * (size_t)n_items);
+    memcpy(cx->h_fbatch + b_items, planes, sizeof(rox_focus_plane) * (size_t)n_items * n_planes);
+    memcpy(cx->h_fbatch + b_items + b_planes, prm.data(), sizeof(double) * prm.size());
+    HIP_TRY(hipMemcpyAsync(cx->d_fbatch, cx->h_fbatch, staged, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipEventRecord(cx->fbatch_ev, st));
+    hipLaunchKernelGGL(pupil_axes_slots_kernel, dim3((unsigned)((2 * n_slots + 63) / 64)), dim3(64), 0, st,
+                       (const double *)d_prm, n_slots, g0.num, d_axes);
+    HIP_TRY(hipGetLastError());
+
+    bool dev_dst = false;
+    if (stats) {
+        hipPointerAttribute_t at;
+        if (hipPointerGetAttributes(&at, stats) == hipSuccess)
+            dev_dst = at.type == hipMemoryTypeDevice;
+        else
+            (void)hipGetLastError();
+    }
+    for (int32_t i0 = 0; i0 < n_items; i0 += per_launch) {
+        const int32_t n = std::min(per_launch, n_items - i0);
+        if (stats)      // every wave merges into its records: they start at n = 0
+            HIP_TRY(hipMemsetAsync(d_part, 0, item_part * (size_t)n, st));
+        k.grid = dim3((unsigned)blocks, (unsigned)n);
+        trace_fns(inst, k).focus_batch(k, d_items + i0);
+        HIP_TRY(hipGetLastError());
+        if (!stats)
+            continue;
+        hipLaunchKernelGGL(focus_finish_kernel<true>, dim3((unsigned)n_planes, (unsigned)n),
+                           dim3(kFocusFinishBlock), 0, st, (const FocusAcc *)d_part, n_rec, n_planes,
+                           (dev_dst ? stats : d_stats) + (size_t)i0 * n_planes);
+        HIP_TRY(hipGetLastError());
+    }
+    if (!stats || dev_dst)
+        return 0;
+    HIP_TRY(hipMemcpyAsync(stats, d_stats, sizeof(rox_focus_stats) * (size_t)n_items * n_planes,
+                           hipMemcpyDeviceToHost, st));
     enq.unlock();
     HIP_TRY(hipStreamSynchronize(st));
     return 0;

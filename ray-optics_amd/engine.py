@@ -140,7 +140,8 @@ assert FOCUS_STATS_DTYPE.itemsize == C.sizeof(abi.FocusStats)
 
 class FocusRows:
     """the per-ray rows of a through-focus launch on the device: ``rows`` [K, 3, R] (x abr,
-    y abr, OPD in system units; rays that fail keep NaN) and ``status`` [R]"""
+    y abr, OPD in system units; rays that fail keep NaN) and ``status`` [R] -- of a batched
+    launch [n_items, K, 3, R] and [n_items, R]"""
 
     def __init__(self, rows, status):
         self.rows = rows
@@ -877,6 +878,48 @@ class TraceEngine:
         if not want_rows:
             return stats
         return stats, FocusRows(rows[:, :, :R], status)
+
+    @_in_flight
+    def trace_pupil_grids_focus(self, flds, wvl_idxs, grids, opts_list, planes, want_rows=False,
+                                want_stats=True):
+        """rox_trace_through_focus_grids: n_items through-focus scans in one launch -- item i is
+        ``trace_pupil_grid_focus(flds[i], grids[i], wvl_idxs[i], opts_list[i], planes[i])``
+        (``planes``: n_items lists of K abi.FocusPlane each; the grids may differ in start /
+        stop only).  Returns the statistics as a FOCUS_STATS_DTYPE array [n_items, K] (None with
+        ``want_stats=False``) and, with ``want_rows``, ``(stats, FocusRows)`` with rows
+        [n_items, K, 3, R] and status [n_items, R] -- each item bit-identical to its single
+        call."""
+        t = self.torch
+        flds, grids, opts_list = list(flds), list(grids), list(opts_list)
+        planes = [list(p) for p in planes]
+        n = len(flds)
+        K = len(planes[0]) if planes else 0
+        if not (len(wvl_idxs) == len(grids) == len(opts_list) == len(planes) == n) or \
+                any(len(p) != K for p in planes):
+            raise EngineError('trace_pupil_grids_focus: one field, wavelength, grid, opts and '
+                              'list of K planes per item')
+        f_arr = (abi.Field * max(n, 1))(*flds)
+        w_arr = (C.c_int32 * max(n, 1))(*[int(w) for w in wvl_idxs])
+        g_arr = (abi.Grid * max(n, 1))(*grids)
+        o_arr = (abi.Opts * max(n, 1))(*opts_list)
+        p_arr = (abi.FocusPlane * max(n * K, 1))(*[p for ps in planes for p in ps])
+        R = grid_rays(grids[0]) if n else 0
+        ld = padded_ld(R)
+        rows = status = None
+        if want_rows:
+            rows = t.full((max(n, 1), max(K, 1), 3, ld), float('nan'), dtype=t.float64, device=self.device)
+            status = t.empty((max(n, 1), ld), dtype=t.uint8, device=self.device)
+        stats = np.empty((max(n, 1), max(K, 1)), dtype=FOCUS_STATS_DTYPE) if want_stats else None
+        with t.cuda.device(self.device):
+            _check(self.lib.rox_trace_through_focus_grids(
+                self._handle, n, f_arr, w_arr, g_arr, o_arr, K, p_arr,
+                rows.data_ptr() if rows is not None else None, ld,
+                status.data_ptr() if status is not None else None,
+                stats.ctypes.data if stats is not None else None, self._stream()),
+                'rox_trace_through_focus_grids')
+        if not want_rows:
+            return stats
+        return stats, FocusRows(rows[:, :, :, :R], status[:, :R])
 
     def _spot_stats(self, seg_ptr, ld, status_ptr, n_hits_ptr, n, layout, x_edges, y_edges):
         summ = abi.SpotSummary()
