@@ -592,6 +592,37 @@ int rox_trace_through_focus_grids(rox_system *sys, int32_t n_items, const rox_fi
                                   double *rows, int64_t ld, uint8_t *status,
                                   rox_focus_stats *stats, void *stream);
 
+/* Diffraction through focus: the PSF and Strehl ratio of every plane of a through-focus scan,
+ * read straight from the rows the two entries above write (the refocus of
+ * analyses.focus_wavefront, rayoptics/raytr/analyses.py:769-791, followed by calc_psf,
+ * :848-875, at every focus).
+ *   rows   DEVICE [n_items][n_planes][3][ld], status DEVICE [n_items][ld] (the through-focus
+ *          layouts).  Plane (i, k) reads component 2 (OPD, system units) of the first
+ *          ndim*ndim rays, ray r = a*ndim + b being grid[a][b].
+ *   wave_scale  HOST [n_items]: the OPD grid in waves of plane (i, k) is
+ *          wave_scale[i] * rows[i][k][2][r] where status[i][r] == ROX_OK, NaN elsewhere (one
+ *          IEEE product, as focus_wavefront forms convert_to_opd*opdelta).
+ *   psf    DEVICE [n_items][n_planes][maxdim][maxdim] or NULL: each plane bit-identical to
+ *          rox_calc_psf of that plane's OPD grid (same phase, twiddles, GEMM tiles and k order).
+ *   stats  host or device [n_items][n_planes] or NULL (not both psf and stats NULL).
+ *          strehl = |sum_ok exp(i 2 pi W)|^2 / n^2 over the OPD itself (a perfect wavefront
+ *          gives exactly 1), reduced in a fixed order: identical calls give bit-identical
+ *          statistics.  A host destination makes the call synchronous.
+ * ndim even with its block inside maxdim (the rox_calc_psf rules), n_items in
+ * [1, ROX_MAX_FOCUS_ITEMS], n_planes in [1, ROX_MAX_FOCUS_PLANES], ld >= ndim*ndim, finite
+ * wave_scale; argument errors return ROX_E_ARG naming the parameter before anything is
+ * enqueued.  Scratch is bounded per launch; larger batches run as consecutive launches with
+ * the same results.  Asynchronous on `stream` unless stats is host memory.                   */
+typedef struct rox_focus_psf_stats {
+    int64_t n;               /* rays with status ROX_OK on this plane's grid                */
+    double strehl;           /* |sum_ok exp(i 2 pi W)|^2 / n^2; NaN if n == 0               */
+    double psf_peak;         /* AP_max: the max of |F P F^T|^2 the returned PSF was divided by */
+    double reserved;
+} rox_focus_psf_stats;       /* 32 bytes */
+int rox_focus_psf(int32_t n_items, int32_t n_planes, const double *rows, int64_t ld,
+                  const uint8_t *status, const double *wave_scale, int32_t ndim, int32_t maxdim,
+                  double *psf, rox_focus_psf_stats *stats, void *stream);
+
 /* chief-ray aiming ------------------------------------------------------- */
 /* One problem per (field, wavelength): trace.iterate_ray
  * (rayoptics/raytr/trace.py:313-415) as trace.aim_chief_ray calls it

@@ -168,6 +168,12 @@ class FocusStats(C.Structure):
                 ('opd_min', C.c_double), ('opd_max', C.c_double)]
 
 
+class FocusPsfStats(C.Structure):
+    """rox_focus_psf_stats: one plane's ok-ray count, Strehl ratio and the PSF maximum"""
+    _fields_ = [('n', C.c_int64), ('strehl', C.c_double), ('psf_peak', C.c_double),
+                ('reserved', C.c_double)]
+
+
 MAX_FOCUS_PLANES = 256      # include/roxtrace.h ROX_MAX_FOCUS_PLANES
 MAX_FOCUS_ITEMS = 1024      # include/roxtrace.h ROX_MAX_FOCUS_ITEMS
 
@@ -196,6 +202,7 @@ assert C.sizeof(Aim) == 80
 assert C.sizeof(Enp) == 136
 assert C.sizeof(FocusPlane) == 544
 assert C.sizeof(FocusStats) == 72
+assert C.sizeof(FocusPsfStats) == 32
 
 # every symbol include/roxtrace.h declares (checked by tests/test_abi.py) ...
 EXPORTS = ('rox_abi_version', 'rox_device_count', 'rox_set_device',
@@ -205,7 +212,8 @@ EXPORTS = ('rox_abi_version', 'rox_device_count', 'rox_set_device',
            'rox_aim_chief_rays', 'rox_iterate_ray_raw', 'rox_find_real_enp', 'rox_calc_vignetting',
            'rox_iterate_pupil_rays', 'rox_calc_psf',
            'rox_pin_host_memory', 'rox_unpin_host_memory', 'rox_copy_async', 'rox_synchronize',
-           'rox_spot_stats', 'rox_trace_through_focus', 'rox_trace_through_focus_grids')
+           'rox_spot_stats', 'rox_trace_through_focus', 'rox_trace_through_focus_grids',
+           'rox_focus_psf')
 # ... and the measurement / self-test helpers of include/roxtrace_diag.h
 DIAG_EXPORTS = ('rox_time_pupil_grid', 'rox_selftest_fp64', 'rox_diag_pack_launches')
 
@@ -267,6 +275,8 @@ def declare(lib):
     lib.rox_trace_through_focus_grids.restype = C.c_int
     lib.rox_trace_through_focus_grids.argtypes = [vp, i32, P(Field), P(i32), P(Grid), P(Opts), i32,
                                                   P(FocusPlane), vp, i64, vp, vp, vp]
+    lib.rox_focus_psf.restype = C.c_int
+    lib.rox_focus_psf.argtypes = [i32, i32, vp, i64, vp, vp, i32, i32, vp, vp, vp]
     lib.rox_time_pupil_grid.restype = C.c_int
     lib.rox_time_pupil_grid.argtypes = [vp, P(Field), P(Grid), i32, P(Opts),
                                         P(Out), vp, i32, P(dbl)]

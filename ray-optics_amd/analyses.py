@@ -14,6 +14,8 @@
   through_focus_map  (new) through_focus for every field and wavelength in one launch, with
                         polychromatic statistics, field curvature and the white-light best
                         focus (rox_trace_through_focus_grids)
+  through_focus_psf  (new) diffraction through focus: the PSF and Strehl ratio of every plane
+                        of a through_focus scan, from the rows in HBM (rox_focus_psf)
 """
 import numpy as np
 
@@ -632,15 +634,18 @@ def _check_focs(focs, what):
     return focs
 
 
-def _focus_planes(opt_model, fld, wvl, focs, image_pt_2d=None, image_delta=None):
+def _focus_planes(opt_model, fld, wvl, focs, image_pt_2d=None, image_delta=None, radii=None):
     """the rox_focus_plane of every focus shift, each built as focus_wavefront / focus_fan build
     their one focus (rayoptics/raytr/analyses.py:313-342, 769-791): setup_pupil_coords at that
     foc, its reference sphere as rox_wavefront (the pre-calc / calc split on an infinite sphere,
-    :352-357).  The field keeps the last focus's chief ray and reference sphere."""
+    :352-357).  The field keeps the last focus's chief ray and reference sphere.  ``radii``, a
+    list, receives each focus's reference-sphere radius ref_sphere[2]."""
     from .table import wavefront_from_model
     planes = []
     for foc in focs:
         ref_sphere, cr_pkg = _setup_pupil_coords(opt_model, fld, wvl, foc, image_pt_2d, image_delta)
+        if radii is not None:
+            radii.append(ref_sphere[2])
         own = getattr(fld, 'rox_wavefront', None)       # table-backed models: prebuilt
         wf = own if own is not None else wavefront_from_model(opt_model, fld, cr_pkg, ref_sphere)
         wf = abi.Wavefront.from_buffer_copy(bytes(wf))
@@ -706,6 +711,95 @@ def through_focus(opt_model, fld, wvl, focs, num_rays=21, xy=None, image_pt_2d=N
         host_rows = np.array(host_rows[:, :, :grid_rays(grid)])
         host_rows[:, 2] = convert_to_opd * host_rows[:, 2]
     return ThroughFocus(focs, stats, host_rows, status)
+
+
+class ThroughFocusPSF:
+    """what :func:`through_focus_psf` returns.
+
+    focs       the focus shifts, as given
+    stats      [K] engine.FOCUS_STATS_DTYPE: the geometric statistics, as :func:`through_focus`
+               returns them
+    n          [K] rays with status OK on each plane's grid
+    strehl     [K] |sum_ok exp(i 2 pi W)|^2 / n^2 of each plane's OPD W in waves (NaN: no ray)
+    psf_peak   [K] the maximum of |FFT|^2 each PSF was normalised by (calc_psf's AP_max)
+    psf        [K, maxdim, maxdim] each plane's calc_psf -- NumPy, a torch tensor in HBM with
+               ``on_device=True``, or None with ``psf=False``
+    best_focus_strehl (+ ``_kind``): :func:`best_focus` of -strehl -- the diffraction focus
+    delta_x / delta_xp [K]: calc_psf_scaling (rayoptics/raytr/analyses.py:818-845) at each focus,
+               with that focus's reference-sphere radius; None without paraxial data"""
+
+    def __init__(self, focs, stats, psf_stats, psf, delta_x=None, delta_xp=None):
+        self.focs = np.asarray(focs, dtype=np.float64)
+        self.stats = stats
+        self.n = psf_stats['n'].copy()
+        self.strehl = psf_stats['strehl'].copy()
+        self.psf_peak = psf_stats['psf_peak'].copy()
+        self.psf = psf
+        self.delta_x = delta_x
+        self.delta_xp = delta_xp
+        self.best_focus_strehl, self.best_focus_strehl_kind = best_focus(self.focs, -self.strehl)
+
+
+def _psf_block_fits(ndim, maxdim):
+    """calc_psf's slice assignment (analyses.py:861-863) has a matching shape only for an even
+    ndim whose block fits inside maxdim (the rox_calc_psf / rox_focus_psf rules)"""
+    o = maxdim // 2 - (ndim // 2 - 1)
+    return ndim >= 2 and ndim % 2 == 0 and maxdim >= 2 and o >= 0 and o + ndim <= maxdim and maxdim <= 32768
+
+
+def psf_scaling(opt_model, wvl, ndim, maxdim, ref_sphere_radius):
+    """calc_psf_scaling (rayoptics/raytr/analyses.py:818-845), the same arithmetic, with the
+    reference-sphere radius given -> (delta_x, delta_xp); None for a model without paraxial data
+    (a workloads.TableModel has no 'analysis_results')"""
+    try:
+        results = opt_model['analysis_results']
+    except KeyError:
+        return None
+    fod = results['parax_data'].fod
+    wl = opt_model.nm_to_sys_units(wvl)
+    fill_factor = ndim/maxdim
+    max_D = 2 * fod.enp_radius / fill_factor
+    delta_x = max_D / maxdim
+    C = wl/fod.exp_radius
+    delta_theta = (fill_factor * C) / 2
+    delta_xp = delta_theta * ref_sphere_radius
+    return delta_x, delta_xp
+
+
+def through_focus_psf(opt_model, fld, wvl, focs, num_rays=32, maxdim=128, image_pt_2d=None,
+                      image_delta=None, psf=True, on_device=False, **kwargs):
+    """Diffraction through focus on the device: the square pupil grid trace_wavefront traces is
+    traced once and evaluated at every focus shift (as :func:`through_focus` with ``xy=None``),
+    and each plane's OPD grid -- what focus_wavefront returns at that focus
+    (rayoptics/raytr/analyses.py:769-791) -- goes through calc_psf (:848-875) and a Strehl ratio
+    without leaving HBM (rox_focus_psf).  Returns a :class:`ThroughFocusPSF`; the diffraction
+    best focus is the peak of the Strehl curve."""
+    from .engine import grid_rays
+    focs = _check_focs(focs, 'through_focus_psf')
+    num_rays, maxdim = int(num_rays), int(maxdim)
+    if num_rays < 2 or num_rays % 2:
+        raise ValueError(f'through_focus_psf: num_rays must be even and >= 2, got {num_rays}')
+    if not _psf_block_fits(num_rays, maxdim):
+        raise ValueError(f'through_focus_psf: the {num_rays} x {num_rays} grid does not fit in maxdim {maxdim}')
+    radii = []
+    planes = _focus_planes(opt_model, fld, wvl, focs, image_pt_2d, image_delta, radii=radii)
+    kw = dict(kwargs)
+    grid = _focus_grid(opt_model, fld, None, num_rays, kw)
+    assert grid_rays(grid) == num_rays * num_rays
+    eng, f, wi, opts = _launch_setup(opt_model, fld, wvl, kw, abi.OUT_FAN)
+    stats, dev_rows = eng.trace_pupil_grid_focus(f, grid, wi, opts, planes, want_rows=True, want_stats=True)
+    convert_to_opd = 1 / opt_model.nm_to_sys_units(wvl)
+    dev_psf, psf_stats = eng.focus_psf(dev_rows, num_rays, maxdim, convert_to_opd, want_psf=psf)
+    out_psf = None
+    if dev_psf is not None:
+        out_psf = dev_psf[0] if on_device else dev_psf[0].cpu().numpy()
+    delta_x = delta_xp = None
+    scal = [psf_scaling(opt_model, wvl, num_rays, maxdim, r) for r in radii]
+    if all(s is not None for s in scal):
+        delta_x = np.array([s[0] for s in scal])
+        delta_xp = np.array([s[1] for s in scal])
+    return ThroughFocusPSF(focs, _stats_in_waves(stats, opt_model, wvl), psf_stats[0], out_psf,
+                           delta_x, delta_xp)
 
 
 # polychromatic statistics per field and plane (through_focus_map): the weighted ray count,

@@ -16,6 +16,9 @@
 //   cgemm_nt<0>   T = F P            C[i][j] = sum_k A[i][k] B[j][k], complex
 //   cgemm_nt<1>   AP = |T F^T|^2 and its maximum (epilogue)
 //   psf_scale     AP / max
+// rox_focus_psf runs the same steps over a batch of through-focus planes (blockIdx.y / .z =
+// plane): focus_psf_prepare reads the rows and adds the Strehl partials, cgemm_nt_batch is
+// cgemm_nt per plane, focus_psf_scale and focus_psf_finish close each plane.
 // Up to maxdim 512 (the sizes figures use) the GEMMs take 32 x 32 workgroup tiles; the padded
 // planes are zeroed and F is formed once per shape, not per call.
 //
@@ -24,8 +27,11 @@
 // to a multiple of 64), so the GEMM loads need no guards.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cfloat>
+#include <cmath>
 #include <cstdint>
+#include <cstring>
 
 #include "rox_host.hpp"
 
@@ -166,12 +172,194 @@ __global__ __launch_bounds__(256) void cgemm_nt(const double *__restrict__ ar_, 
     }
 }
 
+// rox_focus_psf: cgemm_nt on problem z = blockIdx.z, its operands sa / sb / sc doubles after
+// problem 0's (a stride 0 shares F) and its maximum in maxbits[z].  The body is cgemm_nt's, line
+// for line, so a plane of a batch is computed exactly as a single call computes it (a shared
+// inline body changes the register allocation of cgemm_nt's own instances; these stay as they are).
+// KEEP THE TWO BODIES IN STEP: a change to one is made to the other.  The bit-identity test of
+// rox_focus_psf against rox_calc_psf (tests/test_gpu_through_focus_psf.py) is what checks it.
+template <int EPI, int TM>
+__global__ __launch_bounds__(256) void cgemm_nt_batch(const double *__restrict__ ar0, const double *__restrict__ ai0,
+                                                      int64_t sa, const double *__restrict__ br0,
+                                                      const double *__restrict__ bi0, int64_t sb, int kp, int I,
+                                                      int J, double *c00, double *c10, int64_t sc, int ldc,
+                                                      unsigned long long *maxbits0)
+{
+    const int64_t z = blockIdx.z;
+    const double *__restrict__ ar_ = ar0 + z * sa, *__restrict__ ai_ = ai0 + z * sa;
+    const double *__restrict__ br_ = br0 + z * sb, *__restrict__ bi_ = bi0 + z * sb;
+    double *c0 = c00 + z * sc, *c1 = EPI == 0 ? c10 + z * sc : nullptr;
+    unsigned long long *maxbits = maxbits0 + z;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int r = lane & 15, g = lane >> 4;
+    constexpr int WT = 16 * TM;             // rows / columns of the wave's tile; the block's is 2 WT
+    const int i0 = blockIdx.y * (2 * WT) + (wave >> 1) * WT;
+    const int j0 = blockIdx.x * (2 * WT) + (wave & 1) * WT;
+    d4 cr[TM][TM], ci[TM][TM];
+    for (int a = 0; a < TM; ++a)
+        for (int b = 0; b < TM; ++b)
+            cr[a][b] = ci[a][b] = d4{0., 0., 0., 0.};
+    const double *pa_r = ar_ + (size_t)(i0 + r) * kp + 4 * g;
+    const double *pa_i = ai_ + (size_t)(i0 + r) * kp + 4 * g;
+    const double *pb_r = br_ + (size_t)(j0 + r) * kp + 4 * g;
+    const double *pb_i = bi_ + (size_t)(j0 + r) * kp + 4 * g;
+    const size_t t16 = (size_t)16 * kp;
+    // software pipeline: the operands of k block i + 1 are in flight while the 64 MFMAs of
+    // block i issue (a lone wave per SIMD has nobody else to hide the load latency behind)
+    d4 xr[TM], xi[TM], yr[TM], yi[TM];
+    for (int t = 0; t < TM; ++t) {
+        xr[t] = *(const d4 *)(pa_r + t * t16);
+        xi[t] = *(const d4 *)(pa_i + t * t16);
+        yr[t] = *(const d4 *)(pb_r + t * t16);
+        yi[t] = *(const d4 *)(pb_i + t * t16);
+    }
+    for (int k0 = 0; k0 < kp; k0 += kKBlock) {
+        d4 nxr[TM], nxi[TM], nyr[TM], nyi[TM], xn[TM];
+        const int kn = (k0 + kKBlock < kp) ? k0 + kKBlock : k0;     // last block: a harmless reload
+        for (int t = 0; t < TM; ++t) {
+            nxr[t] = *(const d4 *)(pa_r + t * t16 + kn);
+            nxi[t] = *(const d4 *)(pa_i + t * t16 + kn);
+            nyr[t] = *(const d4 *)(pb_r + t * t16 + kn);
+            nyi[t] = *(const d4 *)(pb_i + t * t16 + kn);
+            xn[t] = -xi[t];
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+#pragma unroll
+            for (int a = 0; a < TM; ++a)
+#pragma unroll
+                for (int b = 0; b < TM; ++b) {
+                    cr[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(xr[a][e], yr[b][e], cr[a][b], 0, 0, 0);
+                    cr[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(xn[a][e], yi[b][e], cr[a][b], 0, 0, 0);
+                    ci[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(xr[a][e], yi[b][e], ci[a][b], 0, 0, 0);
+                    ci[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(xi[a][e], yr[b][e], ci[a][b], 0, 0, 0);
+                }
+        for (int t = 0; t < TM; ++t) {
+            xr[t] = nxr[t]; xi[t] = nxi[t]; yr[t] = nyr[t]; yi[t] = nyi[t];
+        }
+    }
+    double vmax = 0.0;
+    for (int a = 0; a < TM; ++a)
+        for (int b = 0; b < TM; ++b)
+            for (int q = 0; q < 4; ++q) {
+                const int row = i0 + 16 * a + g + 4 * q, col = j0 + 16 * b + r;
+                if (row >= I || col >= J)
+                    continue;
+                const size_t at = (size_t)row * ldc + col;
+                if (EPI == 0) {
+                    c0[at] = cr[a][b][q];
+                    c1[at] = ci[a][b][q];
+                } else {
+                    const double m = hypot(cr[a][b][q], ci[a][b][q]);     // abs(z)
+                    const double v = m * m;                               // ... ** 2
+                    c0[at] = v;
+                    vmax = fmax(vmax, v);                                 // nanmax
+                }
+            }
+    if (EPI == 1) {
+        for (int off = 32; off; off >>= 1)
+            vmax = fmax(vmax, __shfl_xor(vmax, off));
+        if (lane == 0)
+            atomicMax(maxbits, (unsigned long long)__double_as_longlong(vmax));
+    }
+}
+
+
 __global__ void psf_scale(double *ap, int64_t count, const unsigned long long *maxbits)
 {
     const double m = __longlong_as_double((long long)*maxbits);
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count;
          i += (int64_t)gridDim.x * blockDim.x)
         ap[i] = ap[i] / m;                                                // AP / AP_max
+}
+
+// ---- rox_focus_psf ----------------------------------------------------------------------------
+// Plane q = blockIdx.y of a launch is plane p0 + q of the call, item (p0 + q) / n_planes.
+constexpr int kFocusBlock = 256;
+
+// P^T of plane q from the through-focus rows (the OPD grid in waves is one product, NaN where a
+// ray failed, exactly what the host hands rox_calc_psf), the Strehl partial record of this
+// workgroup (ok rays, sum cos, sum sin of 2 pi W -- of the OPD, not the zeroed phase), and the
+// plane's maximum reset for the second GEMM.
+__global__ __launch_bounds__(kFocusBlock) void focus_psf_prepare(
+    const double *__restrict__ rows, int64_t ld, const uint8_t *__restrict__ status,
+    const double *__restrict__ scale, int32_t n_planes, int64_t p0, int n, int kp, int64_t plane,
+    double *ptr, double *pti, double *partial, unsigned long long *maxbits)
+{
+    __shared__ double red[kFocusBlock / 64][3];
+    const int64_t q = blockIdx.y, gp = p0 + q, item = gp / n_planes;
+    const int64_t idx = (int64_t)blockIdx.x * kFocusBlock + threadIdx.x;
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        maxbits[q] = 0;
+    double cnt = 0.0, sc = 0.0, ss = 0.0;
+    if (idx < (int64_t)n * n) {
+        const int a = (int)(idx / n), b = (int)(idx % n);
+        double w = __builtin_nan("");
+        if (status[item * ld + idx] == ROX_OK) {
+            w = scale[item] * rows[(gp * 3 + 2) * ld + idx];
+            sincos(6.283185307179586 * w, &ss, &sc);
+            cnt = 1.0;
+        }
+        double s, c;
+        pupil_phase(w, c, s);
+        ptr[q * plane + (int64_t)b * kp + a] = c;
+        pti[q * plane + (int64_t)b * kp + a] = s;
+    }
+    // fixed-order reduction: a butterfly in each wave, then the waves in order
+    for (int off = 32; off; off >>= 1) {
+        cnt += __shfl_xor(cnt, off);
+        sc += __shfl_xor(sc, off);
+        ss += __shfl_xor(ss, off);
+    }
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        red[wave][0] = cnt;
+        red[wave][1] = sc;
+        red[wave][2] = ss;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t[3] = {0.0, 0.0, 0.0};
+        for (int w = 0; w < kFocusBlock / 64; ++w)
+            for (int j = 0; j < 3; ++j)
+                t[j] += red[w][j];
+        double *rec = partial + (q * gridDim.x + blockIdx.x) * 3;
+        rec[0] = t[0];
+        rec[1] = t[1];
+        rec[2] = t[2];
+    }
+}
+
+// plane q's PSF divided by its maximum (psf_scale per plane)
+__global__ void focus_psf_scale(double *ap, int64_t count, int64_t stride, const unsigned long long *maxbits)
+{
+    const double m = __longlong_as_double((long long)maxbits[blockIdx.y]);
+    double *p = ap + (int64_t)blockIdx.y * stride;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count;
+         i += (int64_t)gridDim.x * blockDim.x)
+        p[i] = p[i] / m;                                                  // AP / AP_max
+}
+
+// one thread per plane: the workgroups' partial records in order -> rox_focus_psf_stats
+__global__ void focus_psf_finish(const double *partial, int64_t n_rec, int32_t count,
+                                 const unsigned long long *maxbits, rox_focus_psf_stats *out)
+{
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= count)
+        return;
+    double cnt = 0.0, sc = 0.0, ss = 0.0;
+    for (int64_t r = 0; r < n_rec; ++r) {
+        const double *rec = partial + ((int64_t)q * n_rec + r) * 3;
+        cnt += rec[0];
+        sc += rec[1];
+        ss += rec[2];
+    }
+    rox_focus_psf_stats st;
+    st.n = (int64_t)cnt;
+    st.strehl = cnt > 0.0 ? (sc * sc + ss * ss) / (cnt * cnt) : __builtin_nan("");
+    st.psf_peak = __longlong_as_double((long long)maxbits[q]);
+    st.reserved = 0.0;
+    out[q] = st;
 }
 
 // grow-only workspace per (device, stream)
@@ -276,5 +464,185 @@ extern "C" int rox_calc_psf(const double *opd, int32_t ndim, int32_t maxdim, dou
         HIP_TRY(hipMemcpyAsync(psf, d_psf, b_psf, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
     }
+    return 0;
+}
+
+namespace {
+
+constexpr char kFocusWhere[] = "rox_focus_psf: ";
+
+// scratch per launch (T and P^T of each plane, the PSF when psf is NULL) is capped; larger
+// batches run as consecutive launches (as rox_trace_through_focus_grids caps its partials)
+constexpr size_t kFocusPsfScratchBytes = size_t(256) << 20;
+
+// grow-only workspace per (device, stream):
+//   [F: fr fi] [plane blocks: tr ti ptr pti, one per plane of a launch] [per call: maximums,
+//   partial records, statistics, wave scales, PSF scratch]
+// F and the plane blocks are zero-padded to the GEMM tiles, so they sit at offsets that depend
+// on the shape alone; the per-call region behind them may overwrite plane blocks a later, larger
+// call then zeroes again (`clean` counts the plane blocks known to be zero-padded).
+struct FocusWorkspace {
+    char *buf = nullptr;
+    size_t cap = 0;
+    int64_t shape[2] = {0, 0};      // (n, M) F was formed for
+    int64_t clean = 0;
+    double *h_scale = nullptr;      // pinned staging of wave_scale, reused once ev has passed
+    size_t h_cap = 0;
+    hipEvent_t ev = nullptr;
+};
+rox::PerStream<FocusWorkspace> g_focus_ws;
+
+}  // namespace
+
+extern "C" int rox_focus_psf(int32_t n_items, int32_t n_planes, const double *rows, int64_t ld,
+                             const uint8_t *status, const double *wave_scale, int32_t ndim, int32_t maxdim,
+                             double *psf, rox_focus_psf_stats *stats, void *stream)
+{
+    static const char kE[] = "rox_focus_psf";
+    const char *const kHipWhere = kFocusWhere;
+    // every argument check comes before anything touches a device
+    if (n_items < 1 || n_items > ROX_MAX_FOCUS_ITEMS)
+        return rox::host_fail(ROX_E_ARG, "%s: n_items %d outside [1, %d]", kE, n_items, ROX_MAX_FOCUS_ITEMS);
+    if (n_planes < 1 || n_planes > ROX_MAX_FOCUS_PLANES)
+        return rox::host_fail(ROX_E_ARG, "%s: n_planes %d outside [1, %d]", kE, n_planes, ROX_MAX_FOCUS_PLANES);
+    if (ndim < 2 || (ndim & 1))
+        return rox::host_fail(ROX_E_ARG, "%s: ndim %d must be even and >= 2", kE, ndim);
+    const int n = ndim, M = maxdim;
+    const int o = M / 2 - (n / 2 - 1);
+    if (M < 2 || o < 0 || o + n > M)
+        return rox::host_fail(ROX_E_ARG, "%s: the ndim %d block does not fit in maxdim %d", kE, n, M);
+    if (M > 32768)
+        return rox::host_fail(ROX_E_ARG, "%s: maxdim %d > 32768", kE, M);
+    if (ld < (int64_t)n * n)
+        return rox::host_fail(ROX_E_ARG, "%s: ld %lld < ndim*ndim %lld", kE, (long long)ld, (long long)n * n);
+    if (!rows || !status || !wave_scale)
+        return rox::host_fail(ROX_E_ARG, "%s: null rows, status or wave_scale", kE);
+    for (int32_t i = 0; i < n_items; ++i)
+        if (!std::isfinite(wave_scale[i]))
+            return rox::host_fail(ROX_E_ARG, "%s: wave_scale[%d] = %g is not finite", kE, i, wave_scale[i]);
+    if (!psf && !stats)
+        return rox::host_fail(ROX_E_ARG, "%s: psf and stats are both null", kE);
+
+    hipStream_t st = (hipStream_t)stream;
+    int device = 0;
+    HIP_TRY(hipGetDevice(&device));
+    auto *slot = g_focus_ws.get(device, st);
+    if (!slot)
+        return rox::host_fail(ROX_E_NOMEM, "%s: out of host memory", kE);
+    std::lock_guard<std::mutex> turn(slot->mu);
+    FocusWorkspace *ws = &slot->data;
+
+    // the shapes of rox_calc_psf, per plane
+    const int64_t kp = round_up(n, kKBlock), mp = round_up(M, kTile), np_ = round_up(n, kTile);
+    const int64_t f_el = mp * kp, p_el = np_ * kp;              // doubles of an F / T and a P^T plane
+    const int64_t blk_el = 2 * f_el + 2 * p_el;                 // one plane block: tr ti ptr pti
+    const int64_t psf_el = (int64_t)M * M;
+    const int64_t nblk = ((int64_t)n * n + kFocusBlock - 1) / kFocusBlock;
+    const int64_t total = (int64_t)n_items * n_planes;
+    auto up256 = [](size_t b) { return (b + 255) & ~size_t(255); };
+    const size_t per_plane = sizeof(double) * (size_t)(blk_el + (psf ? 0 : psf_el) + 3 * nblk) + 8;
+    const int64_t chunk = std::max<int64_t>(
+        1, std::min<int64_t>({total, (int64_t)(kFocusPsfScratchBytes / per_plane), 65535}));
+    const size_t b_f = sizeof(double) * 2 * (size_t)f_el;
+    const size_t b_blocks = sizeof(double) * (size_t)blk_el * chunk;
+    const size_t b_max = up256(sizeof(unsigned long long) * chunk);
+    const size_t b_part = up256(sizeof(double) * 3 * (size_t)nblk * chunk);
+    const size_t b_stats = up256(sizeof(rox_focus_psf_stats) * (size_t)total);
+    const size_t b_scale = up256(sizeof(double) * (size_t)n_items);
+    const size_t b_psf = psf ? 0 : sizeof(double) * (size_t)psf_el * chunk;
+    const size_t need = b_f + b_blocks + b_max + b_part + b_stats + b_scale + b_psf;
+    if (ws->cap < need) {
+        HIP_TRY(rox::regrow(ws->buf, ws->cap, need, need));
+        ws->shape[0] = ws->shape[1] = 0;
+        ws->clean = 0;
+    }
+    double *fr = (double *)ws->buf, *fi = fr + f_el;
+    double *blocks = fr + 2 * f_el;
+    char *p = ws->buf + b_f + b_blocks;
+    unsigned long long *maxbits = (unsigned long long *)p;  p += b_max;
+    double *partial = (double *)p;                          p += b_part;
+    rox_focus_psf_stats *d_stats = (rox_focus_psf_stats *)p; p += b_stats;
+    double *d_scale = (double *)p;                          p += b_scale;
+    double *scratch_psf = (double *)p;
+
+    // F (and zeroed plane blocks) for this shape; plane blocks beyond `clean` are zeroed first
+    const bool new_shape = ws->shape[0] != n || ws->shape[1] != M;
+    if (new_shape) {
+        HIP_TRY(hipMemsetAsync(ws->buf, 0, b_f, st));
+        ws->clean = 0;
+    }
+    if (ws->clean < chunk)
+        HIP_TRY(hipMemsetAsync(blocks + ws->clean * blk_el, 0,
+                               sizeof(double) * (size_t)blk_el * (chunk - ws->clean), st));
+    ws->clean = chunk;                      // the per-call region starts right behind the chunk
+    if (new_shape) {
+        hipLaunchKernelGGL(psf_prepare, dim3((unsigned)(((int64_t)M * n + 255) / 256)), dim3(256), 0, st,
+                           (const double *)nullptr, n, M, (int)kp, (double *)nullptr, (double *)nullptr, fr, fi,
+                           (unsigned long long *)nullptr, 0, 1);
+        HIP_TRY(hipGetLastError());
+        ws->shape[0] = n;
+        ws->shape[1] = M;
+    }
+
+    // wave_scale -> pinned block (once the previous call's copy has read it) -> device
+    if (!ws->ev)
+        HIP_TRY(hipEventCreateWithFlags(&ws->ev, hipEventDisableTiming));
+    else
+        HIP_TRY(hipEventSynchronize(ws->ev));
+    if (ws->h_cap < (size_t)n_items)
+        HIP_TRY(rox::regrow(ws->h_scale, ws->h_cap, (size_t)n_items, sizeof(double) * (size_t)n_items,
+                            hipHostMallocDefault));
+    memcpy(ws->h_scale, wave_scale, sizeof(double) * (size_t)n_items);
+    HIP_TRY(hipMemcpyAsync(d_scale, ws->h_scale, sizeof(double) * (size_t)n_items, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipEventRecord(ws->ev, st));
+
+    bool dev_dst = false;
+    if (stats) {
+        hipPointerAttribute_t at;
+        if (hipPointerGetAttributes(&at, stats) == hipSuccess)
+            dev_dst = at.type == hipMemoryTypeDevice;
+        else
+            (void)hipGetLastError();
+    }
+    rox_focus_psf_stats *out_stats = dev_dst ? stats : d_stats;
+    const bool small = M <= 512;
+    const int W = small ? 32 : kTile;
+    for (int64_t p0 = 0; p0 < total; p0 += chunk) {
+        const int64_t c = std::min(chunk, total - p0);
+        double *tr = blocks, *ti = blocks + f_el, *ptr = blocks + 2 * f_el, *pti = ptr + p_el;
+        double *dst = psf ? psf + p0 * psf_el : scratch_psf;
+        hipLaunchKernelGGL(focus_psf_prepare, dim3((unsigned)nblk, (unsigned)c), dim3(kFocusBlock), 0, st,
+                           rows, ld, status, (const double *)d_scale, n_planes, p0, n, (int)kp, blk_el, ptr, pti,
+                           partial, maxbits);
+        // T = F P per plane, then AP = |T F^T|^2 with each plane's maximum: the tile instance
+        // rox_calc_psf takes for this maxdim
+        const dim3 g1((unsigned)(np_ / W), (unsigned)(mp / W), (unsigned)c);
+        const dim3 g2((unsigned)(mp / W), (unsigned)(mp / W), (unsigned)c);
+        if (small) {
+            hipLaunchKernelGGL((cgemm_nt_batch<0, 1>), g1, dim3(256), 0, st, fr, fi, (int64_t)0, ptr, pti, blk_el,
+                               (int)kp, M, n, tr, ti, blk_el, (int)kp, maxbits);
+            hipLaunchKernelGGL((cgemm_nt_batch<1, 1>), g2, dim3(256), 0, st, tr, ti, blk_el, fr, fi, (int64_t)0,
+                               (int)kp, M, M, dst, (double *)nullptr, psf_el, M, maxbits);
+        } else {
+            hipLaunchKernelGGL((cgemm_nt_batch<0, 2>), g1, dim3(256), 0, st, fr, fi, (int64_t)0, ptr, pti, blk_el,
+                               (int)kp, M, n, tr, ti, blk_el, (int)kp, maxbits);
+            hipLaunchKernelGGL((cgemm_nt_batch<1, 2>), g2, dim3(256), 0, st, tr, ti, blk_el, fr, fi, (int64_t)0,
+                               (int)kp, M, M, dst, (double *)nullptr, psf_el, M, maxbits);
+        }
+        if (psf) {
+            const int64_t bx = std::min<int64_t>((psf_el + 255) / 256, 1024);
+            hipLaunchKernelGGL(focus_psf_scale, dim3((unsigned)bx, (unsigned)c), dim3(256), 0, st, dst, psf_el,
+                               psf_el, (const unsigned long long *)maxbits);
+        }
+        if (stats)
+            hipLaunchKernelGGL(focus_psf_finish, dim3((unsigned)((c + 63) / 64)), dim3(64), 0, st,
+                               (const double *)partial, nblk, (int32_t)c, (const unsigned long long *)maxbits,
+                               out_stats + p0);
+        HIP_TRY(hipGetLastError());
+    }
+    if (!stats || dev_dst)
+        return 0;
+    HIP_TRY(hipMemcpyAsync(stats, d_stats, sizeof(rox_focus_psf_stats) * (size_t)total, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     return 0;
 }

@@ -138,6 +138,12 @@ FOCUS_STATS_DTYPE = np.dtype([(name, np.int64 if name == 'n' else np.float64)
 assert FOCUS_STATS_DTYPE.itemsize == C.sizeof(abi.FocusStats)
 
 
+# rox_focus_psf_stats: what focus_psf returns
+FOCUS_PSF_STATS_DTYPE = np.dtype([(name, np.int64 if name == 'n' else np.float64)
+                                  for name, _t in abi.FocusPsfStats._fields_])
+assert FOCUS_PSF_STATS_DTYPE.itemsize == C.sizeof(abi.FocusPsfStats)
+
+
 class FocusRows:
     """the per-ray rows of a through-focus launch on the device: ``rows`` [K, 3, R] (x abr,
     y abr, OPD in system units; rays that fail keep NaN) and ``status`` [R] -- of a batched
@@ -920,6 +926,40 @@ class TraceEngine:
         if not want_rows:
             return stats
         return stats, FocusRows(rows[:, :, :, :R], status[:, :R])
+
+    @_in_flight
+    def focus_psf(self, focus_rows, ndim, maxdim, wave_scale, want_psf=True):
+        """rox_focus_psf over the rows of a through-focus launch (``focus_rows``: the FocusRows
+        trace_pupil_grid_focus / trace_pupil_grids_focus return, still in HBM): the OPD grid in
+        waves of each plane is ``wave_scale[i] * OPD`` of item i's first ndim*ndim rays (NaN where
+        a ray failed), its PSF bit-identical to calc_psf of that grid.  Returns ``(psf, stats)``:
+        the PSFs as a float64 tensor in HBM [n_items, K, maxdim, maxdim] (None without
+        ``want_psf``) and a FOCUS_PSF_STATS_DTYPE array [n_items, K] (n, strehl, psf_peak)."""
+        t = self.torch
+        rows, status = focus_rows.rows, focus_rows.status
+        single = rows.dim() == 3
+        if single:
+            rows, status = rows.unsqueeze(0), status.unsqueeze(0)
+        n_items, K = int(rows.shape[0]), int(rows.shape[1])
+        ld = int(rows.stride(2))
+        if rows.dtype != t.float64 or rows.stride(3) != 1 or rows.stride(1) != 3 * ld or \
+                rows.stride(0) != K * 3 * ld or status.stride(-1) != 1 or \
+                (n_items > 1 and status.stride(0) != ld):
+            raise EngineError('focus_psf reads the [n_items][K][3][ld] rows and [n_items][ld] status '
+                              'of a through-focus launch')
+        scale = np.ascontiguousarray(np.broadcast_to(np.asarray(wave_scale, dtype=np.float64), (n_items,)))
+        ndim, maxdim = int(ndim), int(maxdim)
+        if ndim * ndim > int(rows.shape[3]) or ndim * ndim > int(status.shape[-1]):
+            raise EngineError(f'focus_psf: a {ndim} x {ndim} grid needs {ndim * ndim} rays, the rows hold '
+                              f'{int(rows.shape[3])}')
+        psf = t.empty((n_items, K, maxdim, maxdim), dtype=t.float64, device=self.device) if want_psf else None
+        stats = np.empty((n_items, K), dtype=FOCUS_PSF_STATS_DTYPE)
+        with t.cuda.device(self.device):
+            _check(self.lib.rox_focus_psf(n_items, K, rows.data_ptr(), ld, status.data_ptr(),
+                                          scale.ctypes.data, ndim, maxdim,
+                                          psf.data_ptr() if psf is not None else None,
+                                          stats.ctypes.data, self._stream()), 'rox_focus_psf')
+        return psf, stats
 
     def _spot_stats(self, seg_ptr, ld, status_ptr, n_hits_ptr, n, layout, x_edges, y_edges):
         summ = abi.SpotSummary()
