@@ -623,6 +623,35 @@ int rox_focus_psf(int32_t n_items, int32_t n_planes, const double *rows, int64_t
                   const uint8_t *status, const double *wave_scale, int32_t ndim, int32_t maxdim,
                   double *psf, rox_focus_psf_stats *stats, void *stream);
 
+/* MTF through focus: the line OTFs of every PSF rox_focus_psf writes, along image x and y.
+ * A PSF is M x M (M = maxdim); axis 0 is the pupil / image x direction (grid[a][b], a stepping
+ * pupil x), axis 1 is y, pixel (M/2, M/2) is the plane's image point, and pixel j of direction
+ * d sits at image coordinate -p (j - M/2), p the plane's pitch (calc_psf_scaling's delta_xp,
+ * rayoptics/raytr/analyses.py:818-845).  The sign puts the OTF phase in image coordinates: the
+ * PSF's centroid there has the sign of the geometric spot centroid about the image point.
+ *   LSF_x[j] = sum_l PSF[j][l],  LSF_y[l] = sum_j PSF[j][l]
+ *   OTF_d(nu) = sum_j LSF_d[j] exp(+2 pi i nu p (j - M/2)) / sum_j LSF_d[j],  MTF = |OTF|
+ * (the DTFT at nu cycles per system unit; at nu = m / (M p) the normalised circular
+ * autocorrelation of calc_psf's padded pupil array).
+ *   psf    DEVICE [n_items][n_planes][maxdim][maxdim] (the rox_focus_psf layout)
+ *   pitch  HOST [n_items][n_planes], each finite and > 0
+ *   freqs  HOST [n_freq], each finite and >= 0 (cycles per system unit: lp/mm for a mm system)
+ *   otf    host or device [n_items][n_planes][2][n_freq][2]: (re, im), direction 0 = x, 1 = y.
+ *          nu = 0 gives exactly (1, 0) (the normaliser is the zero-phase DTFT's sum, in its
+ *          order).  NaN where nu p > 1/2 (above the PSF grid's Nyquist frequency) or where the
+ *          PSF's sum is not positive and finite (a plane no ray reached).  Reduced in a fixed
+ *          order without atomics: identical calls give bit-identical results.  A host
+ *          destination makes the call synchronous.
+ * n_items in [1, ROX_MAX_FOCUS_ITEMS], n_planes in [1, ROX_MAX_FOCUS_PLANES], maxdim in
+ * [2, 32768], n_freq in [1, ROX_MAX_MTF_FREQS]; argument errors return ROX_E_ARG naming the
+ * parameter before anything is enqueued.  Scratch is bounded per launch; larger stacks run as
+ * consecutive launches with the same results.  Asynchronous on `stream` unless otf is host
+ * memory.                                                                                       */
+#define ROX_MAX_MTF_FREQS 1024
+int rox_focus_mtf(int32_t n_items, int32_t n_planes, const double *psf, int32_t maxdim,
+                  const double *pitch, int32_t n_freq, const double *freqs,
+                  double *otf, void *stream);
+
 /* chief-ray aiming ------------------------------------------------------- */
 /* One problem per (field, wavelength): trace.iterate_ray
  * (rayoptics/raytr/trace.py:313-415) as trace.aim_chief_ray calls it

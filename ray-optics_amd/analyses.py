@@ -16,6 +16,8 @@
                         focus (rox_trace_through_focus_grids)
   through_focus_psf  (new) diffraction through focus: the PSF and Strehl ratio of every plane
                         of a through_focus scan, from the rows in HBM (rox_focus_psf)
+  through_focus_mtf  (new) the MTF through focus along image x and y, per field and
+                        polychromatic, from the PSFs in HBM (rox_focus_mtf)
 """
 import numpy as np
 
@@ -907,18 +909,10 @@ def overall_best_focus(focs, curves, field_wts):
     return best_focus(focs, (wt[:, None] * np.asarray(curves, dtype=np.float64)).sum(axis=0) / wt.sum())
 
 
-def through_focus_map(opt_model, focs, flds=None, wvls=None, num_rays=21, xy=None, field_wts=None,
-                      spectral_wts=None, ref_wvl=None, rows=False, **kwargs):
-    """Through-focus scans of every field at every wavelength in ONE device call
-    (rox_trace_through_focus_grids): item (f, w) is through_focus(opt_model, flds[f], wvls[w],
-    focs, num_rays, xy, ...) -- the same planes, grid and statistics, bit for bit -- and the
-    per-field polychromatic statistics, field curvature and white-light best focus follow on the
-    host (:class:`ThroughFocusMap`).  Defaults: the fields of osp['fov'] with their ``wt``, the
-    wavelengths of osp['wvls'] with its spectral_wts, ref_wvl = its central_wvl (a
-    workloads.TableModel has no osp: pass them).  A focus whose reference sphere the device
-    cannot express raises UnsupportedModelError for the whole call."""
-    from .engine import grid_rays
-    focs = _check_focs(focs, 'through_focus_map')
+def _map_spec(opt_model, flds, wvls, field_wts, spectral_wts, ref_wvl, what):
+    """the fields, wavelengths and weights of a map: defaults from osp (the fields of osp['fov']
+    with their ``wt``, the wavelengths of osp['wvls'] with its spectral_wts, ref_wvl = its
+    central_wvl), checked -> (flds, wvls, field_wts, spectral_wts, ref_wvl)"""
     osp = opt_model['osp'] if flds is None or wvls is None or ref_wvl is None else None
     if flds is None:
         flds = list(osp['fov'].fields)
@@ -937,23 +931,52 @@ def through_focus_map(opt_model, focs, flds=None, wvls=None, num_rays=21, xy=Non
         ref_wvl = osp['wvls'].central_wvl
     ref_wvl = float(ref_wvl)
     if ref_wvl not in wvls:
-        raise ValueError(f'through_focus_map: ref_wvl {ref_wvl} is not one of the wavelengths {wvls}')
-    F, W, K = len(flds), len(wvls), len(focs)
+        raise ValueError(f'{what}: ref_wvl {ref_wvl} is not one of the wavelengths {wvls}')
+    F, W = len(flds), len(wvls)
     if not 1 <= F * W <= abi.MAX_FOCUS_ITEMS:
-        raise ValueError(f'through_focus_map: 1 to {abi.MAX_FOCUS_ITEMS} (field, wavelength) items, got {F * W}')
+        raise ValueError(f'{what}: 1 to {abi.MAX_FOCUS_ITEMS} (field, wavelength) items, got {F * W}')
     if len(field_wts) != F or len(spectral_wts) != W:
-        raise ValueError('through_focus_map: one weight per field and per wavelength')
+        raise ValueError(f'{what}: one weight per field and per wavelength')
+    return flds, wvls, field_wts, spectral_wts, ref_wvl
+
+
+def _map_items(opt_model, flds, wvls, focs, xy, num_rays, kwargs, radii=None):
+    """every (field, wavelength) item of a map, field-major, each built as through_focus builds
+    its one scan -> (engine, fields, wavelength indices, grids, options, planes); ``radii``, a
+    list, receives each item's list of reference-sphere radii"""
     planes, grids, fs, wis, opts_list = [], [], [], [], []
     eng = None
     for fld in flds:
         for wvl in wvls:                                # each item as through_focus builds it
-            planes.append(_focus_planes(opt_model, fld, wvl, focs))
+            r = [] if radii is not None else None
+            planes.append(_focus_planes(opt_model, fld, wvl, focs, radii=r))
+            if radii is not None:
+                radii.append(r)
             kw = dict(kwargs)
             grids.append(_focus_grid(opt_model, fld, xy, num_rays, kw))
             eng, f, wi, opts = _launch_setup(opt_model, fld, wvl, kw, abi.OUT_FAN)
             fs.append(f)
             wis.append(wi)
             opts_list.append(opts)
+    return eng, fs, wis, grids, opts_list, planes
+
+
+def through_focus_map(opt_model, focs, flds=None, wvls=None, num_rays=21, xy=None, field_wts=None,
+                      spectral_wts=None, ref_wvl=None, rows=False, **kwargs):
+    """Through-focus scans of every field at every wavelength in ONE device call
+    (rox_trace_through_focus_grids): item (f, w) is through_focus(opt_model, flds[f], wvls[w],
+    focs, num_rays, xy, ...) -- the same planes, grid and statistics, bit for bit -- and the
+    per-field polychromatic statistics, field curvature and white-light best focus follow on the
+    host (:class:`ThroughFocusMap`).  Defaults: the fields of osp['fov'] with their ``wt``, the
+    wavelengths of osp['wvls'] with its spectral_wts, ref_wvl = its central_wvl (a
+    workloads.TableModel has no osp: pass them).  A focus whose reference sphere the device
+    cannot express raises UnsupportedModelError for the whole call."""
+    from .engine import grid_rays
+    focs = _check_focs(focs, 'through_focus_map')
+    flds, wvls, field_wts, spectral_wts, ref_wvl = _map_spec(opt_model, flds, wvls, field_wts, spectral_wts,
+                                                             ref_wvl, 'through_focus_map')
+    F, W, K = len(flds), len(wvls), len(focs)
+    eng, fs, wis, grids, opts_list, planes = _map_items(opt_model, flds, wvls, focs, xy, num_rays, kwargs)
     out = eng.trace_pupil_grids_focus(fs, wis, grids, opts_list, planes, want_rows=rows)
     stats, dev_rows = out if rows else (out, None)
     stats = np.stack([_stats_in_waves(stats[i], opt_model, wvls[i % W]) for i in range(F * W)])
@@ -969,6 +992,193 @@ def through_focus_map(opt_model, focs, flds=None, wvls=None, num_rays=21, xy=Non
         status = np.asarray(status)[:, :R].reshape(F, W, R)
     return ThroughFocusMap(focs, wvls, field_wts, spectral_wts, ref_wvl, stats.reshape(F, W, K),
                            image_pts.reshape(F, W, K, 2), host_rows, status)
+
+
+# ---- MTF through focus ----------------------------------------------------------
+# the PSF stack through_focus_mtf holds at once: larger maps run rox_focus_psf / rox_focus_mtf
+# over consecutive groups of items (the results do not depend on the grouping)
+MTF_PSF_CHUNK_BYTES = 512 << 20
+
+
+def _check_freqs(freqs, what):
+    nu = np.asarray(freqs, dtype=np.float64).reshape(-1)
+    if not 1 <= nu.size <= abi.MAX_MTF_FREQS:
+        raise ValueError(f'{what}: 1 to {abi.MAX_MTF_FREQS} frequencies, got {nu.size}')
+    if not (np.isfinite(nu).all() and (nu >= 0).all()):
+        raise ValueError(f'{what}: frequencies must be finite and >= 0, got {nu}')
+    return nu
+
+
+def poly_otf_merge(otf, image_pts, spectral_wts, ref_index, freqs):
+    """the polychromatic line OTFs [K, 2, Q] of one field from its per-wavelength OTFs.
+
+    otf         [W, K, 2, Q] complex: each wavelength's line OTFs along image x and y, phase
+                about that wavelength's own image point
+    image_pts   [W, K, 2] each plane's image point
+    spectral_wts  [W] weights s_w;  ref_index: the wavelength whose image point is the origin
+
+    poly_otf(nu) = sum_w s_w exp(-2 pi i nu D_w) OTF_w(nu) / sum_w s_w, D_w the component of
+    image_pt_w - image_pt_ref along the direction, so lateral colour counts.  Entries whose OTF is
+    NaN are skipped and the remaining weights renormalised; none left -> NaN.  One wavelength
+    gives its own OTF exactly (its weight is 1 and its phase factor exp(0) = 1)."""
+    otf = np.asarray(otf, dtype=np.complex128)
+    W, K, _two, Q = otf.shape
+    ip = np.asarray(image_pts, dtype=np.float64).reshape(W, K, 2)
+    nu = np.asarray(freqs, dtype=np.float64).reshape(Q)
+    delta = ip - ip[ref_index][None]                                    # [W, K, 2]
+    shifted = np.exp(-2j * np.pi * delta[..., None] * nu) * otf          # [W, K, 2, Q]
+    ok = ~np.isnan(otf)
+    s = np.where(ok, np.asarray(spectral_wts, dtype=np.float64).reshape(W, 1, 1, 1), 0.0)
+    total = s.sum(axis=0)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        wt = s / total
+    out = np.where(ok, wt * shifted, 0.0).sum(axis=0)
+    return np.where(total > 0, out, np.nan + 0j)
+
+
+class ThroughFocusMTF:
+    """what :func:`through_focus_mtf` returns.
+
+    focs, freqs, wvls, field_wts, spectral_wts, ref_wvl   as used
+    otf         [F, W, K, 2, Q] complex: the line OTFs of each PSF along image x (direction 0)
+                and y (1) -- rox_focus_mtf: the DTFT of the PSF's projection, phase in image
+                coordinates about the plane's image point; NaN above a plane's Nyquist
+                frequency 1 / (2 pitch) and on planes no ray reached
+    mtf         [F, W, K, 2, Q] abs(otf)
+    pitch       [F, W, K] each PSF's pixel pitch (calc_psf_scaling's delta_xp at that focus)
+    image_pts   [F, W, K, 2] each plane's image point
+    strehl      [F, W, K] each plane's Strehl ratio (rox_focus_psf)
+    poly_otf / poly_mtf [F, K, 2, Q]: :func:`poly_otf_merge` of each field's wavelengths
+    best_focus  [F, 2, Q] (+ ``_kind``): :func:`best_focus` of -poly_mtf per field, direction
+                and frequency
+    best_focus_all [Q] (+ ``_kind``): the same of the field-weighted mean over both directions
+    meridional  [F] True for a field whose image points stay in the y-z plane (x == 0 at every
+                wavelength and focus): there y is tangential and x sagittal
+    tangential / sagittal [F, K, Q]: poly_mtf along y / x for meridional fields, NaN rows for
+                the others (their tangential direction is neither x nor y)
+    psf         [F, W, K, maxdim, maxdim] with ``psf=True`` (a torch tensor in HBM with
+                ``on_device=True``), else None"""
+
+    def __init__(self, focs, freqs, wvls, field_wts, spectral_wts, ref_wvl, otf, pitch, image_pts, strehl,
+                 psf=None):
+        self.focs = np.asarray(focs, dtype=np.float64)
+        self.freqs = np.asarray(freqs, dtype=np.float64)
+        self.wvls = list(wvls)
+        self.field_wts = np.asarray(field_wts, dtype=np.float64)
+        self.spectral_wts = np.asarray(spectral_wts, dtype=np.float64)
+        self.ref_wvl = ref_wvl
+        self.otf = otf
+        self.mtf = np.abs(otf)
+        self.pitch = pitch
+        self.image_pts = image_pts
+        self.strehl = strehl
+        self.psf = psf
+        F, _W, K, _two, Q = otf.shape
+        ref = self.wvls.index(ref_wvl)
+        self.poly_otf = np.stack([poly_otf_merge(otf[f], image_pts[f], self.spectral_wts, ref, self.freqs)
+                                  for f in range(F)])
+        self.poly_mtf = np.abs(self.poly_otf)
+        self.best_focus = np.empty((F, 2, Q))
+        self.best_focus_kind = np.empty((F, 2, Q), dtype=object)
+        for f in range(F):
+            for d in range(2):
+                for q in range(Q):
+                    self.best_focus[f, d, q], self.best_focus_kind[f, d, q] = best_focus(
+                        self.focs, -self.poly_mtf[f, :, d, q])
+        mean = self.poly_mtf.mean(axis=2)                                   # [F, K, Q] both directions
+        wt = self.field_wts[:, None, None]
+        curve = (wt * mean).sum(axis=0) / self.field_wts.sum()              # [K, Q]
+        res = [best_focus(self.focs, -curve[:, q]) for q in range(Q)]
+        self.best_focus_all = np.array([r[0] for r in res])
+        self.best_focus_all_kind = np.array([r[1] for r in res], dtype=object)
+        self.meridional = np.all(np.asarray(image_pts)[..., 0] == 0.0, axis=(1, 2))
+
+    def _view(self, d):
+        out = np.full(self.poly_mtf.shape[:2] + self.poly_mtf.shape[3:], np.nan)
+        out[self.meridional] = self.poly_mtf[self.meridional, :, d, :]
+        return out
+
+    @property
+    def tangential(self):
+        """[F, K, Q] the polychromatic MTF along y of the meridional fields (NaN rows elsewhere)"""
+        return self._view(1)
+
+    @property
+    def sagittal(self):
+        """[F, K, Q] the polychromatic MTF along x of the meridional fields (NaN rows elsewhere)"""
+        return self._view(0)
+
+
+def through_focus_mtf(opt_model, focs, freqs, flds=None, wvls=None, num_rays=32, maxdim=128, field_wts=None,
+                      spectral_wts=None, ref_wvl=None, psf=False, on_device=False, pitch=None, **kwargs):
+    """The MTF through focus, along image x and y, of every field at every wavelength, and its
+    polychromatic merge per field, on the device: one rox_trace_through_focus_grids launch traces
+    each item's square pupil grid (as :func:`through_focus_psf`) and evaluates it at every focus,
+    rox_focus_psf turns the rows into PSFs (each calc_psf of that focus's focus_wavefront grid),
+    and rox_focus_mtf takes the line OTFs of every PSF at ``freqs`` (cycles per system unit) --
+    the PSFs stay in HBM.  The merge over wavelengths follows on the host
+    (:class:`ThroughFocusMTF`).  Fields, wavelengths and weights default as in
+    :func:`through_focus_map`.  Each PSF's pitch is calc_psf_scaling's delta_xp at its focus; a
+    model without paraxial data (a workloads.TableModel) needs ``pitch`` [F, W, K].  ``maxdim``
+    must be at least 2 ``num_rays``: below that the pupil autocorrelation wraps and the MTF is
+    aliased.  ``psf=True`` keeps the PSFs (in HBM with ``on_device=True``)."""
+    from .engine import grid_rays
+    what = 'through_focus_mtf'
+    focs = _check_focs(focs, what)
+    num_rays, maxdim = int(num_rays), int(maxdim)
+    if num_rays < 2 or num_rays % 2:
+        raise ValueError(f'{what}: num_rays must be even and >= 2, got {num_rays}')
+    if maxdim < 2 * num_rays:
+        raise ValueError(f'{what}: maxdim {maxdim} < 2 num_rays = {2 * num_rays}: the pupil autocorrelation '
+                         f'would wrap (an aliased MTF)')
+    if not _psf_block_fits(num_rays, maxdim):
+        raise ValueError(f'{what}: the {num_rays} x {num_rays} grid does not fit in maxdim {maxdim}')
+    nu = _check_freqs(freqs, what)
+    flds, wvls, field_wts, spectral_wts, ref_wvl = _map_spec(opt_model, flds, wvls, field_wts, spectral_wts,
+                                                             ref_wvl, what)
+    F, W, K = len(flds), len(wvls), len(focs)
+    if pitch is not None:
+        pitch = np.array(np.broadcast_to(np.asarray(pitch, dtype=np.float64), (F, W, K)))
+        if not (np.isfinite(pitch).all() and (pitch > 0).all()):
+            raise ValueError(f'{what}: pitch must be finite and > 0')
+    radii = []
+    eng, fs, wis, grids, opts_list, planes = _map_items(opt_model, flds, wvls, focs, None, num_rays, kwargs,
+                                                        radii=radii)
+    assert grid_rays(grids[0]) == num_rays * num_rays
+    if pitch is None:
+        scal = [[psf_scaling(opt_model, wvls[i % W], num_rays, maxdim, r) for r in radii[i]] for i in range(F * W)]
+        if any(s is None for ss in scal for s in ss):
+            raise ValueError(f'{what}: the model has no paraxial data for calc_psf_scaling: pass pitch [F, W, K]')
+        pitch = np.array([[s[1] for s in ss] for ss in scal], dtype=np.float64).reshape(F, W, K)
+    _none, dev_rows = eng.trace_pupil_grids_focus(fs, wis, grids, opts_list, planes, want_rows=True,
+                                                  want_stats=False)
+    scale = np.array([1 / opt_model.nm_to_sys_units(wvls[i % W]) for i in range(F * W)])
+    flat_pitch = pitch.reshape(F * W, K)
+    per_item = K * maxdim * maxdim * 8
+    step = max(1, MTF_PSF_CHUNK_BYTES // per_item)
+    from .engine import FocusRows
+    otf, strehl, psfs = [], [], []
+    for i0 in range(0, F * W, step):
+        i1 = min(F * W, i0 + step)
+        part = FocusRows(dev_rows.rows[i0:i1], dev_rows.status[i0:i1])
+        dev_psf, psf_stats = eng.focus_psf(part, num_rays, maxdim, scale[i0:i1], want_psf=True)
+        otf.append(eng.focus_mtf(dev_psf, flat_pitch[i0:i1], nu))
+        strehl.append(psf_stats['strehl'])
+        if psf:
+            psfs.append(dev_psf if on_device else dev_psf.cpu().numpy())
+        del dev_psf
+    otf = np.concatenate(otf).reshape(F, W, K, 2, nu.size)
+    strehl = np.concatenate(strehl).reshape(F, W, K)
+    image_pts = np.array([[(p.image_pt[0], p.image_pt[1]) for p in ps] for ps in planes]).reshape(F, W, K, 2)
+    out_psf = None
+    if psf:
+        if on_device:
+            import torch
+            out_psf = torch.cat(psfs).reshape(F, W, K, maxdim, maxdim)
+        else:
+            out_psf = np.concatenate(psfs).reshape(F, W, K, maxdim, maxdim)
+    return ThroughFocusMTF(focs, nu, wvls, field_wts, spectral_wts, ref_wvl, otf, pitch, image_pts, strehl,
+                           out_psf)
 
 
 # ---- point spread function ------------------------------------------------------

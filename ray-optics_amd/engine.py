@@ -961,6 +961,35 @@ class TraceEngine:
                                           stats.ctypes.data, self._stream()), 'rox_focus_psf')
         return psf, stats
 
+    @_in_flight
+    def focus_mtf(self, psf, pitch, freqs, on_device=False):
+        """rox_focus_mtf over the PSFs focus_psf returns (``psf``: float64 [n_items, K, M, M] in
+        HBM): the line OTF of every plane along image x and y at the frequencies ``freqs``
+        (cycles per system unit), ``pitch`` (broadcast to [n_items, K]) being each plane's pixel
+        pitch.  Returns a complex128 array [n_items, K, 2, Q] (direction 0 = x, 1 = y), or with
+        ``on_device`` a complex128 tensor of that shape in HBM.  NaN above a plane's Nyquist
+        frequency and on planes no ray reached."""
+        t = self.torch
+        if psf.dim() != 4 or psf.dtype != t.float64 or not psf.is_contiguous() or \
+                int(psf.shape[2]) != int(psf.shape[3]):
+            raise EngineError('focus_mtf reads the contiguous float64 [n_items][K][M][M] PSFs of focus_psf')
+        n_items, K, M = int(psf.shape[0]), int(psf.shape[1]), int(psf.shape[2])
+        p = np.ascontiguousarray(np.broadcast_to(np.asarray(pitch, dtype=np.float64), (n_items, K)))
+        f = np.ascontiguousarray(np.asarray(freqs, dtype=np.float64).reshape(-1))
+        Q = int(f.size)
+        if on_device:
+            out = t.empty((n_items, K, 2, Q, 2), dtype=t.float64, device=self.device)
+            ptr = out.data_ptr()
+        else:
+            out = np.empty((n_items, K, 2, Q, 2), dtype=np.float64)
+            ptr = out.ctypes.data
+        with t.cuda.device(self.device):
+            _check(self.lib.rox_focus_mtf(n_items, K, psf.data_ptr(), M, p.ctypes.data, Q, f.ctypes.data,
+                                          ptr, self._stream()), 'rox_focus_mtf')
+        if on_device:
+            return t.view_as_complex(out)
+        return out.view(np.complex128)[..., 0]
+
     def _spot_stats(self, seg_ptr, ld, status_ptr, n_hits_ptr, n, layout, x_edges, y_edges):
         summ = abi.SpotSummary()
         hist = None
