@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json's metric on BASELINE.json's configuration.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 ``--gpus N`` with N > 1 needs one process per GPU: when this script is started
 plainly (no WORLD_SIZE in the environment) it re-executes itself under
@@ -17,6 +17,11 @@ entry of the C ABI.  One "step" = one such grid.  Inputs are resident in HBM
 
 metric        ray-surface intersections per second, counting the intersections
               actually performed (a ray blocked at surface s contributes s, not K)
+
+A plain run does only what that figure needs: it sets up, warms up, times the K steps, writes
+--dump-outputs and prints the line (`full`: false).  Everything below is measured by a run
+with --full, after the same timed steps (the --no-* switches leave parts of it out):
+
 cold_ms_per_step  the same K launches issued right after an idle second, before any
               warm-up (the GPU's clocks ramp over the first ~100 launches)
 roofline      HBM-bound kernel: algorithmic bytes = what one launch must write
@@ -41,7 +46,7 @@ cpu_baseline  kind "reference": the reference ITSELF (staged as sourceless byte 
               launch's (parity_vs_timed_launch).  Beside it the plain-C port
               (oracle/rox_oracle.c), one thread and all cores.  Where no reference is staged:
               kind "port" with the build container's reference figure bridged by a ratio
-strong_scaling  every run, any N: BASELINE configs[4]'s shape -- 9 fields x 5
+strong_scaling  any N: BASELINE configs[4]'s shape -- 9 fields x 5
               wavelengths x 2048^2 pupil grids of the 44-interface lithography
               lens (188.7 M rays) cut into pupil-row blocks over the ranks, packed
               hits (no padding for blocked rays), brought to rank 0's host memory
@@ -63,9 +68,10 @@ path north_star describes: BASELINE configs[4]'s spot problem (188.7 M rays) cut
 over the ranks, packed hits gathered to rank 0 over RCCL and delivered to its host memory,
 pipelined per piece, K passes between two fences -- the exchange is INSIDE the timed region;
 `predicted_ms` holds DESIGN section 7's arithmetic per N.  The collective-free figure (one
-FULL grid per rank, weak scaling) is kept under `weak_full`.  `strong_scaling` carries every
-exchange variant incl. the N = 1 line's own grid cut by rows (`c2_sharded`).  A rank hanging
-in an exchange ends the run with "ok": false and exit status 3 (the line is still printed).
+FULL grid per rank, weak scaling) is kept under `weak_full`.  With --full, `strong_scaling`
+carries every exchange variant incl. the N = 1 line's own grid cut by rows (`c2_sharded`).  A
+rank hanging in an exchange ends the run with "ok": false and exit status 3 (the line is still
+printed).
 """
 import argparse
 import atexit
@@ -93,6 +99,10 @@ def parse():
     ap.add_argument('--steps', type=int, default=400)
     ap.add_argument('--warmup', type=int, default=20)
     ap.add_argument('--num', type=int, default=1024, help='pupil grid is num x num')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure everything beyond the headline: the cold launches, rooflines, the '
+                         'spot diagram, the PSF, every BASELINE configuration, the strong-scaling '
+                         'variants and the CPU baseline (the --no-* switches below trim a --full run)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--force-dist', action='store_true',
                     help='take the multi-rank code path (process group, collectives, sharded '
@@ -102,7 +112,8 @@ def parse():
     ap.add_argument('--ref-sample-rows', type=int, default=64,
                     help='pupil rows of the timed grid the reference itself (oracle/_ref) re-traces: '
                          '64 x 1024 = 65 536 rays, ~15 s of its per-ray Python loop')
-    ap.add_argument('--no-strong', action='store_true', help='skip the strong-scaling leg')
+    ap.add_argument('--no-strong', action='store_true',
+                    help='skip the strong-scaling legs (N > 1: the strong-scaled headline too)')
     ap.add_argument('--strong-timeout', type=float, default=300.0,
                     help='multi-rank runs: seconds after which the strong-scaling leg is given up')
     ap.add_argument('--preflight-timeout', type=float, default=20.0,
@@ -250,17 +261,20 @@ def main():
                 time.sleep(2.0)
             os._exit(3)
 
-    # cold: the K launches as a caller meets them after an idle second (one launch first, so
-    # that module load and allocation are not in it)
+    # one launch first, so that module load and allocation are in neither the warm-up's clock nor
+    # the cold figure
     step()
     torch.cuda.synchronize()
-    time.sleep(1.0)
-    fence()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
-    fence()
-    cold_dt = time.perf_counter() - t0
+    cold_dt = None
+    if args.full:
+        # cold: the K launches as a caller meets them after an idle second
+        time.sleep(1.0)
+        fence()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            step()
+        fence()
+        cold_dt = time.perf_counter() - t0
 
     # the GPU's clocks need tens of milliseconds of continuous work to settle (a cold
     # start reads 10-30 % slow, tools/sustained_probe.py): untimed launches first, at
@@ -285,9 +299,10 @@ def main():
         # `out` is traced into again by the legs below: what the last timed step left, now
         dump_outputs(torch, args.dump_outputs, out, N, abi)
     if multi:
-        t = torch.tensor([dt, cold_dt], dtype=torch.float64, device=eng.device)
+        t = torch.tensor([dt, cold_dt or 0.0], dtype=torch.float64, device=eng.device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dt, cold_dt = t[0].item(), t[1].item()
+        dt = t[0].item()
+        cold_dt = t[1].item() if args.full else None
 
     # work actually done by this rank's grid
     inters, alg_bytes = work_of(out.status, out.fail_surf, N, abi, full=True)
@@ -296,125 +311,126 @@ def main():
         dist.all_reduce(tot, op=dist.ReduceOp.SUM)
     inters_all, rays_all = tot[0].item(), tot[1].item()
 
-    # dominant kernel: mean launch duration from HIP events on the launch stream
-    kern_ms = eng.time_pupil_grid_sustained(fld, grid, wi, opts, out, max(min(args.steps, 50), 10))
-    # HITS kernel (spot diagrams, OPD, refocus): mean launch duration
-    o_hits = make_opts(flags=flags, out_mode=abi.OUT_HITS, first_surf=1, last_surf=N - 2,
-                       foc=wl.foc, image_pt=wl.image_pts[fi])
-    hits = DeviceResult(torch, eng.device, 0, R, abi.OUT_HITS, want_pupil=False, nan_fill=False)
-    hits_kern_ms = eng.time_pupil_grid_sustained(fld, grid, wi, o_hits, hits,
-                                                 max(min(args.steps, 50), 10))
-    # ... and its tolerance-mode twin (ROX_FAST_FP64: <= 1e-10 from the reference instead of its
-    # bits, tests/test_gpu_fast.py), with the deviation of this very launch from the exact one
-    o_fast = make_opts(flags=flags | abi.FAST_FP64, out_mode=abi.OUT_HITS, first_surf=1, last_surf=N - 2,
-                       foc=wl.foc, image_pt=wl.image_pts[fi])
-    hits_f = DeviceResult(torch, eng.device, 0, R, abi.OUT_HITS, want_pupil=False, nan_fill=False)
-    hits_fast_ms = eng.time_pupil_grid_sustained(fld, grid, wi, o_fast, hits_f,
-                                                 max(min(args.steps, 50), 10))
-    fast_check = fast_vs_exact(torch, abi, hits, hits_f)
-    del hits, hits_f
+    # everything else this run can measure (--full): kernel rooflines, the spot diagram at the
+    # product function, the PSF, every BASELINE configuration
+    dev_sample = None
+    if args.full:
+        # dominant kernel: mean launch duration from HIP events on the launch stream
+        kern_ms = eng.time_pupil_grid_sustained(fld, grid, wi, opts, out, max(min(args.steps, 50), 10))
+        # HITS kernel (spot diagrams, OPD, refocus): mean launch duration
+        o_hits = make_opts(flags=flags, out_mode=abi.OUT_HITS, first_surf=1, last_surf=N - 2,
+                           foc=wl.foc, image_pt=wl.image_pts[fi])
+        hits = DeviceResult(torch, eng.device, 0, R, abi.OUT_HITS, want_pupil=False, nan_fill=False)
+        hits_kern_ms = eng.time_pupil_grid_sustained(fld, grid, wi, o_hits, hits,
+                                                     max(min(args.steps, 50), 10))
+        # ... and its tolerance-mode twin (ROX_FAST_FP64: <= 1e-10 from the reference instead of its
+        # bits, tests/test_gpu_fast.py), with the deviation of this very launch from the exact one
+        o_fast = make_opts(flags=flags | abi.FAST_FP64, out_mode=abi.OUT_HITS, first_surf=1, last_surf=N - 2,
+                           foc=wl.foc, image_pt=wl.image_pts[fi])
+        hits_f = DeviceResult(torch, eng.device, 0, R, abi.OUT_HITS, want_pupil=False, nan_fill=False)
+        hits_fast_ms = eng.time_pupil_grid_sustained(fld, grid, wi, o_fast, hits_f,
+                                                     max(min(args.steps, 50), 10))
+        fast_check = fast_vs_exact(torch, abi, hits, hits_f)
+        del hits, hits_f
 
-    # spot-diagram wall-clock at the product boundary: the function the reference's
-    # SpotDiagramFigure reaches through SequentialModel.trace_grid, on a table-backed
-    # model (the extraction of table / field constants from a live reference model is
-    # what the stand-in skips; the reference is not installed on the GPU box)
-    from rayoptics_amd import trace as rox_trace
-    model = workloads.TableModel(wl)
-    mfld = model.fields[fi]
-    grid_rng = [np.array([-1., -1.]), np.array([1., 1.]), num]
-    wvl_nm = wl.table.wvls[wi]
-    for _ in range(60):         # settle clocks / pinned pool
-        xy = rox_trace.trace_grid_spot(model, grid_rng, mfld, wvl_nm, wl.foc, wl.image_pts[fi])
-    spot_ms = []
-    for _ in range(41):
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        xy = rox_trace.trace_grid_spot(model, grid_rng, mfld, wvl_nm, wl.foc, wl.image_pts[fi])
-        spot_ms.append((time.perf_counter() - t1) * 1e3)
-    n_through = int(xy.shape[0])
-    # ... and behind the opt-in tolerance-mode kernels (session.set_tolerance_mode: ROX_FAST_FP64 on
-    # every reduced-output launch of the drop-ins; <= 1e-10 from the reference, not its bits)
-    from rayoptics_amd import session as rox_session
-    spot_tol_ms, n_through_tol = [], None
-    rox_session.set_tolerance_mode(True)
-    try:
-        for _ in range(20):
-            xy_t = rox_trace.trace_grid_spot(model, grid_rng, mfld, wvl_nm, wl.foc, wl.image_pts[fi])
+        # spot-diagram wall-clock at the product boundary: the function the reference's
+        # SpotDiagramFigure reaches through SequentialModel.trace_grid, on a table-backed
+        # model (the extraction of table / field constants from a live reference model is
+        # what the stand-in skips; the reference is not installed on the GPU box)
+        from rayoptics_amd import trace as rox_trace
+        model = workloads.TableModel(wl)
+        mfld = model.fields[fi]
+        grid_rng = [np.array([-1., -1.]), np.array([1., 1.]), num]
+        wvl_nm = wl.table.wvls[wi]
+        for _ in range(60):         # settle clocks / pinned pool
+            xy = rox_trace.trace_grid_spot(model, grid_rng, mfld, wvl_nm, wl.foc, wl.image_pts[fi])
+        spot_ms = []
         for _ in range(41):
             torch.cuda.synchronize()
             t1 = time.perf_counter()
-            xy_t = rox_trace.trace_grid_spot(model, grid_rng, mfld, wvl_nm, wl.foc, wl.image_pts[fi])
-            spot_tol_ms.append((time.perf_counter() - t1) * 1e3)
-        n_through_tol = int(xy_t.shape[0])
-        spot_tol_dev = (float(np.max(np.abs(xy_t - xy))) if xy_t.shape == xy.shape else None)
-    finally:
-        rox_session.set_tolerance_mode(False)
-    # what an interactive caller meets: the same call after the GPU has idled for a second (the
-    # clocks have dropped), at the 1M-ray grid and at the 64 x 64 grid figures default to
-    cold_spot = {}
-    for cnum in (num, 64):
-        cgrid = [np.array([-1., -1.]), np.array([1., 1.]), cnum]
-        rox_trace.trace_grid_spot(model, cgrid, mfld, wvl_nm, wl.foc, wl.image_pts[fi])
-        ts = []
-        for _ in range(3):
+            xy = rox_trace.trace_grid_spot(model, grid_rng, mfld, wvl_nm, wl.foc, wl.image_pts[fi])
+            spot_ms.append((time.perf_counter() - t1) * 1e3)
+        n_through = int(xy.shape[0])
+        # ... and behind the opt-in tolerance-mode kernels (session.set_tolerance_mode: ROX_FAST_FP64 on
+        # every reduced-output launch of the drop-ins; <= 1e-10 from the reference, not its bits)
+        from rayoptics_amd import session as rox_session
+        spot_tol_ms, n_through_tol = [], None
+        rox_session.set_tolerance_mode(True)
+        try:
+            for _ in range(20):
+                xy_t = rox_trace.trace_grid_spot(model, grid_rng, mfld, wvl_nm, wl.foc, wl.image_pts[fi])
+            for _ in range(41):
+                torch.cuda.synchronize()
+                t1 = time.perf_counter()
+                xy_t = rox_trace.trace_grid_spot(model, grid_rng, mfld, wvl_nm, wl.foc, wl.image_pts[fi])
+                spot_tol_ms.append((time.perf_counter() - t1) * 1e3)
+            n_through_tol = int(xy_t.shape[0])
+            spot_tol_dev = (float(np.max(np.abs(xy_t - xy))) if xy_t.shape == xy.shape else None)
+        finally:
+            rox_session.set_tolerance_mode(False)
+        # what an interactive caller meets: the same call after the GPU has idled for a second (the
+        # clocks have dropped), at the 1M-ray grid and at the 64 x 64 grid figures default to
+        cold_spot = {}
+        for cnum in (num, 64):
+            cgrid = [np.array([-1., -1.]), np.array([1., 1.]), cnum]
+            rox_trace.trace_grid_spot(model, cgrid, mfld, wvl_nm, wl.foc, wl.image_pts[fi])
+            ts = []
+            for _ in range(3):
+                torch.cuda.synchronize()
+                time.sleep(1.0)
+                t1 = time.perf_counter()
+                rox_trace.trace_grid_spot(model, cgrid, mfld, wvl_nm, wl.foc, wl.image_pts[fi])
+                ts.append((time.perf_counter() - t1) * 1e3)
+            warm = []
+            for _ in range(21):
+                t1 = time.perf_counter()
+                rox_trace.trace_grid_spot(model, cgrid, mfld, wvl_nm, wl.foc, wl.image_pts[fi])
+                warm.append((time.perf_counter() - t1) * 1e3)
+            cold_spot[f'{cnum}x{cnum}'] = {'first_call_after_1s_idle_ms': float(np.median(ts)),
+                                           'back_to_back_ms': float(np.median(warm))}
+        # the rows of the timed launch's packets the CPU legs re-trace (the reference itself, when
+        # it is staged on this host, is compared with them ray by ray)
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            rr = min(args.ref_sample_rows, num)
+            i0r = (num - rr) // 2
+            sl = slice(i0r * num, (i0r + rr) * num)
+            step()
             torch.cuda.synchronize()
-            time.sleep(1.0)
-            t1 = time.perf_counter()
-            rox_trace.trace_grid_spot(model, cgrid, mfld, wvl_nm, wl.foc, wl.image_pts[fi])
-            ts.append((time.perf_counter() - t1) * 1e3)
-        warm = []
-        for _ in range(21):
-            t1 = time.perf_counter()
-            rox_trace.trace_grid_spot(model, cgrid, mfld, wvl_nm, wl.foc, wl.image_pts[fi])
-            warm.append((time.perf_counter() - t1) * 1e3)
-        cold_spot[f'{cnum}x{cnum}'] = {'first_call_after_1s_idle_ms': float(np.median(ts)),
-                                       'back_to_back_ms': float(np.median(warm))}
-    # the rows of the timed launch's packets the CPU legs re-trace (the reference itself, when
-    # it is staged on this host, is compared with them ray by ray)
-    dev_sample = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        rr = min(args.ref_sample_rows, num)
-        i0r = (num - rr) // 2
-        sl = slice(i0r * num, (i0r + rr) * num)
-        step()
-        torch.cuda.synchronize()
-        dev_sample = {'row0': i0r, 'rows': rr,
-                      'seg': out.seg[:, :, sl].cpu().numpy(), 'op': out.op[sl].cpu().numpy(),
-                      'status': out.status[sl].cpu().numpy(),
-                      'fail_surf': out.fail_surf[sl].cpu().numpy(),
-                      'pupil': out.pupil[:, sl].cpu().numpy()}
-    del xy, out
+            dev_sample = {'row0': i0r, 'rows': rr,
+                          'seg': out.seg[:, :, sl].cpu().numpy(), 'op': out.op[sl].cpu().numpy(),
+                          'status': out.status[sl].cpu().numpy(),
+                          'fail_surf': out.fail_surf[sl].cpu().numpy(),
+                          'pupil': out.pupil[:, sl].cpu().numpy()}
+        del xy
 
-    # the PSF of an OPD grid (analyses.calc_psf): the GEMM-shaped neighbour of the path,
-    # on the fp64 matrix cores; device-resident, mean of back-to-back calls
-    psf = None
-    if rank == 0:
-        try:
-            psf = psf_leg(torch)
-        except Exception as e:
-            psf = {'error': repr(e)}
+        # the PSF of an OPD grid (analyses.calc_psf): the GEMM-shaped neighbour of the path,
+        # on the fp64 matrix cores; device-resident, mean of back-to-back calls
+        psf = None
+        if rank == 0:
+            try:
+                psf = psf_leg(torch)
+            except Exception as e:
+                psf = {'error': repr(e)}
 
-    # every BASELINE configuration at its own shape (rank 0's GPU; the others wait at the
-    # next fence)
-    configs = None
-    if rank == 0 and not args.no_configs:
-        try:
-            configs = configs_leg(torch, abi, workloads)
-        except Exception as e:
-            configs = {'error': repr(e)}
+        # every BASELINE configuration at its own shape (rank 0's GPU; the others wait at the
+        # next fence)
+        configs = None
+        if rank == 0 and not args.no_configs:
+            try:
+                configs = configs_leg(torch, abi, workloads)
+            except Exception as e:
+                configs = {'error': repr(e)}
+    del out
     torch.cuda.empty_cache()
 
     line = None
     if rank == 0:
-        traffic, traffic_source = committed_traffic(num, wl.name)
-        achieved = alg_bytes / (kern_ms * 1e-3) / 1e9
         line = {
             'metric': 'ray-surface intersections/sec',
             'value': inters_all / dt * args.steps,
             'unit': 'ray-surface intersections/s',
             'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'warmup_steps_run': n_w,
             'ms_per_step': dt / args.steps * 1e3,
-            'cold_ms_per_step': cold_dt / args.steps * 1e3,
             'fence_ms': fence_ms,
             'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
             'dtype': 'f64', 'data': 'synthetic',
@@ -429,43 +445,50 @@ def main():
                        'out_mode': 'FULL', 'field_index': fi, 'wvl_nm': wl.table.wvls[wi],
                        'sharding': 'one (field,wvl) grid per rank' if world > 1 else 'single GPU'},
             'rays_per_s': rays_all / dt * args.steps,
-            'roofline': {'bound': 'hbm', 'achieved': achieved, 'peak': 8000.0, 'unit': 'GB/s',
-                         'frac': achieved / 8000.0, 'traffic': traffic,
-                         'traffic_committed_from': traffic_source,
-                         'kernel': 'trace_kernel<FULL,PUPIL>', 'kernel_ms': kern_ms,
-                         'algorithmic_bytes_per_launch': alg_bytes,
-                         'frac_of_measured_copy_peak_6290': achieved / 6290.0},
-            'roofline_hits': roofline_hits(inters, R, hits_kern_ms),
-            'roofline_hits_fast': dict(roofline_hits(inters, R, hits_fast_ms, workload='dblgauss_c2_fast'),
-                                       kernel='trace_kernel<HITS,PUPIL,F_FAST> (ROX_FAST_FP64: <= 1e-10 '
-                                              'from the reference, not bit-exact; opt-in)',
-                                       vs_exact_same_launch=fast_check,
-                                       speedup_over_exact=hits_kern_ms / hits_fast_ms),
-            'spot_diagram': {'wallclock_ms': float(np.median(spot_ms)),
-                             'wallclock_min_ms': float(np.min(spot_ms)), 'rays': R,
-                             'rays_through': n_through, 'kernel_hits_ms': hits_kern_ms,
-                             'tolerance_mode': {'wallclock_ms': float(np.median(spot_tol_ms)),
-                                                'wallclock_min_ms': float(np.min(spot_tol_ms)),
-                                                'rays_through': n_through_tol,
-                                                'max_abs_deviation_from_exact': spot_tol_dev,
-                                                'what': 'the same call after session.set_tolerance_mode(True): '
-                                                        'opt-in, never the figure above'},
-                             'pcie_floor_ms': n_through * 16 / 54.7e9 * 1e3,
-                             'after_idle': cold_spot,
-                             'what': 'rayoptics_amd.trace.trace_grid_spot(model, grid_rng, fld, wvl, '
-                                     'foc, image_pt): Python call -> host (R_ok, 2) float64 array '
-                                     '(survivors packed in ray order by the trace launch, written '
-                                     'straight into pinned host memory; 13 MB over PCIe at ~55 GB/s '
-                                     'is the floor)'},
-            'configs': configs,
-            'configs_batch_items_uploaded_every_pass': os.environ.get('ROX_BATCH_ALWAYS_UPLOAD') == '1',
-            'configs_batch_items_in_kernel_argument_up_to': 16,
-            'psf': psf,
-            'cpu_baseline': None,
-            'strong_scaling': None,
+            'full': args.full,
             'library': library_id(),
             'ok': True,
         }
+        if args.full:
+            traffic, traffic_source = committed_traffic(num, wl.name)
+            achieved = alg_bytes / (kern_ms * 1e-3) / 1e9
+            line.update({
+                'cold_ms_per_step': cold_dt / args.steps * 1e3,
+                'roofline': {'bound': 'hbm', 'achieved': achieved, 'peak': 8000.0, 'unit': 'GB/s',
+                             'frac': achieved / 8000.0, 'traffic': traffic,
+                             'traffic_committed_from': traffic_source,
+                             'kernel': 'trace_kernel<FULL,PUPIL>', 'kernel_ms': kern_ms,
+                             'algorithmic_bytes_per_launch': alg_bytes,
+                             'frac_of_measured_copy_peak_6290': achieved / 6290.0},
+                'roofline_hits': roofline_hits(inters, R, hits_kern_ms),
+                'roofline_hits_fast': dict(roofline_hits(inters, R, hits_fast_ms, workload='dblgauss_c2_fast'),
+                                           kernel='trace_kernel<HITS,PUPIL,F_FAST> (ROX_FAST_FP64: <= 1e-10 '
+                                                  'from the reference, not bit-exact; opt-in)',
+                                           vs_exact_same_launch=fast_check,
+                                           speedup_over_exact=hits_kern_ms / hits_fast_ms),
+                'spot_diagram': {'wallclock_ms': float(np.median(spot_ms)),
+                                 'wallclock_min_ms': float(np.min(spot_ms)), 'rays': R,
+                                 'rays_through': n_through, 'kernel_hits_ms': hits_kern_ms,
+                                 'tolerance_mode': {'wallclock_ms': float(np.median(spot_tol_ms)),
+                                                    'wallclock_min_ms': float(np.min(spot_tol_ms)),
+                                                    'rays_through': n_through_tol,
+                                                    'max_abs_deviation_from_exact': spot_tol_dev,
+                                                    'what': 'the same call after session.set_tolerance_mode(True): '
+                                                            'opt-in, never the figure above'},
+                                 'pcie_floor_ms': n_through * 16 / 54.7e9 * 1e3,
+                                 'after_idle': cold_spot,
+                                 'what': 'rayoptics_amd.trace.trace_grid_spot(model, grid_rng, fld, wvl, '
+                                         'foc, image_pt): Python call -> host (R_ok, 2) float64 array '
+                                         '(survivors packed in ray order by the trace launch, written '
+                                         'straight into pinned host memory; 13 MB over PCIe at ~55 GB/s '
+                                         'is the floor)'},
+                'configs': configs,
+                'configs_batch_items_uploaded_every_pass': os.environ.get('ROX_BATCH_ALWAYS_UPLOAD') == '1',
+                'configs_batch_items_in_kernel_argument_up_to': 16,
+                'psf': psf,
+                'cpu_baseline': None,
+                'strong_scaling': None,
+            })
 
     emitted = threading.Event()
 
@@ -532,7 +555,7 @@ def main():
         head = guarded('strong_headline', lambda: strong_headline(args, torch, dist, multi, world, rank, fence))
         if rank == 0:
             line['weak_full'] = {k: line[k] for k in ('value', 'ms_per_step', 'cold_ms_per_step', 'rays_per_s',
-                                                      'config', 'scaling')}
+                                                      'config', 'scaling') if k in line}
             if 'error' in head:
                 line['headline'] = 'weak_full (the strong-scaled leg failed: ' + head['error'] + ')'
                 line['ok'] = False
@@ -572,9 +595,9 @@ def main():
                 line['strong_headline'] = {k: head[k] for k in ('exchange', 'ms_per_step_by_exchange', 'errors',
                                                                   'last_pass_phases_ms_rank0', 'grids_delivered')}
 
-    # every run: the fixed-size problems in every exchange variant (extra; the line above is
+    # --full: the fixed-size problems in every exchange variant (extra; the line above is
     # complete without it)
-    if not args.no_strong:
+    if args.full and not args.no_strong:
         strong = guarded('strong_scaling', lambda: strong_scaling(args, torch, dist, multi, world, rank,
                                                                    fence, ranks_seen))
         if rank == 0:
@@ -599,7 +622,7 @@ def main():
                         # the same problem behind the tolerance-mode kernels (ROX_FAST_FP64; opt-in, not the headline)
                         line['strong_equiv']['ms_per_step_tolerance_mode'] = tm['end_to_end_ms']
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         line['cpu_baseline'] = cpu_baseline(wl, fld, wi, opts, num, args.cpu_sample_rows,
                                             fi, dev_sample)
     emit()

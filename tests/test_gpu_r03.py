@@ -250,7 +250,7 @@ def test_bench_launches_its_own_ranks():
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT'):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3',
-                        '--warmup', '1', '--strong-num', '192', '--no-cpu-baseline', '--no-configs'],
+                        '--warmup', '1', '--strong-num', '192', '--full', '--no-cpu-baseline', '--no-configs'],
                        env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -308,7 +308,7 @@ def test_bench_reports_a_hung_exchange_and_keeps_its_line():
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT'):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '5',
-                        '--warmup', '2', '--no-cpu-baseline', '--no-configs', '--strong-timeout', '0.02'],
+                        '--warmup', '2', '--full', '--no-cpu-baseline', '--no-configs', '--strong-timeout', '0.02'],
                        env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode != 0
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]

@@ -9,7 +9,9 @@ walks the x axis from the start like the full grid, so its rays are the grid's r
 `bench.work_of`'s counts -- the figures `value` and `roofline.achieved` are computed from --
 are recomputed from the ORACLE's status arrays and pinned to the numbers DESIGN quotes.
 One item of each batched configs_leg launch gets the same treatment."""
+import json
 import os
+import subprocess
 import sys
 import threading
 
@@ -104,6 +106,29 @@ def test_the_main_leg_launch_bit_exact_and_its_work_counts():
     assert o_bytes == 1_004_884_352
     assert int((status == abi.OK).sum()) == 821_936
     eng.close()
+
+
+def test_a_plain_bench_run_prints_the_headline_alone(tmp_path):
+    """`python bench.py` without --full: one JSON line whose headline is that launch's work over
+    the time per step, none of the legs --full adds, and --dump-outputs still written"""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '5',
+                        '--warmup', '2', '--dump-outputs', str(tmp_path)],
+                       capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout[-2000:]
+    b = json.loads(lines[0])
+    assert b['ok'] is True and b['full'] is False
+    assert b['metric'] == 'ray-surface intersections/sec' and b['unit'] == 'ray-surface intersections/s'
+    assert b['higher_is_better'] is True and b['dtype'] == 'f64'
+    assert b['steps'] == 5 and b['warmup_steps_run'] >= 2
+    assert b['config']['intersections_per_step'] == 11_158_584
+    assert b['value'] == pytest.approx(b['config']['intersections_per_step'] / (b['ms_per_step'] * 1e-3))
+    for k in ('cold_ms_per_step', 'roofline', 'roofline_hits', 'spot_diagram', 'configs', 'psf',
+              'cpu_baseline', 'strong_scaling'):
+        assert k not in b, k
+    assert sorted(p.stem for p in tmp_path.glob('*.npy')) == [
+        'fail_surf', 'n_seg', 'op', 'pupil', 'ray_index', 'seg', 'status']
 
 
 @pytest.mark.parametrize('name,num,item,mode', [

@@ -8,9 +8,9 @@
 # steps:
 #   tests[:pytest -k expression]   pytest -m gpu (-x), log to pytest.log
 #   testfile:<path>[:k-expr]       one test file
-#   bench[:extra args]             python bench.py --steps 20 --warmup 5 (driver's shape) -> bench.json
-#   benchN:<n>[:extra args]        plain `python bench.py --gpus n` (self-launch; gloo + shared GPU rehearsal)
-#   prof[:tag[:extra args]]        rocprofv3 --kernel-trace --stats of bench.py (no cpu baseline) -> prof[_tag]/
+#   bench[:extra args]             python bench.py --steps 20 --warmup 5 --full (driver's shape) -> bench.json
+#   benchN:<n>[:extra args]        `python bench.py --gpus n --full` (self-launch; gloo + shared GPU rehearsal)
+#   prof[:tag[:extra args]]        rocprofv3 --kernel-trace --stats of bench.py --full (no cpu baseline) -> prof[_tag]/
 #   pmc:<workload>[:num]           tools/pmc_collect.sh passes for a workload -> pmc_<tag>_<workload>/
 #   probe:<mode>:<workload>[:field[:lib[:uncached]]]   tools/sustained_probe.py (steady-state kernel time)
 #   py:<script and args>           python <script...> > <tag>/<script>.out
@@ -39,7 +39,7 @@ for step in "$@"; do
       else timeout 2400 python -m pytest "$f" -m gpu -x -q > "$log" 2>&1; fi
       echo "rc=$?" >> "$log"; tail -12 "$log" ;;
     bench)
-      timeout 1200 python bench.py --gpus 1 --steps 20 --warmup 5 $rest > "$OUT/bench.json" 2> "$OUT/bench.err"
+      timeout 1200 python bench.py --gpus 1 --steps 20 --warmup 5 --full $rest > "$OUT/bench.json" 2> "$OUT/bench.err"
       echo "rc=$? lines=$(wc -l < "$OUT/bench.json")"; tail -3 "$OUT/bench.err"
       python - "$OUT/bench.json" <<'PY'
 import json, sys
@@ -62,7 +62,7 @@ PY
       ;;
     benchN)
       n=${rest%%:*}; extra=""; [ "$rest" != "$n" ] && extra=${rest#*:}
-      ROX_BENCH_BACKEND=gloo ROX_BENCH_SHARE_GPU=1 timeout 1500 python bench.py --gpus $n --steps 20 --warmup 5 $extra > "$OUT/bench_n$n.json" 2> "$OUT/bench_n$n.err"
+      ROX_BENCH_BACKEND=gloo ROX_BENCH_SHARE_GPU=1 timeout 1500 python bench.py --gpus $n --steps 20 --warmup 5 --full $extra > "$OUT/bench_n$n.json" 2> "$OUT/bench_n$n.err"
       echo "n=$n rc=$? lines=$(wc -l < "$OUT/bench_n$n.json")"; tail -5 "$OUT/bench_n$n.err"
       python - "$OUT/bench_n$n.json" <<'PY'
 import json, sys
@@ -78,6 +78,7 @@ PY
       R=$PWD
       ptag=${rest%%:*}; pextra=""; [ "$rest" != "$ptag" ] && pextra=${rest#*:}
       pdir="prof${ptag:+_$ptag}"
+      pextra="--full $pextra"      # the profile covers every leg the bench has
       (cd /tmp; export TMPDIR=/tmp; timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$OUT/$pdir" -o bench -- python "$R/bench.py" --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline $pextra > "$R/$OUT/${pdir}_bench.json" 2> "$R/$OUT/$pdir.err")
       echo "rc=$?"; find "$OUT/$pdir" -name "*kernel_stats.csv" | head -1 | xargs -r head -12 | cut -c1-220
       find "$OUT/$pdir" -name "*kernel_trace.csv" -size +8M -delete ;;

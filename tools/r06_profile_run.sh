@@ -16,6 +16,6 @@ cp profiles/valu_per_intersection.json gpurun_out/$T/valu_per_intersection.json
 python tools/make_traffic.py gpurun_out/pmc_${T}_dblgauss_c2 gpurun_out/$T/traffic.json "gpurun_out/pmc_${T}_dblgauss_c2 ($T)" > gpurun_out/$T/make_traffic.log 2>&1
 # the bench line once more, now that traffic / valu records of THIS build exist
 cp gpurun_out/$T/traffic.json profiles/traffic.json
-timeout 1200 python bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/$T/bench_with_traffic.json 2> gpurun_out/$T/bench_with_traffic.err
+bash tools/gpu_run.sh ${T}_with_traffic bench
 find gpurun_out/$T -name "*kernel_stats.csv" | head
 tail -4 gpurun_out/${T}_run.log
