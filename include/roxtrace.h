@@ -652,6 +652,65 @@ int rox_focus_mtf(int32_t n_items, int32_t n_planes, const double *psf, int32_t 
                   const double *pitch, int32_t n_freq, const double *freqs,
                   double *otf, void *stream);
 
+/* Encircled energy through focus, geometric: ray counts within radii and the radii that hold
+ * given fractions of the rays, for the spot of every plane of a through-focus scan.
+ *   rows, status  DEVICE [n_items][n_planes][3][ld] and [n_items][ld] (the through-focus
+ *          layouts): components 0 and 1 are x abr and y abr about the plane's image point.  Only
+ *          the first n_rays rays count, and of those only the ones with status ROX_OK; the rows
+ *          of a failed ray are never read.
+ *   centers  HOST [n_items][n_planes][2], finite, in the rows' coordinates; NULL = (0, 0).
+ *          d2 = dx*dx + dy*dy with dx = x - cx, dy = y - cy: each step one IEEE binary64
+ *          operation in this order, no contraction into FMA.
+ *   radii  HOST [n_items][n_planes][n_radii], each finite and >= 0, non-decreasing within a
+ *          plane (read only with counts).
+ *   counts optional, host or device [n_items][n_planes][n_radii]: the number of OK rays with
+ *          d2 <= r*r (r*r one IEEE product).  Exact.
+ *   fractions  HOST [n_frac], each in (0, 1] (read only with ee_radius).
+ *   ee_radius  optional, host or device [n_items][n_planes][n_frac]: sqrt(D(m)), D(1) <= ... <=
+ *          D(n) the plane's sorted d2 and m = clamp(ceil(fractions[q] * n), 1, n) (the product
+ *          one IEEE product): an exact order statistic (fraction 1: the farthest ray).  NaN
+ *          where n == 0.
+ *   n_ok   optional, host or device [n_items][n_planes]: the OK ray count n.
+ * counts and ee_radius may not both be NULL.  n_items in [1, ROX_MAX_FOCUS_ITEMS], n_planes in
+ * [1, ROX_MAX_FOCUS_PLANES], n_rays in [1, ld], n_radii in [0, ROX_MAX_EE_RADII] (>= 1 with
+ * counts), n_frac in [0, ROX_MAX_EE_FRACTIONS] (>= 1 with ee_radius).  Integer histograms and a
+ * radix select on the bit patterns of d2; identical calls give bit-identical results, host and
+ * device destinations alike.  Argument errors return ROX_E_ARG naming the parameter before
+ * anything is enqueued.  Scratch is bounded per launch; larger jobs run as consecutive launches
+ * with the same results.  Asynchronous on `stream` unless an output is host memory.          */
+#define ROX_MAX_EE_RADII     1024
+#define ROX_MAX_EE_FRACTIONS   64
+int rox_focus_ee(int32_t n_items, int32_t n_planes, const double *rows, int64_t ld,
+                 const uint8_t *status, int64_t n_rays, const double *centers,
+                 int32_t n_radii, const double *radii, int64_t *counts,
+                 int32_t n_frac, const double *fractions, double *ee_radius,
+                 int64_t *n_ok, void *stream);
+
+/* Encircled energy through focus, diffraction: the fraction of every PSF rox_focus_psf writes
+ * that lies within given radii.  Orientation as rox_focus_mtf: pixel (j, l) sits at image
+ * (X, Y) = (-p (j - M/2), -p (l - M/2)) about the plane's image point, M = maxdim.
+ *   psf    DEVICE [n_items][n_planes][maxdim][maxdim] (the rox_focus_psf layout)
+ *   pitch  HOST [n_items][n_planes], each finite and > 0
+ *   centers  HOST [n_items][n_planes][2], finite, in those coordinates; NULL = each PSF's own
+ *          centroid.
+ *   radii  HOST [n_items][n_planes][n_radii], each finite and >= 0, non-decreasing per plane
+ *   ee     host or device [n_items][n_planes][n_radii]: the sum of the PSF over the pixels whose
+ *          centre has d2 <= r*r (d2 formed from X - cx and Y - cy as rox_focus_ee forms it),
+ *          divided by the sum over all pixels.  Numerator and denominator are reduced in the
+ *          same fixed order: a radius covering every pixel gives exactly 1.0.  NaN where the
+ *          PSF's sum is not positive and finite.
+ *   centroid  optional, host or device [n_items][n_planes][2]: sum(X PSF) / sum(PSF) and
+ *          likewise for Y, written whether or not it served as the centre (NaN where the sum is
+ *          not positive and finite).
+ * No floating-point atomics: identical calls give bit-identical results.  n_items in
+ * [1, ROX_MAX_FOCUS_ITEMS], n_planes in [1, ROX_MAX_FOCUS_PLANES], maxdim in [2, 32768], n_radii
+ * in [1, ROX_MAX_EE_RADII]; argument errors return ROX_E_ARG naming the parameter before
+ * anything is enqueued.  Scratch is bounded per launch; larger stacks run as consecutive
+ * launches with the same results.  Asynchronous on `stream` unless an output is host memory. */
+int rox_focus_psf_ee(int32_t n_items, int32_t n_planes, const double *psf, int32_t maxdim,
+                     const double *pitch, const double *centers, int32_t n_radii,
+                     const double *radii, double *ee, double *centroid, void *stream);
+
 /* chief-ray aiming ------------------------------------------------------- */
 /* One problem per (field, wavelength): trace.iterate_ray
  * (rayoptics/raytr/trace.py:313-415) as trace.aim_chief_ray calls it

@@ -1181,6 +1181,290 @@ def through_focus_mtf(opt_model, focs, freqs, flds=None, wvls=None, num_rays=32,
                            out_psf)
 
 
+# ---- encircled energy through focus ---------------------------------------------------------
+def curve_radius(radii, curve, fraction):
+    """the radius at which a sampled encircled-energy curve first reaches ``fraction``: linear
+    interpolation inside the first segment that crosses it (the first sample when it already
+    does); NaN when the curve never reaches it or holds NaN"""
+    r = np.asarray(radii, dtype=np.float64)
+    e = np.asarray(curve, dtype=np.float64)
+    if np.isnan(e).any():
+        return float('nan')
+    hit = np.nonzero(e >= fraction)[0]
+    if not hit.size:
+        return float('nan')
+    j = int(hit[0])
+    if j == 0:
+        return float(r[0])
+    t = (fraction - e[j - 1]) / (e[j] - e[j - 1])
+    return float(r[j - 1] + t * (r[j] - r[j - 1]))
+
+
+def _curve_radii(radii, curves, fractions):
+    """curve_radius over [..., n] radii and curves -> [..., Nf]"""
+    r = np.asarray(radii, dtype=np.float64)
+    c = np.asarray(curves, dtype=np.float64)
+    lead = c.shape[:-1]
+    r = np.broadcast_to(r, c.shape)
+    out = np.empty(lead + (len(fractions),))
+    for idx in np.ndindex(*lead):
+        out[idx] = [curve_radius(r[idx], c[idx], fq) for fq in fractions]
+    return out
+
+
+class ThroughFocusEE:
+    """what :func:`through_focus_ee` returns.
+
+    focs, fractions, radii, wvls, field_wts, spectral_wts, ref_wvl, kind   as used
+                ('geometric' or 'diffraction'; ``radii`` None when not given)
+    image_pts   [F, W, K, 2] each plane's image point
+    n_ok        [F, W, K] OK rays per plane (geometric; None for diffraction)
+    strehl      [F, W, K] each plane's Strehl ratio (diffraction; None for geometric)
+    pitch       [F, W, K] each PSF's pixel pitch (diffraction; None for geometric)
+    centroid    [F, W, K, 2] each item's centre about its image point: the spot centroid
+                (geometric) or the PSF centroid (diffraction)
+    ee_radius   [F, W, K, Nf] the radius about that centre holding each fraction: the exact
+                order statistic of the rays (geometric, rox_focus_ee), or interpolated on the
+                item's curve (diffraction); NaN where no ray arrived
+    ee          [F, W, K, Nr] the encircled energy at ``radii`` about that centre (None without
+                ``radii``)
+    curve_radii [F, K, n_curve] the radii of each field's polychromatic curve
+    poly_ee     [F, K, n_curve] the polychromatic encircled energy about the field's polychromatic
+                centroid at curve_radii
+    poly_ee_at  [F, K, Nr] the same at ``radii`` (None without ``radii``)
+    poly_ee_radius [F, K, Nf] poly_ee interpolated at each fraction: its resolution is the
+                curve's step, curve_radii[..., 1]
+    best_focus  [F, Nf] (+ ``_kind``): :func:`best_focus` of each field's poly_ee_radius curve
+    best_focus_all [Nf] (+ ``_kind``): the same of the field-weighted mean of poly_ee_radius"""
+
+    def __init__(self, focs, fractions, radii, wvls, field_wts, spectral_wts, ref_wvl, kind, image_pts,
+                 centroid, ee_radius, ee, curve_radii, poly_ee, poly_ee_at, n_ok=None, strehl=None, pitch=None):
+        self.focs = np.asarray(focs, dtype=np.float64)
+        self.fractions = np.asarray(fractions, dtype=np.float64)
+        self.radii = None if radii is None else np.asarray(radii, dtype=np.float64)
+        self.wvls = list(wvls)
+        self.field_wts = np.asarray(field_wts, dtype=np.float64)
+        self.spectral_wts = np.asarray(spectral_wts, dtype=np.float64)
+        self.ref_wvl = ref_wvl
+        self.kind = kind
+        self.image_pts = image_pts
+        self.centroid = centroid
+        self.n_ok = n_ok
+        self.strehl = strehl
+        self.pitch = pitch
+        self.ee_radius = ee_radius
+        self.ee = ee
+        self.curve_radii = curve_radii
+        self.poly_ee = poly_ee
+        self.poly_ee_at = poly_ee_at
+        self.poly_ee_radius = _curve_radii(curve_radii, poly_ee, self.fractions)
+        F, _K, Nf = self.poly_ee_radius.shape
+        self.best_focus = np.empty((F, Nf))
+        self.best_focus_kind = np.empty((F, Nf), dtype=object)
+        for f in range(F):
+            for q in range(Nf):
+                self.best_focus[f, q], self.best_focus_kind[f, q] = best_focus(self.focs, self.poly_ee_radius[f, :, q])
+        res = [overall_best_focus(self.focs, self.poly_ee_radius[:, :, q], self.field_wts) for q in range(Nf)]
+        self.best_focus_all = np.array([r[0] for r in res])
+        self.best_focus_all_kind = np.array([r[1] for r in res], dtype=object)
+
+
+def _check_fractions(fractions, what):
+    f = np.asarray(fractions, dtype=np.float64).reshape(-1)
+    if not 1 <= f.size <= abi.MAX_EE_FRACTIONS:
+        raise ValueError(f'{what}: 1 to {abi.MAX_EE_FRACTIONS} fractions, got {f.size}')
+    if not ((f > 0).all() and (f <= 1).all()):
+        raise ValueError(f'{what}: fractions must lie in (0, 1], got {f}')
+    return f
+
+
+def _check_radii(radii, what):
+    if radii is None:
+        return None
+    r = np.asarray(radii, dtype=np.float64).reshape(-1)
+    if not 1 <= r.size <= abi.MAX_EE_RADII:
+        raise ValueError(f'{what}: 1 to {abi.MAX_EE_RADII} radii, got {r.size}')
+    if not (np.isfinite(r).all() and (r >= 0).all() and (np.diff(r) >= 0).all()):
+        raise ValueError(f'{what}: radii must be finite, >= 0 and non-decreasing, got {r}')
+    return r
+
+
+def poly_centroid(centroid, image_pts, wts, ok):
+    """C [K, 2] = sum_w wts_w (image_pt_w + centroid_w) / sum_w wts_w over the entries with ``ok``
+    (centroid, image_pts [W, K, 2]; wts [W] or [W, K]); NaN where no weight is left"""
+    W, K = np.asarray(ok).shape
+    w = np.where(ok, np.broadcast_to(np.asarray(wts, dtype=np.float64).reshape(W, -1), (W, K)), 0.0)
+    c = np.where(ok[..., None], np.asarray(image_pts) + np.asarray(centroid), 0.0)
+    tot = w.sum(axis=0)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        return np.where(tot[:, None] > 0, (w[..., None] * c).sum(axis=0) / tot[:, None], np.nan)
+
+
+def through_focus_ee(opt_model, focs, fractions=(0.5, 0.8), radii=None, kind='geometric', flds=None, wvls=None,
+                     num_rays=64, maxdim=None, field_wts=None, spectral_wts=None, ref_wvl=None, pitch=None,
+                     n_curve=256, **kwargs):
+    """Encircled energy through focus, per field and wavelength and polychromatic per field, on the
+    device: one rox_trace_through_focus_grids launch traces each item's square pupil grid (as
+    :func:`through_focus_mtf`) and evaluates it at every focus.  Fields, wavelengths and weights
+    default as in :func:`through_focus_map`.  Returns a :class:`ThroughFocusEE`.
+
+    ``kind='geometric'``: the spot of the rays.  Per item, about the plane's spot centroid,
+    rox_focus_ee gives the exact order-statistic radius holding each fraction and, with ``radii``
+    (1-D, system units), the fraction of the rays within each.  Per field, about the polychromatic
+    centroid C of :func:`poly_merge` (lateral colour included), each wavelength's ray counts are
+    weighted by its spectral weight, poly_ee(r) = sum_w s_w counts_w(r) / sum_w s_w n_w, on
+    ``n_curve`` radii from 0 to the farthest ray R_max (the last one ulp beyond it);
+    poly_ee_radius is interpolated on that curve, to a resolution of R_max / (n_curve - 1).
+
+    ``kind='diffraction'``: the PSFs of rox_focus_psf (``num_rays`` even, ``maxdim`` -- default
+    4 ``num_rays`` -- at least 2 ``num_rays``), in groups under MTF_PSF_CHUNK_BYTES.  Per item,
+    about the PSF's own centroid, rox_focus_psf_ee gives the curve on ``n_curve`` radii from 0 to
+    p maxdim / 2 (p its pitch) and ee_radius is interpolated on it.  Per field, about
+    C = sum_w s_w (image_pt_w + centroid_w) / sum_w s_w, poly_ee = sum_w s_w ee_w / sum_w s_w of
+    the unit-energy PSFs, on radii up to the smallest window of the field's wavelengths.  The EE
+    is that of the PSF window, which is periodic: light the window wraps counts where it lands.
+    Each PSF's pitch is calc_psf_scaling's delta_xp; a model without paraxial data needs
+    ``pitch`` [F, W, K]."""
+    from .engine import grid_rays, FocusRows
+    what = 'through_focus_ee'
+    focs = _check_focs(focs, what)
+    frac = _check_fractions(fractions, what)
+    rad = _check_radii(radii, what)
+    if kind not in ('geometric', 'diffraction'):
+        raise ValueError(f"{what}: kind must be 'geometric' or 'diffraction', got {kind!r}")
+    n_curve = int(n_curve)
+    if not 2 <= n_curve <= abi.MAX_EE_RADII:
+        raise ValueError(f'{what}: n_curve {n_curve} outside [2, {abi.MAX_EE_RADII}]')
+    num_rays = int(num_rays)
+    if kind == 'diffraction':
+        maxdim = 4 * num_rays if maxdim is None else int(maxdim)
+        if num_rays < 2 or num_rays % 2:
+            raise ValueError(f'{what}: num_rays must be even and >= 2, got {num_rays}')
+        if maxdim < 2 * num_rays:
+            raise ValueError(f'{what}: maxdim {maxdim} < 2 num_rays = {2 * num_rays}')
+        if not _psf_block_fits(num_rays, maxdim):
+            raise ValueError(f'{what}: the {num_rays} x {num_rays} grid does not fit in maxdim {maxdim}')
+    elif num_rays < 1:
+        raise ValueError(f'{what}: num_rays must be >= 1, got {num_rays}')
+    flds, wvls, field_wts, spectral_wts, ref_wvl = _map_spec(opt_model, flds, wvls, field_wts, spectral_wts,
+                                                             ref_wvl, what)
+    F, W, K = len(flds), len(wvls), len(focs)
+    s = np.asarray(spectral_wts, dtype=np.float64)
+    if kind == 'diffraction' and pitch is not None:
+        pitch = np.array(np.broadcast_to(np.asarray(pitch, dtype=np.float64), (F, W, K)))
+        if not (np.isfinite(pitch).all() and (pitch > 0).all()):
+            raise ValueError(f'{what}: pitch must be finite and > 0')
+    ref_radii = []
+    eng, fs, wis, grids, opts_list, planes = _map_items(opt_model, flds, wvls, focs, None, num_rays, kwargs,
+                                                        radii=ref_radii)
+    R = grid_rays(grids[0])
+    image_pts = np.array([[(p.image_pt[0], p.image_pt[1]) for p in ps] for ps in planes]).reshape(F, W, K, 2)
+    args = dict(focs=focs, fractions=frac, radii=rad, wvls=wvls, field_wts=field_wts, spectral_wts=spectral_wts,
+                ref_wvl=ref_wvl, kind=kind, image_pts=image_pts)
+
+    if kind == 'geometric':
+        stats, dev_rows = eng.trace_pupil_grids_focus(fs, wis, grids, opts_list, planes, want_rows=True)
+        stats = stats.reshape(F, W, K)
+        own = np.nan_to_num(np.stack([stats['cx'], stats['cy']], axis=-1))          # [F, W, K, 2]
+        flat = (F * W, K)
+        _c, ee_radius, n_ok = eng.focus_ee(dev_rows, R, own.reshape(flat + (2,)), None, frac)
+        ee = None
+        if rad is not None:
+            counts, _r, _n = eng.focus_ee(dev_rows, R, own.reshape(flat + (2,)), rad, None)
+            with np.errstate(invalid='ignore', divide='ignore'):
+                ee = np.where(n_ok[..., None] > 0, counts / n_ok[..., None], np.nan).reshape(F, W, K, -1)
+        ref = wvls.index(ref_wvl)
+        pm = [poly_merge(stats[f], image_pts[f], s, ref) for f in range(F)]
+        C = np.stack([np.stack([m['cx'], m['cy']], axis=-1) for m in pm])           # [F, K, 2]
+        about = np.nan_to_num(C[:, None] - image_pts).reshape(flat + (2,))          # [F W, K, 2]
+        _c, far, _n = eng.focus_ee(dev_rows, R, about, None, [1.0])
+        far = far.reshape(F, W, K)
+        with np.errstate(invalid='ignore'):
+            r_max = np.where(np.isnan(far).all(axis=1), 0.0, np.nanmax(np.where(np.isnan(far), -np.inf, far), axis=1))
+        curve_radii = r_max[..., None] * np.linspace(0.0, 1.0, n_curve)             # [F, K, n_curve]
+        # R_max^2 may round below the farthest ray's d2: the last radius is one ulp beyond R_max
+        curve_radii[..., -1] = np.nextafter(r_max, np.inf)
+        counts, _r, _n = eng.focus_ee(dev_rows, R, about, np.repeat(curve_radii, W, axis=0), None)
+        n_ok = n_ok.reshape(F, W, K)
+        poly_ee = _poly_counts(counts.reshape(F, W, K, n_curve), n_ok, s)
+        poly_ee_at = None
+        if rad is not None:
+            counts, _r, _n = eng.focus_ee(dev_rows, R, about, rad, None)
+            poly_ee_at = _poly_counts(counts.reshape(F, W, K, -1), n_ok, s)
+        return ThroughFocusEE(centroid=np.stack([stats['cx'], stats['cy']], axis=-1),
+                              ee_radius=ee_radius.reshape(F, W, K, -1), ee=ee, curve_radii=curve_radii,
+                              poly_ee=poly_ee, poly_ee_at=poly_ee_at, n_ok=n_ok, **args)
+
+    # diffraction
+    assert R == num_rays * num_rays
+    if pitch is None:
+        scal = [[psf_scaling(opt_model, wvls[i % W], num_rays, maxdim, r) for r in ref_radii[i]]
+                for i in range(F * W)]
+        if any(x is None for xs in scal for x in xs):
+            raise ValueError(f'{what}: the model has no paraxial data for calc_psf_scaling: pass pitch [F, W, K]')
+        pitch = np.array([[x[1] for x in xs] for xs in scal], dtype=np.float64).reshape(F, W, K)
+    _none, dev_rows = eng.trace_pupil_grids_focus(fs, wis, grids, opts_list, planes, want_rows=True,
+                                                  want_stats=False)
+    scale = np.array([1 / opt_model.nm_to_sys_units(wvls[i % W]) for i in range(F * W)])
+    window = pitch * (maxdim / 2)                                                   # [F, W, K]
+    item_radii = window[..., None] * np.linspace(0.0, 1.0, n_curve)                 # [F, W, K, n_curve]
+    curve_radii = window.min(axis=1)[..., None] * np.linspace(0.0, 1.0, n_curve)   # [F, K, n_curve]
+    per_field = W * K * maxdim * maxdim * 8
+    fstep = max(1, MTF_PSF_CHUNK_BYTES // per_field)                                # whole fields per group
+    strehl = np.empty((F, W, K))
+    centroid = np.empty((F, W, K, 2))
+    item_ee = np.empty((F, W, K, n_curve))
+    per_w = np.empty((F, W, K, n_curve))
+    ee = None if rad is None else np.empty((F, W, K, rad.size))
+    per_w_at = None if rad is None else np.empty((F, W, K, rad.size))
+    C = np.empty((F, K, 2))
+    for f0 in range(0, F, fstep):
+        f1 = min(F, f0 + fstep)
+        part = FocusRows(dev_rows.rows[f0 * W:f1 * W], dev_rows.status[f0 * W:f1 * W])
+        dev_psf, psf_stats = eng.focus_psf(part, num_rays, maxdim, scale[f0 * W:f1 * W], want_psf=True)
+        p = pitch[f0:f1].reshape(-1, K)
+        e, cen = eng.focus_psf_ee(dev_psf, p, None, item_radii[f0:f1].reshape(-1, K, n_curve))
+        item_ee[f0:f1] = e.reshape(f1 - f0, W, K, n_curve)
+        centroid[f0:f1] = cen.reshape(f1 - f0, W, K, 2)
+        strehl[f0:f1] = psf_stats['strehl'].reshape(f1 - f0, W, K)
+        if rad is not None:
+            e, _cen = eng.focus_psf_ee(dev_psf, p, None, rad, want_centroid=False)
+            ee[f0:f1] = e.reshape(f1 - f0, W, K, -1)
+        for f in range(f0, f1):
+            C[f] = poly_centroid(centroid[f], image_pts[f], s, np.isfinite(centroid[f]).all(axis=-1))
+        about = np.nan_to_num(C[f0:f1, None] - image_pts[f0:f1]).reshape(-1, K, 2)
+        e, _cen = eng.focus_psf_ee(dev_psf, p, about, np.repeat(curve_radii[f0:f1], W, axis=0),
+                                   want_centroid=False)
+        per_w[f0:f1] = e.reshape(f1 - f0, W, K, n_curve)
+        if rad is not None:
+            e, _cen = eng.focus_psf_ee(dev_psf, p, about, rad, want_centroid=False)
+            per_w_at[f0:f1] = e.reshape(f1 - f0, W, K, -1)
+        del dev_psf
+    ee_radius = _curve_radii(item_radii, item_ee, frac)
+    poly_ee = _poly_psf(per_w, s)
+    poly_ee_at = None if rad is None else _poly_psf(per_w_at, s)
+    return ThroughFocusEE(centroid=centroid, ee_radius=ee_radius, ee=ee, curve_radii=curve_radii, poly_ee=poly_ee,
+                          poly_ee_at=poly_ee_at, strehl=strehl, pitch=pitch, **args)
+
+
+def _poly_counts(counts, n_ok, s):
+    """[F, W, K, N] ray counts, [F, W, K] ray totals -> sum_w s_w counts_w / sum_w s_w n_w [F, K, N]"""
+    num = (s[None, :, None, None] * counts).sum(axis=1)
+    den = (s[None, :, None] * n_ok).sum(axis=1)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        return np.where(den[..., None] > 0, num / den[..., None], np.nan)
+
+
+def _poly_psf(ee, s):
+    """[F, W, K, N] unit-energy EE curves -> sum_w s_w ee_w / sum_w s_w over the wavelengths whose
+    curve is not NaN [F, K, N]; NaN where none is left"""
+    ok = ~np.isnan(ee)
+    w = np.where(ok, s[None, :, None, None], 0.0)
+    tot = w.sum(axis=1)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        return np.where(tot > 0, np.where(ok, w * ee, 0.0).sum(axis=1) / tot, np.nan)
+
+
 # ---- point spread function ------------------------------------------------------
 PSF_BACKEND = None          # None -> engine.calc_psf (the HIP path); tests inject a double
 

@@ -990,6 +990,97 @@ class TraceEngine:
             return t.view_as_complex(out)
         return out.view(np.complex128)[..., 0]
 
+    @_in_flight
+    def focus_ee(self, focus_rows, n_rays, centers, radii, fractions, on_device=False):
+        """rox_focus_ee over the rows of a through-focus launch (``focus_rows``: the FocusRows
+        trace_pupil_grid_focus / trace_pupil_grids_focus return, still in HBM): the geometric
+        encircled energy of each plane's spot over the first ``n_rays`` rays with status OK,
+        about ``centers`` (broadcast to [n_items, K, 2], in the rows' coordinates; None = the
+        image point).  ``radii`` (broadcast to [n_items, K, Nr], non-decreasing per plane; None
+        for no counts) and ``fractions`` ([Nf] in (0, 1]; None for no radii).  Returns
+        ``(counts, ee_radius, n_ok)``: int64 [n_items, K, Nr] rays with d2 <= r^2, float64
+        [n_items, K, Nf] the exact order-statistic radius that holds each fraction (NaN where no
+        ray arrived), int64 [n_items, K] -- NumPy, or torch tensors in HBM with ``on_device``;
+        None for what was not asked."""
+        t = self.torch
+        rows, status = focus_rows.rows, focus_rows.status
+        if rows.dim() == 3:
+            rows, status = rows.unsqueeze(0), status.unsqueeze(0)
+        n_items, K = int(rows.shape[0]), int(rows.shape[1])
+        ld = int(rows.stride(2))
+        if rows.dtype != t.float64 or rows.stride(3) != 1 or rows.stride(1) != 3 * ld or \
+                rows.stride(0) != K * 3 * ld or status.stride(-1) != 1 or \
+                (n_items > 1 and status.stride(0) != ld):
+            raise EngineError('focus_ee reads the [n_items][K][3][ld] rows and [n_items][ld] status '
+                              'of a through-focus launch')
+        n_rays = int(n_rays)
+        if not 1 <= n_rays <= min(int(rows.shape[3]), int(status.shape[-1])):
+            raise EngineError(f'focus_ee: n_rays {n_rays} outside [1, {int(rows.shape[3])}]')
+        if radii is None and fractions is None:
+            raise EngineError('focus_ee: radii or fractions (or both)')
+        c = None
+        if centers is not None:
+            c = np.ascontiguousarray(np.broadcast_to(np.asarray(centers, dtype=np.float64), (n_items, K, 2)))
+        r = f = None
+        Nr = Nf = 0
+        if radii is not None:
+            r = np.asarray(radii, dtype=np.float64)
+            Nr = int(r.shape[-1]) if r.ndim else 1
+            r = np.ascontiguousarray(np.broadcast_to(r, (n_items, K, Nr)))
+        if fractions is not None:
+            f = np.ascontiguousarray(np.asarray(fractions, dtype=np.float64).reshape(-1))
+            Nf = int(f.size)
+
+        def out(shape, dtype, tdtype, want):
+            if not want:
+                return None, None
+            if on_device:
+                a = t.empty(shape, dtype=tdtype, device=self.device)
+                return a, a.data_ptr()
+            a = np.empty(shape, dtype=dtype)
+            return a, a.ctypes.data
+        counts, p_counts = out((n_items, K, Nr), np.int64, t.int64, r is not None)
+        eer, p_eer = out((n_items, K, Nf), np.float64, t.float64, f is not None)
+        n_ok, p_nok = out((n_items, K), np.int64, t.int64, True)
+        with t.cuda.device(self.device):
+            _check(self.lib.rox_focus_ee(n_items, K, rows.data_ptr(), ld, status.data_ptr(), n_rays,
+                                         c.ctypes.data if c is not None else None, Nr,
+                                         r.ctypes.data if r is not None else None, p_counts, Nf,
+                                         f.ctypes.data if f is not None else None, p_eer, p_nok,
+                                         self._stream()), 'rox_focus_ee')
+        return counts, eer, n_ok
+
+    @_in_flight
+    def focus_psf_ee(self, psf, pitch, centers, radii, want_centroid=True):
+        """rox_focus_psf_ee over the PSFs focus_psf returns (``psf``: float64 [n_items, K, M, M] in
+        HBM): the fraction of each PSF's sum over the pixels whose centre lies within ``radii``
+        (broadcast to [n_items, K, Nr], non-decreasing per plane) of ``centers`` (broadcast to
+        [n_items, K, 2] in image coordinates about the image point, None = each PSF's own
+        centroid); ``pitch`` (broadcast to [n_items, K]) is each plane's pixel pitch, pixel
+        (j, l) sitting at (-p (j - M/2), -p (l - M/2)) as in focus_mtf.  Returns
+        ``(ee, centroid)``: float64 [n_items, K, Nr] (NaN on planes no ray reached) and
+        [n_items, K, 2] (None without ``want_centroid``)."""
+        t = self.torch
+        if psf.dim() != 4 or psf.dtype != t.float64 or not psf.is_contiguous() or \
+                int(psf.shape[2]) != int(psf.shape[3]):
+            raise EngineError('focus_psf_ee reads the contiguous float64 [n_items][K][M][M] PSFs of focus_psf')
+        n_items, K, M = int(psf.shape[0]), int(psf.shape[1]), int(psf.shape[2])
+        p = np.ascontiguousarray(np.broadcast_to(np.asarray(pitch, dtype=np.float64), (n_items, K)))
+        r = np.asarray(radii, dtype=np.float64)
+        Nr = int(r.shape[-1]) if r.ndim else 1
+        r = np.ascontiguousarray(np.broadcast_to(r, (n_items, K, Nr)))
+        c = None
+        if centers is not None:
+            c = np.ascontiguousarray(np.broadcast_to(np.asarray(centers, dtype=np.float64), (n_items, K, 2)))
+        ee = np.empty((n_items, K, Nr), dtype=np.float64)
+        cen = np.empty((n_items, K, 2), dtype=np.float64) if want_centroid else None
+        with t.cuda.device(self.device):
+            _check(self.lib.rox_focus_psf_ee(n_items, K, psf.data_ptr(), M, p.ctypes.data,
+                                             c.ctypes.data if c is not None else None, Nr, r.ctypes.data,
+                                             ee.ctypes.data, cen.ctypes.data if cen is not None else None,
+                                             self._stream()), 'rox_focus_psf_ee')
+        return ee, cen
+
     def _spot_stats(self, seg_ptr, ld, status_ptr, n_hits_ptr, n, layout, x_edges, y_edges):
         summ = abi.SpotSummary()
         hist = None
