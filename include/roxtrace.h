@@ -711,6 +711,60 @@ int rox_focus_psf_ee(int32_t n_items, int32_t n_planes, const double *psf, int32
                      const double *pitch, const double *centers, int32_t n_radii,
                      const double *radii, double *ee, double *centroid, void *stream);
 
+/* Zernike fits of the wavefront through focus: the least-squares coefficients of the OPD of
+ * every plane of a through-focus scan in a given Zernike basis.
+ *   rows, status  DEVICE [n_items][n_planes][3][ld] and [n_items][ld] (the through-focus
+ *          layouts).  Only component 2 (OPD) is read: W = wave_scale[i] * rows[i][k][2][r] in
+ *          waves (one IEEE product); the rows of a ray that is not fitted are never read.
+ *   grids  HOST [n_items]: each ROX_GRID_PRODUCT and whole (row_begin 0, row_count 0 or num),
+ *          num >= 2; start and stop may differ per item.  Ray r = a*num + b sits at pupil
+ *          (px[a], py[b]), each axis built from start by repeated += of (stop - start)/(num - 1)
+ *          in binary64, the doubles the trace started the ray from.
+ *   circle HOST [n_items][3]: (cx, cy, radius) in pupil coordinates, finite, radius > 0; NULL =
+ *          (0, 0, 1).  x = (px - cx) / radius, y = (py - cy) / radius; a ray is fitted when its
+ *          status is ROX_OK and x*x + y*y <= 1 (two products, then the sum, no FMA).
+ *   wave_scale  HOST [n_items], finite.
+ *   terms  HOST [n_terms]: term j is scale * R_n^|m|(rho) * {1 | cos(m theta) | sin(|m| theta)}
+ *          for m = 0, m > 0, m < 0, x = rho cos theta, y = rho sin theta.  Evaluated as
+ *          P(rho^2) * Re/Im((x + i y)^|m|), P the radial polynomial over rho^|m| with scale
+ *          folded into its integer coefficients, by Horner from the highest power.
+ *          1 <= n_terms <= ROX_MAX_ZERNIKE_TERMS, 0 <= n <= ROX_MAX_ZERNIKE_ORDER, |m| <= n,
+ *          n - |m| even, finite scale.
+ *   coef   optional, host or device [n_items][n_planes][n_terms], waves.
+ *   stats  optional, host or device [n_items][n_planes].
+ * coef and stats may not both be NULL.  Normal equations G c = Z^T W (G = Z^T Z, the same for
+ * every plane) accumulated with f64 MFMA in a fixed order, a Jacobi-equilibrated Cholesky
+ * solve, and one step of iterative refinement from a second read of the rows (c += G^-1 Z^T r);
+ * a third read forms the residual statistics from the residuals themselves.  fit = 1 where
+ * n < n_terms (n = 0 included), fit = 2 where a Cholesky pivot of the equilibrated G is not
+ * above 1e-12 (singular or ill-conditioned); either gives NaN coefficients, rms_residual and
+ * pv_residual.  cond is max/min pivot of the equilibrated G (1/pivot at the failing pivot with
+ * fit = 2, NaN with fit = 1).  No floating-point atomics: identical calls give bit-identical
+ * results, host and device destinations alike.  Argument errors return ROX_E_ARG naming the
+ * parameter and item before anything is enqueued.  Scratch is bounded per launch; larger jobs
+ * run as consecutive launches with the same results.  Asynchronous on `stream` unless an output
+ * is host memory.                                                                            */
+#define ROX_MAX_ZERNIKE_TERMS 91      /* every term up to radial order 12 */
+#define ROX_MAX_ZERNIKE_ORDER 20
+typedef struct rox_zernike_term {
+    int32_t n, m;
+    double scale;
+} rox_zernike_term;           /* 16 bytes */
+typedef struct rox_zernike_stats {
+    int64_t n;                /* rays fitted: status ROX_OK and inside the unit circle       */
+    int64_t n_outside;        /* ROX_OK rays outside the circle (not fitted, counted)         */
+    double rms;               /* sqrt(sum (W - mean W)^2 / n) over the fitted rays, waves     */
+    double rms_residual;      /* sqrt(sum (W - sum_j c_j Z_j)^2 / n), waves                   */
+    double pv_residual;       /* max - min of the residuals, waves                            */
+    double cond;              /* max / min Cholesky pivot of the equilibrated G               */
+    int32_t fit;              /* 0 fitted; 1 n < n_terms; 2 singular / ill-conditioned        */
+    int32_t reserved;
+} rox_zernike_stats;          /* 56 bytes */
+int rox_focus_zernike(int32_t n_items, int32_t n_planes, const double *rows, int64_t ld,
+                      const uint8_t *status, const rox_grid *grids, const double *circle,
+                      const double *wave_scale, int32_t n_terms, const rox_zernike_term *terms,
+                      double *coef, rox_zernike_stats *stats, void *stream);
+
 /* chief-ray aiming ------------------------------------------------------- */
 /* One problem per (field, wavelength): trace.iterate_ray
  * (rayoptics/raytr/trace.py:313-415) as trace.aim_chief_ray calls it

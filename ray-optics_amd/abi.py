@@ -179,6 +179,21 @@ MAX_FOCUS_ITEMS = 1024      # include/roxtrace.h ROX_MAX_FOCUS_ITEMS
 MAX_MTF_FREQS = 1024        # include/roxtrace.h ROX_MAX_MTF_FREQS
 MAX_EE_RADII = 1024         # include/roxtrace.h ROX_MAX_EE_RADII
 MAX_EE_FRACTIONS = 64       # include/roxtrace.h ROX_MAX_EE_FRACTIONS
+MAX_ZERNIKE_TERMS = 91      # include/roxtrace.h ROX_MAX_ZERNIKE_TERMS
+MAX_ZERNIKE_ORDER = 20      # include/roxtrace.h ROX_MAX_ZERNIKE_ORDER
+
+
+class ZernikeTerm(C.Structure):
+    """rox_zernike_term: radial order n, azimuthal m (< 0: sine), and the term's scale"""
+    _fields_ = [('n', C.c_int32), ('m', C.c_int32), ('scale', C.c_double)]
+
+
+class ZernikeStats(C.Structure):
+    """rox_zernike_stats: one plane's fitted / outside ray counts, RMS wavefront, residuals,
+    conditioning and fit status"""
+    _fields_ = [('n', C.c_int64), ('n_outside', C.c_int64), ('rms', C.c_double),
+                ('rms_residual', C.c_double), ('pv_residual', C.c_double), ('cond', C.c_double),
+                ('fit', C.c_int32), ('reserved', C.c_int32)]
 
 
 class Vig(C.Structure):
@@ -206,6 +221,8 @@ assert C.sizeof(Enp) == 136
 assert C.sizeof(FocusPlane) == 544
 assert C.sizeof(FocusStats) == 72
 assert C.sizeof(FocusPsfStats) == 32
+assert C.sizeof(ZernikeTerm) == 16
+assert C.sizeof(ZernikeStats) == 56
 
 # every symbol include/roxtrace.h declares (checked by tests/test_abi.py) ...
 EXPORTS = ('rox_abi_version', 'rox_device_count', 'rox_set_device',
@@ -216,7 +233,8 @@ EXPORTS = ('rox_abi_version', 'rox_device_count', 'rox_set_device',
            'rox_iterate_pupil_rays', 'rox_calc_psf',
            'rox_pin_host_memory', 'rox_unpin_host_memory', 'rox_copy_async', 'rox_synchronize',
            'rox_spot_stats', 'rox_trace_through_focus', 'rox_trace_through_focus_grids',
-           'rox_focus_psf', 'rox_focus_mtf', 'rox_focus_ee', 'rox_focus_psf_ee')
+           'rox_focus_psf', 'rox_focus_mtf', 'rox_focus_ee', 'rox_focus_psf_ee',
+           'rox_focus_zernike')
 # ... and the measurement / self-test helpers of include/roxtrace_diag.h
 DIAG_EXPORTS = ('rox_time_pupil_grid', 'rox_selftest_fp64', 'rox_diag_pack_launches')
 
@@ -286,6 +304,9 @@ def declare(lib):
     lib.rox_focus_ee.argtypes = [i32, i32, vp, i64, vp, i64, vp, i32, vp, vp, i32, vp, vp, vp, vp]
     lib.rox_focus_psf_ee.restype = C.c_int
     lib.rox_focus_psf_ee.argtypes = [i32, i32, vp, i32, vp, vp, i32, vp, vp, vp, vp]
+    lib.rox_focus_zernike.restype = C.c_int
+    lib.rox_focus_zernike.argtypes = [i32, i32, vp, i64, vp, P(Grid), vp, vp, i32, P(ZernikeTerm),
+                                      vp, vp, vp]
     lib.rox_time_pupil_grid.restype = C.c_int
     lib.rox_time_pupil_grid.argtypes = [vp, P(Field), P(Grid), i32, P(Opts),
                                         P(Out), vp, i32, P(dbl)]

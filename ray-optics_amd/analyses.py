@@ -1465,6 +1465,134 @@ def _poly_psf(ee, s):
         return np.where(tot > 0, np.where(ok, w * ee, 0.0).sum(axis=1) / tot, np.nan)
 
 
+# ---- Zernike fits through focus --------------------------------------------------------------
+def zero_crossing(focs, values):
+    """the focus at which a sampled curve crosses zero: a sample that is exactly 0 -> (focus,
+    'sample'); else linear interpolation inside the first pair of neighbouring samples of
+    opposite sign -> (focus, 'crossing').  NaN samples are skipped; no pair brackets zero ->
+    (nan, 'none')."""
+    f = np.asarray(focs, dtype=np.float64)
+    v = np.asarray(values, dtype=np.float64)
+    ok = ~np.isnan(v)
+    f, v = f[ok], v[ok]
+    for i in range(len(v)):
+        if v[i] == 0.0:
+            return float(f[i]), 'sample'
+        if i + 1 < len(v) and (v[i] < 0) != (v[i + 1] < 0) and v[i + 1] != 0.0:
+            return float(f[i] + (f[i + 1] - f[i]) * v[i] / (v[i] - v[i + 1])), 'crossing'
+    return float('nan'), 'none'
+
+
+class ThroughFocusZernike:
+    """what :func:`through_focus_zernike` returns.
+
+    focs, wvls, field_wts, spectral_wts, ref_wvl   as used
+    terms       the (n, m, scale) of each coefficient; ``names`` their classical names
+    coef        [F, W, K, J] the least-squares coefficients, in waves (NaN where a plane's fit
+                failed: stats['fit'] 1 too few rays, 2 singular)
+    stats       [F, W, K] engine.ZERNIKE_STATS_DTYPE: n, n_outside, rms, rms_residual,
+                pv_residual (waves), cond, fit
+    circle      [F, W, 3] (cx, cy, radius) of the unit circle in pupil coordinates
+    defocus_zero [F, W] (+ ``_kind``): :func:`zero_crossing` of each item's defocus (2, 0)
+                coefficient through focus (NaN, 'none' without a defocus term)
+    defocus_zero_field [F] (+ ``_kind``): the same at ref_wvl"""
+
+    def __init__(self, focs, wvls, field_wts, spectral_wts, ref_wvl, terms, coef, stats, circle):
+        from .zernike import term_names
+        self.focs = np.asarray(focs, dtype=np.float64)
+        self.wvls, self.field_wts, self.spectral_wts, self.ref_wvl = wvls, field_wts, spectral_wts, ref_wvl
+        self.terms = list(terms)
+        self.names = term_names(self.terms)
+        self.coef = coef
+        self.stats = stats
+        self.circle = circle
+        F, W, _K, _J = coef.shape
+        self.defocus_zero = np.full((F, W), np.nan)
+        self.defocus_zero_kind = np.full((F, W), 'none', dtype=object)
+        jd = [j for j, t in enumerate(self.terms) if (t[0], t[1]) == (2, 0)]
+        if jd:
+            for f in range(F):
+                for w in range(W):
+                    self.defocus_zero[f, w], self.defocus_zero_kind[f, w] = zero_crossing(
+                        self.focs, coef[f, w, :, jd[0]])
+        ref = self.wvls.index(ref_wvl)
+        self.defocus_zero_field = self.defocus_zero[:, ref].copy()
+        self.defocus_zero_field_kind = self.defocus_zero_kind[:, ref].copy()
+
+
+def zernike_terms(terms='fringe', n_terms=37):
+    """'fringe' / 'noll' and a count, or explicit (n, m[, scale]) triples -> checked triples"""
+    from . import zernike as Z
+    if isinstance(terms, str):
+        if terms == 'fringe':
+            return Z.fringe_terms(n_terms)
+        if terms == 'noll':
+            return Z.noll_terms(n_terms)
+        raise ValueError(f"Zernike terms: 'fringe', 'noll' or (n, m, scale) triples, got {terms!r}")
+    return Z.check_terms(terms)
+
+
+def zernike_circles(grids, circle, n_items, what):
+    """[n_items, 3] (cx, cy, radius): 'pupil' the unit circle, 'bbox' each grid's vignetting box's
+    centre and half its larger side, or values broadcast to [n_items, 3]"""
+    if isinstance(circle, str):
+        if circle == 'pupil':
+            return np.tile([0.0, 0.0, 1.0], (n_items, 1))
+        if circle == 'bbox':
+            return np.array([[0.5 * (g.start[0] + g.stop[0]), 0.5 * (g.start[1] + g.stop[1]),
+                              0.5 * max(abs(g.stop[0] - g.start[0]), abs(g.stop[1] - g.start[1]))]
+                             for g in grids])
+        raise ValueError(f"{what}: circle 'pupil', 'bbox' or (cx, cy, radius), got {circle!r}")
+    c = np.array(np.broadcast_to(np.asarray(circle, dtype=np.float64), (n_items, 3)))
+    if not (np.isfinite(c).all() and (c[:, 2] > 0).all()):
+        raise ValueError(f'{what}: circle must be finite with radius > 0')
+    return c
+
+
+def through_focus_zernike(opt_model, focs, flds=None, wvls=None, num_rays=64, terms='fringe', n_terms=37,
+                          circle='pupil', field_wts=None, spectral_wts=None, ref_wvl=None, **kwargs):
+    """Zernike fits of the wavefront of every field at every wavelength through focus, on the
+    device: one rox_trace_through_focus_grids launch traces each item's square pupil grid (the
+    trace_wavefront grid, as :func:`through_focus_map` with ``xy=None``) and evaluates it at every
+    focus, and one rox_focus_zernike fits each plane's OPD in waves -- the rows stay in HBM.
+    ``terms``: 'fringe' or 'noll' (the first ``n_terms``) or (n, m, scale) triples; ``circle``:
+    'pupil' the unit circle of the entrance pupil, 'bbox' the circle about each field's vignetting
+    box with half its larger side, or (cx, cy, radius) broadcast to [F, W, 3].  Fields,
+    wavelengths and weights default as in :func:`through_focus_map`
+    (:class:`ThroughFocusZernike`)."""
+    what = 'through_focus_zernike'
+    focs = _check_focs(focs, what)
+    num_rays = int(num_rays)
+    if num_rays < 2:
+        raise ValueError(f'{what}: num_rays must be >= 2, got {num_rays}')
+    tl = zernike_terms(terms, n_terms)
+    flds, wvls, field_wts, spectral_wts, ref_wvl = _map_spec(opt_model, flds, wvls, field_wts, spectral_wts,
+                                                             ref_wvl, what)
+    F, W, K = len(flds), len(wvls), len(focs)
+    if not isinstance(circle, str):
+        circle = np.broadcast_to(np.asarray(circle, dtype=np.float64), (F, W, 3)).reshape(F * W, 3)
+    eng, fs, wis, grids, opts_list, planes = _map_items(opt_model, flds, wvls, focs, None, num_rays, kwargs)
+    circ = zernike_circles(grids, circle, F * W, what)
+    _none, dev_rows = eng.trace_pupil_grids_focus(fs, wis, grids, opts_list, planes, want_rows=True,
+                                                  want_stats=False)
+    scale = np.array([1 / opt_model.nm_to_sys_units(wvls[i % W]) for i in range(F * W)])
+    coef, stats = eng.focus_zernike(dev_rows, grids, tl, scale, circ)
+    J = len(tl)
+    return ThroughFocusZernike(focs, wvls, field_wts, spectral_wts, ref_wvl, tl,
+                               np.asarray(coef).reshape(F, W, K, J), np.asarray(stats).reshape(F, W, K),
+                               circ.reshape(F, W, 3))
+
+
+def wavefront_zernike(opt_model, fld, wvl, foc=0., num_rays=64, terms='fringe', n_terms=37, circle='pupil',
+                      **kwargs):
+    """the Zernike fit of one field's wavefront at one wavelength and focus: :func:`through_focus_zernike`
+    of that single item -> (coef [J] in waves, stats record, terms)"""
+    r = through_focus_zernike(opt_model, [foc], flds=[fld], wvls=[wvl], num_rays=num_rays, terms=terms,
+                              n_terms=n_terms, circle=circle, field_wts=[1.0], spectral_wts=[1.0],
+                              ref_wvl=wvl, **kwargs)
+    return r.coef[0, 0, 0], r.stats[0, 0, 0], r.terms
+
+
 # ---- point spread function ------------------------------------------------------
 PSF_BACKEND = None          # None -> engine.calc_psf (the HIP path); tests inject a double
 

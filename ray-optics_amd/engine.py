@@ -144,6 +144,20 @@ FOCUS_PSF_STATS_DTYPE = np.dtype([(name, np.int64 if name == 'n' else np.float64
 assert FOCUS_PSF_STATS_DTYPE.itemsize == C.sizeof(abi.FocusPsfStats)
 
 
+# rox_zernike_stats: what focus_zernike returns
+ZERNIKE_STATS_DTYPE = np.dtype([('n', np.int64), ('n_outside', np.int64), ('rms', np.float64),
+                                ('rms_residual', np.float64), ('pv_residual', np.float64),
+                                ('cond', np.float64), ('fit', np.int32), ('reserved', np.int32)])
+assert ZERNIKE_STATS_DTYPE.itemsize == C.sizeof(abi.ZernikeStats)
+
+
+def zernike_stats_view(raw):
+    """the ZERNIKE_STATS_DTYPE array [..] of the raw uint8 records [.., 56] focus_zernike returns
+    with ``on_device`` (copied to the host)"""
+    a = np.ascontiguousarray(raw.cpu().numpy() if hasattr(raw, 'cpu') else raw)
+    return a.view(ZERNIKE_STATS_DTYPE).reshape(a.shape[:-1])
+
+
 class FocusRows:
     """the per-ray rows of a through-focus launch on the device: ``rows`` [K, 3, R] (x abr,
     y abr, OPD in system units; rays that fail keep NaN) and ``status`` [R] -- of a batched
@@ -1049,6 +1063,60 @@ class TraceEngine:
                                          f.ctypes.data if f is not None else None, p_eer, p_nok,
                                          self._stream()), 'rox_focus_ee')
         return counts, eer, n_ok
+
+    @_in_flight
+    def focus_zernike(self, focus_rows, grids, terms, wave_scale, circle=None, on_device=False):
+        """rox_focus_zernike over the rows of a through-focus launch (``focus_rows``: the
+        FocusRows trace_pupil_grid_focus / trace_pupil_grids_focus return, still in HBM): the
+        least-squares Zernike coefficients, in waves, of the OPD ``wave_scale[i] * OPD`` of every
+        plane.  ``grids``: one abi.Grid (PRODUCT, whole) per item, or one for all; ``terms``:
+        (n, m, scale) triples or abi.ZernikeTerm; ``wave_scale`` broadcast to [n_items];
+        ``circle`` broadcast to [n_items, 3] (cx, cy, radius) in pupil coordinates, None = the
+        unit circle.  Returns ``(coef, stats)``: float64 [n_items, K, J] and a
+        ZERNIKE_STATS_DTYPE array [n_items, K] -- NumPy, or with ``on_device`` a torch tensor in
+        HBM and a torch uint8 tensor [n_items, K, 56] of the raw records (``zernike_stats_view``
+        reads it on the host)."""
+        t = self.torch
+        rows, status = focus_rows.rows, focus_rows.status
+        if rows.dim() == 3:
+            rows, status = rows.unsqueeze(0), status.unsqueeze(0)
+        n_items, K = int(rows.shape[0]), int(rows.shape[1])
+        ld = int(rows.stride(2))
+        if rows.dtype != t.float64 or rows.stride(3) != 1 or rows.stride(1) != 3 * ld or \
+                rows.stride(0) != K * 3 * ld or status.stride(-1) != 1 or \
+                (n_items > 1 and status.stride(0) != ld):
+            raise EngineError('focus_zernike reads the [n_items][K][3][ld] rows and [n_items][ld] '
+                              'status of a through-focus launch')
+        if isinstance(grids, abi.Grid):
+            grids = [grids] * n_items
+        grids = list(grids)
+        if len(grids) == 1:
+            grids = grids * n_items
+        if len(grids) != n_items:
+            raise EngineError(f'focus_zernike: {len(grids)} grids for {n_items} items')
+        tl = [tm if isinstance(tm, abi.ZernikeTerm) else
+              abi.ZernikeTerm(int(tm[0]), int(tm[1]), float(tm[2]) if len(tm) > 2 else 1.0)
+              for tm in terms]
+        J = len(tl)
+        g_arr = (abi.Grid * max(n_items, 1))(*grids)
+        z_arr = (abi.ZernikeTerm * max(J, 1))(*tl)
+        ws = np.ascontiguousarray(np.broadcast_to(np.asarray(wave_scale, dtype=np.float64), (n_items,)))
+        c = None
+        if circle is not None:
+            c = np.ascontiguousarray(np.broadcast_to(np.asarray(circle, dtype=np.float64), (n_items, 3)))
+        if on_device:
+            coef = t.empty((n_items, K, J), dtype=t.float64, device=self.device)
+            stats = t.empty((n_items, K, C.sizeof(abi.ZernikeStats)), dtype=t.uint8, device=self.device)
+            p_coef, p_stats = coef.data_ptr(), stats.data_ptr()
+        else:
+            coef = np.empty((n_items, K, J), dtype=np.float64)
+            stats = np.empty((n_items, K), dtype=ZERNIKE_STATS_DTYPE)
+            p_coef, p_stats = coef.ctypes.data, stats.ctypes.data
+        with t.cuda.device(self.device):
+            _check(self.lib.rox_focus_zernike(n_items, K, rows.data_ptr(), ld, status.data_ptr(), g_arr,
+                                              c.ctypes.data if c is not None else None, ws.ctypes.data, J,
+                                              z_arr, p_coef, p_stats, self._stream()), 'rox_focus_zernike')
+        return coef, stats
 
     @_in_flight
     def focus_psf_ee(self, psf, pitch, centers, radii, want_centroid=True):
