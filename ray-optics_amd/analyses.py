@@ -961,6 +961,17 @@ def _map_items(opt_model, flds, wvls, focs, xy, num_rays, kwargs, radii=None):
     return eng, fs, wis, grids, opts_list, planes
 
 
+def _wave_scales(opt_model, wvls, n_items):
+    """[n_items] 1 / wavelength in system units of each (field, wavelength) item: OPD -> waves"""
+    W = len(wvls)
+    return np.array([1 / opt_model.nm_to_sys_units(wvls[i % W]) for i in range(n_items)])
+
+
+def _image_pts(planes):
+    """[items, K, 2] the image point of every plane of every item"""
+    return np.array([[(p.image_pt[0], p.image_pt[1]) for p in ps] for ps in planes])
+
+
 def through_focus_map(opt_model, focs, flds=None, wvls=None, num_rays=21, xy=None, field_wts=None,
                       spectral_wts=None, ref_wvl=None, rows=False, **kwargs):
     """Through-focus scans of every field at every wavelength in ONE device call
@@ -980,14 +991,15 @@ def through_focus_map(opt_model, focs, flds=None, wvls=None, num_rays=21, xy=Non
     out = eng.trace_pupil_grids_focus(fs, wis, grids, opts_list, planes, want_rows=rows)
     stats, dev_rows = out if rows else (out, None)
     stats = np.stack([_stats_in_waves(stats[i], opt_model, wvls[i % W]) for i in range(F * W)])
-    image_pts = np.array([[(p.image_pt[0], p.image_pt[1]) for p in ps] for ps in planes])
+    image_pts = _image_pts(planes)
     host_rows = status = None
     if dev_rows is not None:
         R = grid_rays(grids[0])
         host_rows, status = dev_rows.to_host()
         host_rows = np.array(host_rows[:, :, :, :R])
+        scale = _wave_scales(opt_model, wvls, F * W)
         for i in range(F * W):
-            host_rows[i, :, 2] = (1 / opt_model.nm_to_sys_units(wvls[i % W])) * host_rows[i, :, 2]
+            host_rows[i, :, 2] = scale[i] * host_rows[i, :, 2]
         host_rows = host_rows.reshape(F, W, K, 3, R)
         status = np.asarray(status)[:, :R].reshape(F, W, R)
     return ThroughFocusMap(focs, wvls, field_wts, spectral_wts, ref_wvl, stats.reshape(F, W, K),
@@ -1007,6 +1019,26 @@ def _check_freqs(freqs, what):
     if not (np.isfinite(nu).all() and (nu >= 0).all()):
         raise ValueError(f'{what}: frequencies must be finite and >= 0, got {nu}')
     return nu
+
+
+def _given_pitch(pitch, shape, what):
+    """a given pixel pitch as float64 broadcast to shape, checked (None stays None)"""
+    if pitch is None:
+        return None
+    pitch = np.array(np.broadcast_to(np.asarray(pitch, dtype=np.float64), shape))
+    if not (np.isfinite(pitch).all() and (pitch > 0).all()):
+        raise ValueError(f'{what}: pitch must be finite and > 0')
+    return pitch
+
+
+def _default_pitch(opt_model, wvls, num_rays, maxdim, radii, shape, what):
+    """[F, W, K] calc_psf_scaling's delta_xp of every plane, radii[i] being item i's reference
+    sphere radii"""
+    W = len(wvls)
+    scal = [[psf_scaling(opt_model, wvls[i % W], num_rays, maxdim, r) for r in rs] for i, rs in enumerate(radii)]
+    if any(x is None for xs in scal for x in xs):
+        raise ValueError(f'{what}: the model has no paraxial data for calc_psf_scaling: pass pitch [F, W, K]')
+    return np.array([[x[1] for x in xs] for xs in scal], dtype=np.float64).reshape(shape)
 
 
 def poly_otf_merge(otf, image_pts, spectral_wts, ref_index, freqs):
@@ -1137,22 +1169,16 @@ def through_focus_mtf(opt_model, focs, freqs, flds=None, wvls=None, num_rays=32,
     flds, wvls, field_wts, spectral_wts, ref_wvl = _map_spec(opt_model, flds, wvls, field_wts, spectral_wts,
                                                              ref_wvl, what)
     F, W, K = len(flds), len(wvls), len(focs)
-    if pitch is not None:
-        pitch = np.array(np.broadcast_to(np.asarray(pitch, dtype=np.float64), (F, W, K)))
-        if not (np.isfinite(pitch).all() and (pitch > 0).all()):
-            raise ValueError(f'{what}: pitch must be finite and > 0')
+    pitch = _given_pitch(pitch, (F, W, K), what)
     radii = []
     eng, fs, wis, grids, opts_list, planes = _map_items(opt_model, flds, wvls, focs, None, num_rays, kwargs,
                                                         radii=radii)
     assert grid_rays(grids[0]) == num_rays * num_rays
     if pitch is None:
-        scal = [[psf_scaling(opt_model, wvls[i % W], num_rays, maxdim, r) for r in radii[i]] for i in range(F * W)]
-        if any(s is None for ss in scal for s in ss):
-            raise ValueError(f'{what}: the model has no paraxial data for calc_psf_scaling: pass pitch [F, W, K]')
-        pitch = np.array([[s[1] for s in ss] for ss in scal], dtype=np.float64).reshape(F, W, K)
+        pitch = _default_pitch(opt_model, wvls, num_rays, maxdim, radii, (F, W, K), what)
     _none, dev_rows = eng.trace_pupil_grids_focus(fs, wis, grids, opts_list, planes, want_rows=True,
                                                   want_stats=False)
-    scale = np.array([1 / opt_model.nm_to_sys_units(wvls[i % W]) for i in range(F * W)])
+    scale = _wave_scales(opt_model, wvls, F * W)
     flat_pitch = pitch.reshape(F * W, K)
     per_item = K * maxdim * maxdim * 8
     step = max(1, MTF_PSF_CHUNK_BYTES // per_item)
@@ -1169,7 +1195,7 @@ def through_focus_mtf(opt_model, focs, freqs, flds=None, wvls=None, num_rays=32,
         del dev_psf
     otf = np.concatenate(otf).reshape(F, W, K, 2, nu.size)
     strehl = np.concatenate(strehl).reshape(F, W, K)
-    image_pts = np.array([[(p.image_pt[0], p.image_pt[1]) for p in ps] for ps in planes]).reshape(F, W, K, 2)
+    image_pts = _image_pts(planes).reshape(F, W, K, 2)
     out_psf = None
     if psf:
         if on_device:
@@ -1350,15 +1376,13 @@ def through_focus_ee(opt_model, focs, fractions=(0.5, 0.8), radii=None, kind='ge
                                                              ref_wvl, what)
     F, W, K = len(flds), len(wvls), len(focs)
     s = np.asarray(spectral_wts, dtype=np.float64)
-    if kind == 'diffraction' and pitch is not None:
-        pitch = np.array(np.broadcast_to(np.asarray(pitch, dtype=np.float64), (F, W, K)))
-        if not (np.isfinite(pitch).all() and (pitch > 0).all()):
-            raise ValueError(f'{what}: pitch must be finite and > 0')
+    if kind == 'diffraction':
+        pitch = _given_pitch(pitch, (F, W, K), what)
     ref_radii = []
     eng, fs, wis, grids, opts_list, planes = _map_items(opt_model, flds, wvls, focs, None, num_rays, kwargs,
                                                         radii=ref_radii)
     R = grid_rays(grids[0])
-    image_pts = np.array([[(p.image_pt[0], p.image_pt[1]) for p in ps] for ps in planes]).reshape(F, W, K, 2)
+    image_pts = _image_pts(planes).reshape(F, W, K, 2)
     args = dict(focs=focs, fractions=frac, radii=rad, wvls=wvls, field_wts=field_wts, spectral_wts=spectral_wts,
                 ref_wvl=ref_wvl, kind=kind, image_pts=image_pts)
 
@@ -1398,14 +1422,10 @@ def through_focus_ee(opt_model, focs, fractions=(0.5, 0.8), radii=None, kind='ge
     # diffraction
     assert R == num_rays * num_rays
     if pitch is None:
-        scal = [[psf_scaling(opt_model, wvls[i % W], num_rays, maxdim, r) for r in ref_radii[i]]
-                for i in range(F * W)]
-        if any(x is None for xs in scal for x in xs):
-            raise ValueError(f'{what}: the model has no paraxial data for calc_psf_scaling: pass pitch [F, W, K]')
-        pitch = np.array([[x[1] for x in xs] for xs in scal], dtype=np.float64).reshape(F, W, K)
+        pitch = _default_pitch(opt_model, wvls, num_rays, maxdim, ref_radii, (F, W, K), what)
     _none, dev_rows = eng.trace_pupil_grids_focus(fs, wis, grids, opts_list, planes, want_rows=True,
                                                   want_stats=False)
-    scale = np.array([1 / opt_model.nm_to_sys_units(wvls[i % W]) for i in range(F * W)])
+    scale = _wave_scales(opt_model, wvls, F * W)
     window = pitch * (maxdim / 2)                                                   # [F, W, K]
     item_radii = window[..., None] * np.linspace(0.0, 1.0, n_curve)                 # [F, W, K, n_curve]
     curve_radii = window.min(axis=1)[..., None] * np.linspace(0.0, 1.0, n_curve)   # [F, K, n_curve]
@@ -1575,7 +1595,7 @@ def through_focus_zernike(opt_model, focs, flds=None, wvls=None, num_rays=64, te
     circ = zernike_circles(grids, circle, F * W, what)
     _none, dev_rows = eng.trace_pupil_grids_focus(fs, wis, grids, opts_list, planes, want_rows=True,
                                                   want_stats=False)
-    scale = np.array([1 / opt_model.nm_to_sys_units(wvls[i % W]) for i in range(F * W)])
+    scale = _wave_scales(opt_model, wvls, F * W)
     coef, stats = eng.focus_zernike(dev_rows, grids, tl, scale, circ)
     J = len(tl)
     return ThroughFocusZernike(focs, wvls, field_wts, spectral_wts, ref_wvl, tl,

@@ -506,81 +506,11 @@ __global__ __launch_bounds__(kBlock) void ee_psf_finish(const double *__restrict
 }
 
 // ---- host ---------------------------------------------------------------------------------------
-struct EeWorkspace {
-    char *buf = nullptr;
-    size_t cap = 0;
-    double *h_stage = nullptr;      // pinned staging of the host inputs, reused once ev has passed
-    size_t h_cap = 0;
-    hipEvent_t ev = nullptr;
-};
-rox::PerStream<EeWorkspace> g_ee_ws;
-
-size_t up256(size_t b) { return (b + 255) & ~size_t(255); }
+rox::PerStream<rox::Workspace> g_ee_ws;         // (both entries)
 
 int wgs_for(int64_t work, int64_t per_wg)
 {
     return (int)std::max<int64_t>(1, std::min<int64_t>(kMaxWgPerPlane, (work + per_wg - 1) / per_wg));
-}
-
-// the workspace slot of this (device, stream)
-int take_workspace(hipStream_t st, rox::PerStream<EeWorkspace>::Slot **out)
-{
-    int device = 0;
-    HIP_TRY(hipGetDevice(&device));
-    *out = g_ee_ws.get(device, st);
-    if (!*out)
-        return rox::host_fail(ROX_E_NOMEM, "%sout of host memory", kHipWhere);
-    return 0;
-}
-
-// at least `need` device bytes and `n_stage` pinned doubles, once the previous call's uploads
-// have read the staging
-int prepare(EeWorkspace *ws, size_t need, size_t n_stage)
-{
-    if (ws->cap < need)
-        HIP_TRY(rox::regrow(ws->buf, ws->cap, need, need));
-    if (!ws->ev)
-        HIP_TRY(hipEventCreateWithFlags(&ws->ev, hipEventDisableTiming));
-    else
-        HIP_TRY(hipEventSynchronize(ws->ev));
-    if (ws->h_cap < n_stage)
-        HIP_TRY(rox::regrow(ws->h_stage, ws->h_cap, n_stage, sizeof(double) * n_stage, hipHostMallocDefault));
-    return 0;
-}
-
-bool is_device(const void *p)
-{
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) == hipSuccess)
-        return at.type == hipMemoryTypeDevice;
-    (void)hipGetLastError();
-    return false;
-}
-
-// radii [total][nr]: finite, >= 0, non-decreasing per plane
-int check_radii(const char *e, int64_t total, int32_t nr, const double *radii)
-{
-    for (int64_t z = 0; z < total; ++z)
-        for (int32_t j = 0; j < nr; ++j) {
-            const double r = radii[z * nr + j];
-            if (!(std::isfinite(r) && r >= 0.0))
-                return rox::host_fail(ROX_E_ARG, "%s: radii[%lld] = %g is not finite and >= 0", e,
-                                      (long long)(z * nr + j), r);
-            if (j && r < radii[z * nr + j - 1])
-                return rox::host_fail(ROX_E_ARG, "%s: radii[%lld] = %g decreases within its plane", e,
-                                      (long long)(z * nr + j), r);
-        }
-    return 0;
-}
-
-int check_centers(const char *e, int64_t total, const double *centers)
-{
-    if (centers)
-        for (int64_t i = 0; i < 2 * total; ++i)
-            if (!std::isfinite(centers[i]))
-                return rox::host_fail(ROX_E_ARG, "%s: centers[%lld] = %g is not finite", e, (long long)i,
-                                      centers[i]);
-    return 0;
 }
 
 }  // namespace
@@ -592,19 +522,15 @@ extern "C" int rox_focus_ee(int32_t n_items, int32_t n_planes, const double *row
 {
     static const char kE[] = "rox_focus_ee";
     // every argument check comes before anything touches a device
-    if (n_items < 1 || n_items > ROX_MAX_FOCUS_ITEMS)
-        return rox::host_fail(ROX_E_ARG, "%s: n_items %d outside [1, %d]", kE, n_items, ROX_MAX_FOCUS_ITEMS);
-    if (n_planes < 1 || n_planes > ROX_MAX_FOCUS_PLANES)
-        return rox::host_fail(ROX_E_ARG, "%s: n_planes %d outside [1, %d]", kE, n_planes, ROX_MAX_FOCUS_PLANES);
+    ROX_TRY(rox::check_range(kE, "n_items", n_items, 1, ROX_MAX_FOCUS_ITEMS));
+    ROX_TRY(rox::check_range(kE, "n_planes", n_planes, 1, ROX_MAX_FOCUS_PLANES));
     if (!rows || !status)
         return rox::host_fail(ROX_E_ARG, "%s: null rows or status", kE);
     if (n_rays < 1 || n_rays > ld)
         return rox::host_fail(ROX_E_ARG, "%s: n_rays %lld outside [1, ld = %lld]", kE, (long long)n_rays,
                               (long long)ld);
-    if (n_radii < 0 || n_radii > ROX_MAX_EE_RADII)
-        return rox::host_fail(ROX_E_ARG, "%s: n_radii %d outside [0, %d]", kE, n_radii, ROX_MAX_EE_RADII);
-    if (n_frac < 0 || n_frac > ROX_MAX_EE_FRACTIONS)
-        return rox::host_fail(ROX_E_ARG, "%s: n_frac %d outside [0, %d]", kE, n_frac, ROX_MAX_EE_FRACTIONS);
+    ROX_TRY(rox::check_range(kE, "n_radii", n_radii, 0, ROX_MAX_EE_RADII));
+    ROX_TRY(rox::check_range(kE, "n_frac", n_frac, 0, ROX_MAX_EE_FRACTIONS));
     if (!counts && !ee_radius)
         return rox::host_fail(ROX_E_ARG, "%s: null counts and ee_radius", kE);
     if (counts && (n_radii < 1 || !radii))
@@ -613,51 +539,41 @@ extern "C" int rox_focus_ee(int32_t n_items, int32_t n_planes, const double *row
         return rox::host_fail(ROX_E_ARG, "%s: ee_radius needs n_frac >= 1 and fractions", kE);
     const int64_t total = (int64_t)n_items * n_planes;
     const int nr = counts ? n_radii : 0, nq = ee_radius ? n_frac : 0;
-    if (int rc = check_radii(kE, total, nr, radii))
-        return rc;
+    ROX_TRY(rox::check_radii(kE, total, nr, radii));
     for (int q = 0; q < nq; ++q)
         if (!(fractions[q] > 0.0 && fractions[q] <= 1.0))
             return rox::host_fail(ROX_E_ARG, "%s: fractions[%d] = %g outside (0, 1]", kE, q, fractions[q]);
-    if (int rc = check_centers(kE, total, centers))
-        return rc;
+    ROX_TRY(rox::check_centers(kE, total, centers));
 
     hipStream_t st = (hipStream_t)stream;
-    rox::PerStream<EeWorkspace>::Slot *slot = nullptr;
-    if (int rc = take_workspace(st, &slot))
-        return rc;
+    rox::PerStream<rox::Workspace>::Slot *slot;
+    ROX_TRY(g_ee_ws.take(st, kHipWhere, &slot));
     std::lock_guard<std::mutex> turn(slot->mu);
-    EeWorkspace *ws = &slot->data;
+    rox::Workspace *ws = &slot->data;
 
     const int nwg = wgs_for(n_rays, kRaysPerWg);
     const int ngroups = (nq + kQGroup - 1) / kQGroup;
     const size_t per_plane = sizeof(uint32_t) * (size_t)nwg * (nr + 1) + sizeof(uint32_t) * (size_t)nwg * nq * kDigits +
                              sizeof(SelState) * nq + sizeof(double) * (nr + 2 + nq) + sizeof(int64_t) * (nr + 1);
-    const int64_t chunk = std::max<int64_t>(
-        1, std::min<int64_t>({total, (int64_t)(kEeScratchBytes / per_plane), 65535}));
-    const size_t b_frac = up256(sizeof(double) * (size_t)std::max(nq, 1));
-    const size_t b_r2 = up256(sizeof(double) * (size_t)nr * chunk), b_cen = up256(sizeof(double) * 2 * chunk);
-    const size_t b_cpart = up256(sizeof(uint32_t) * (size_t)nwg * (nr + 1) * chunk);
-    const size_t b_spart = up256(sizeof(uint32_t) * (size_t)nwg * nq * kDigits * chunk);
-    const size_t b_state = up256(sizeof(SelState) * (size_t)nq * chunk);
-    const size_t b_counts = up256(sizeof(int64_t) * (size_t)nr * chunk), b_nok = up256(sizeof(int64_t) * chunk);
-    const size_t b_rad = up256(sizeof(double) * (size_t)nq * chunk);
-    const size_t need = b_frac + b_r2 + b_cen + b_cpart + b_spart + b_state + b_counts + b_nok + b_rad;
-    // staging: [fractions nq][r^2 total * nr][centers total * 2]
-    const size_t n_stage = (size_t)nq + (size_t)total * nr + 2 * (size_t)total;
-    if (int rc = prepare(ws, need, n_stage))
-        return rc;
-    char *p = ws->buf;
-    double *d_frac = (double *)p;       p += b_frac;
-    double *d_r2 = (double *)p;         p += b_r2;
-    double *d_cen = (double *)p;        p += b_cen;
-    uint32_t *cpart = (uint32_t *)p;    p += b_cpart;
-    uint32_t *spart = (uint32_t *)p;    p += b_spart;
-    SelState *state = (SelState *)p;    p += b_state;
-    int64_t *d_counts = (int64_t *)p;   p += b_counts;
-    int64_t *d_nok = (int64_t *)p;      p += b_nok;
-    double *d_rad = (double *)p;
+    const int64_t chunk = rox::chunk_for(total, per_plane, kEeScratchBytes);
+    double *d_frac, *d_r2, *d_cen, *d_rad;
+    uint32_t *cpart, *spart;
+    SelState *state;
+    int64_t *d_counts, *d_nok;
+    rox::Layout L;
+    L.add(d_frac, rox::up256(sizeof(double) * (size_t)std::max(nq, 1)));
+    L.add(d_r2, rox::up256(sizeof(double) * (size_t)nr * chunk)).add(d_cen, rox::up256(sizeof(double) * 2 * chunk));
+    L.add(cpart, rox::up256(sizeof(uint32_t) * (size_t)nwg * (nr + 1) * chunk));
+    L.add(spart, rox::up256(sizeof(uint32_t) * (size_t)nwg * nq * kDigits * chunk));
+    L.add(state, rox::up256(sizeof(SelState) * (size_t)nq * chunk));
+    L.add(d_counts, rox::up256(sizeof(int64_t) * (size_t)nr * chunk)).add(d_nok, rox::up256(sizeof(int64_t) * chunk));
+    L.add(d_rad, rox::up256(sizeof(double) * (size_t)nq * chunk));
+    HIP_TRY(ws->reserve(L.size()));
+    L.carve(ws->buf);
+    // staging: [fractions nq][r^2 total * nr][centers total * 2], read by every chunk's uploads
+    HIP_TRY(ws->stage.acquire(sizeof(double) * ((size_t)nq + (size_t)total * nr + 2 * (size_t)total)));
 
-    double *h_frac = ws->h_stage, *h_r2 = h_frac + nq, *h_cen = h_r2 + (size_t)total * nr;
+    double *h_frac = (double *)ws->stage.h, *h_r2 = h_frac + nq, *h_cen = h_r2 + (size_t)total * nr;
     for (int q = 0; q < nq; ++q)
         h_frac[q] = fractions[q];
     for (int64_t i = 0; i < total * nr; ++i)
@@ -667,8 +583,8 @@ extern "C" int rox_focus_ee(int32_t n_items, int32_t n_planes, const double *row
     if (nq)
         HIP_TRY(hipMemcpyAsync(d_frac, h_frac, sizeof(double) * nq, hipMemcpyHostToDevice, st));
 
-    const bool host_dst = (counts && !is_device(counts)) || (ee_radius && !is_device(ee_radius)) ||
-                          (n_ok && !is_device(n_ok));
+    const bool host_dst = (counts && !rox::is_device(counts)) || (ee_radius && !rox::is_device(ee_radius)) ||
+                          (n_ok && !rox::is_device(n_ok));
     for (int64_t z0 = 0; z0 < total; z0 += chunk) {
         const int64_t c = std::min(chunk, total - z0);
         if (nr)
@@ -702,7 +618,7 @@ extern "C" int rox_focus_ee(int32_t n_items, int32_t n_planes, const double *row
         if (n_ok)
             HIP_TRY(hipMemcpyAsync(n_ok + z0, d_nok, sizeof(int64_t) * c, hipMemcpyDefault, st));
     }
-    HIP_TRY(hipEventRecord(ws->ev, st));
+    HIP_TRY(ws->stage.record(st));
     if (host_dst)
         HIP_TRY(hipStreamSynchronize(st));
     return 0;
@@ -713,65 +629,47 @@ extern "C" int rox_focus_psf_ee(int32_t n_items, int32_t n_planes, const double 
                                 double *ee, double *centroid, void *stream)
 {
     static const char kE[] = "rox_focus_psf_ee";
-    if (n_items < 1 || n_items > ROX_MAX_FOCUS_ITEMS)
-        return rox::host_fail(ROX_E_ARG, "%s: n_items %d outside [1, %d]", kE, n_items, ROX_MAX_FOCUS_ITEMS);
-    if (n_planes < 1 || n_planes > ROX_MAX_FOCUS_PLANES)
-        return rox::host_fail(ROX_E_ARG, "%s: n_planes %d outside [1, %d]", kE, n_planes, ROX_MAX_FOCUS_PLANES);
-    if (maxdim < 2 || maxdim > 32768)
-        return rox::host_fail(ROX_E_ARG, "%s: maxdim %d outside [2, 32768]", kE, maxdim);
-    if (n_radii < 1 || n_radii > ROX_MAX_EE_RADII)
-        return rox::host_fail(ROX_E_ARG, "%s: n_radii %d outside [1, %d]", kE, n_radii, ROX_MAX_EE_RADII);
+    ROX_TRY(rox::check_range(kE, "n_items", n_items, 1, ROX_MAX_FOCUS_ITEMS));
+    ROX_TRY(rox::check_range(kE, "n_planes", n_planes, 1, ROX_MAX_FOCUS_PLANES));
+    ROX_TRY(rox::check_range(kE, "maxdim", maxdim, 2, 32768));
+    ROX_TRY(rox::check_range(kE, "n_radii", n_radii, 1, ROX_MAX_EE_RADII));
     if (!psf || !pitch || !radii || !ee)
         return rox::host_fail(ROX_E_ARG, "%s: null psf, pitch, radii or ee", kE);
     const int64_t total = (int64_t)n_items * n_planes;
-    for (int64_t i = 0; i < total; ++i)
-        if (!(std::isfinite(pitch[i]) && pitch[i] > 0.0))
-            return rox::host_fail(ROX_E_ARG, "%s: pitch[%lld] = %g is not finite and > 0", kE, (long long)i,
-                                  pitch[i]);
-    if (int rc = check_radii(kE, total, n_radii, radii))
-        return rc;
-    if (int rc = check_centers(kE, total, centers))
-        return rc;
+    ROX_TRY(rox::check_pitch(kE, total, pitch));
+    ROX_TRY(rox::check_radii(kE, total, n_radii, radii));
+    ROX_TRY(rox::check_centers(kE, total, centers));
 
     hipStream_t st = (hipStream_t)stream;
-    rox::PerStream<EeWorkspace>::Slot *slot = nullptr;
-    if (int rc = take_workspace(st, &slot))
-        return rc;
+    rox::PerStream<rox::Workspace>::Slot *slot;
+    ROX_TRY(g_ee_ws.take(st, kHipWhere, &slot));
     std::lock_guard<std::mutex> turn(slot->mu);
-    EeWorkspace *ws = &slot->data;
+    rox::Workspace *ws = &slot->data;
 
     const int M = maxdim, nr = n_radii;
     const int nwg = wgs_for(M, 4 * kWaves);              // at least 4 rows per wave
     const size_t per_plane = sizeof(double) * ((size_t)nwg * (nr + 1) + (size_t)nwg * 3 + 2 * (size_t)nr + 6);
-    const int64_t chunk = std::max<int64_t>(
-        1, std::min<int64_t>({total, (int64_t)(kEeScratchBytes / per_plane), 65535}));
-    const size_t b_r2 = up256(sizeof(double) * (size_t)nr * chunk), b_pitch = up256(sizeof(double) * chunk);
-    const size_t b_two = up256(sizeof(double) * 2 * chunk);
-    const size_t b_part = up256(sizeof(double) * (size_t)nwg * (nr + 1) * chunk);
-    const size_t b_mom = up256(sizeof(double) * 3 * (size_t)nwg * chunk);
-    const size_t b_ee = up256(sizeof(double) * (size_t)nr * chunk);
-    const size_t need = b_r2 + b_pitch + 2 * b_two + b_part + b_mom + b_ee;
-    // staging: [r^2 total * nr][pitch total][centers total * 2]
-    const size_t n_stage = (size_t)total * nr + (size_t)total + 2 * (size_t)total;
-    if (int rc = prepare(ws, need, n_stage))
-        return rc;
-    char *p = ws->buf;
-    double *d_r2 = (double *)p;         p += b_r2;
-    double *d_pitch = (double *)p;      p += b_pitch;
-    double *d_center = (double *)p;     p += b_two;
-    double *d_centroid = (double *)p;   p += b_two;
-    double *part = (double *)p;         p += b_part;
-    double *mom = (double *)p;          p += b_mom;
-    double *d_ee = (double *)p;
+    const int64_t chunk = rox::chunk_for(total, per_plane, kEeScratchBytes);
+    double *d_r2, *d_pitch, *d_center, *d_centroid, *part, *mom, *d_ee;
+    rox::Layout L;
+    L.add(d_r2, rox::up256(sizeof(double) * (size_t)nr * chunk)).add(d_pitch, rox::up256(sizeof(double) * chunk));
+    L.add(d_center, rox::up256(sizeof(double) * 2 * chunk)).add(d_centroid, rox::up256(sizeof(double) * 2 * chunk));
+    L.add(part, rox::up256(sizeof(double) * (size_t)nwg * (nr + 1) * chunk));
+    L.add(mom, rox::up256(sizeof(double) * 3 * (size_t)nwg * chunk));
+    L.add(d_ee, rox::up256(sizeof(double) * (size_t)nr * chunk));
+    HIP_TRY(ws->reserve(L.size()));
+    L.carve(ws->buf);
+    // staging: [r^2 total * nr][pitch total][centers total * 2], read by every chunk's uploads
+    HIP_TRY(ws->stage.acquire(sizeof(double) * ((size_t)total * nr + (size_t)total + 2 * (size_t)total)));
 
-    double *h_r2 = ws->h_stage, *h_pitch = h_r2 + (size_t)total * nr, *h_cen = h_pitch + total;
+    double *h_r2 = (double *)ws->stage.h, *h_pitch = h_r2 + (size_t)total * nr, *h_cen = h_pitch + total;
     for (int64_t i = 0; i < total * nr; ++i)
         h_r2[i] = radii[i] * radii[i];                   // one IEEE product
     memcpy(h_pitch, pitch, sizeof(double) * (size_t)total);
     if (centers)
         memcpy(h_cen, centers, sizeof(double) * 2 * (size_t)total);
 
-    const bool host_dst = !is_device(ee) || (centroid && !is_device(centroid));
+    const bool host_dst = !rox::is_device(ee) || (centroid && !rox::is_device(centroid));
     const PsfArgs base{psf, M, nwg};
     for (int64_t z0 = 0; z0 < total; z0 += chunk) {
         const int64_t c = std::min(chunk, total - z0);
@@ -795,7 +693,7 @@ extern "C" int rox_focus_psf_ee(int32_t n_items, int32_t n_planes, const double 
         if (centroid)
             HIP_TRY(hipMemcpyAsync(centroid + 2 * z0, d_centroid, sizeof(double) * 2 * c, hipMemcpyDefault, st));
     }
-    HIP_TRY(hipEventRecord(ws->ev, st));
+    HIP_TRY(ws->stage.record(st));
     if (host_dst)
         HIP_TRY(hipStreamSynchronize(st));
     return 0;

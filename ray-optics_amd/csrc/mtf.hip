@@ -155,16 +155,9 @@ __global__ __launch_bounds__(kBlock) void mtf_dtft(const double *__restrict__ ls
     out[1] = (-(d == 0 ? kSignX : kSignY) * im) / nrm + 0.0;
 }
 
-// grow-only workspace per (device, stream):
+// workspace per (device, stream):
 //   [pitch P][freqs Q][row partials][column partials][projections][host-destination staging]
-struct MtfWorkspace {
-    char *buf = nullptr;
-    size_t cap = 0;
-    double *h_stage = nullptr;      // pinned staging of pitch and freqs, reused once ev has passed
-    size_t h_cap = 0;
-    hipEvent_t ev = nullptr;
-};
-rox::PerStream<MtfWorkspace> g_mtf_ws;
+rox::PerStream<rox::Workspace> g_mtf_ws;
 
 }  // namespace
 
@@ -174,77 +167,48 @@ extern "C" int rox_focus_mtf(int32_t n_items, int32_t n_planes, const double *ps
 {
     static const char kE[] = "rox_focus_mtf";
     // every argument check comes before anything touches a device
-    if (n_items < 1 || n_items > ROX_MAX_FOCUS_ITEMS)
-        return rox::host_fail(ROX_E_ARG, "%s: n_items %d outside [1, %d]", kE, n_items, ROX_MAX_FOCUS_ITEMS);
-    if (n_planes < 1 || n_planes > ROX_MAX_FOCUS_PLANES)
-        return rox::host_fail(ROX_E_ARG, "%s: n_planes %d outside [1, %d]", kE, n_planes, ROX_MAX_FOCUS_PLANES);
-    if (maxdim < 2 || maxdim > 32768)
-        return rox::host_fail(ROX_E_ARG, "%s: maxdim %d outside [2, 32768]", kE, maxdim);
-    if (n_freq < 1 || n_freq > ROX_MAX_MTF_FREQS)
-        return rox::host_fail(ROX_E_ARG, "%s: n_freq %d outside [1, %d]", kE, n_freq, ROX_MAX_MTF_FREQS);
+    ROX_TRY(rox::check_range(kE, "n_items", n_items, 1, ROX_MAX_FOCUS_ITEMS));
+    ROX_TRY(rox::check_range(kE, "n_planes", n_planes, 1, ROX_MAX_FOCUS_PLANES));
+    ROX_TRY(rox::check_range(kE, "maxdim", maxdim, 2, 32768));
+    ROX_TRY(rox::check_range(kE, "n_freq", n_freq, 1, ROX_MAX_MTF_FREQS));
     if (!psf || !pitch || !freqs || !otf)
         return rox::host_fail(ROX_E_ARG, "%s: null psf, pitch, freqs or otf", kE);
     const int64_t total = (int64_t)n_items * n_planes;
-    for (int64_t i = 0; i < total; ++i)
-        if (!(std::isfinite(pitch[i]) && pitch[i] > 0.0))
-            return rox::host_fail(ROX_E_ARG, "%s: pitch[%lld] = %g is not finite and > 0", kE, (long long)i,
-                                  pitch[i]);
+    ROX_TRY(rox::check_pitch(kE, total, pitch));
     for (int32_t q = 0; q < n_freq; ++q)
         if (!(std::isfinite(freqs[q]) && freqs[q] >= 0.0))
             return rox::host_fail(ROX_E_ARG, "%s: freqs[%d] = %g is not finite and >= 0", kE, q, freqs[q]);
 
     hipStream_t st = (hipStream_t)stream;
-    int device = 0;
-    HIP_TRY(hipGetDevice(&device));
-    auto *slot = g_mtf_ws.get(device, st);
-    if (!slot)
-        return rox::host_fail(ROX_E_NOMEM, "%s: out of host memory", kE);
+    rox::PerStream<rox::Workspace>::Slot *slot;
+    ROX_TRY(g_mtf_ws.take(st, kHipWhere, &slot));
     std::lock_guard<std::mutex> turn(slot->mu);
-    MtfWorkspace *ws = &slot->data;
+    rox::Workspace *ws = &slot->data;
 
-    bool dev_dst = false;
-    {
-        hipPointerAttribute_t at;
-        if (hipPointerGetAttributes(&at, otf) == hipSuccess)
-            dev_dst = at.type == hipMemoryTypeDevice;
-        else
-            (void)hipGetLastError();
-    }
+    const bool dev_dst = rox::is_device(otf);
     const int M = maxdim, Q = n_freq;
     const int nt = (M + kTile - 1) / kTile;
     const int64_t otf_el = (int64_t)2 * Q * 2;                  // doubles of one plane's result
-    auto up256 = [](size_t b) { return (b + 255) & ~size_t(255); };
     const size_t per_plane = sizeof(double) * ((size_t)2 * nt * M + 2 * (size_t)M + (dev_dst ? 0 : otf_el));
-    const int64_t chunk = std::max<int64_t>(
-        1, std::min<int64_t>({total, (int64_t)(kMtfScratchBytes / per_plane), 65535}));
-    const size_t b_pitch = up256(sizeof(double) * (size_t)total), b_freq = up256(sizeof(double) * (size_t)Q);
-    const size_t b_part = up256(sizeof(double) * (size_t)nt * M * chunk);
-    const size_t b_lsf = up256(sizeof(double) * 2 * (size_t)M * chunk);
-    const size_t b_out = dev_dst ? 0 : sizeof(double) * (size_t)otf_el * chunk;
-    const size_t need = b_pitch + b_freq + 2 * b_part + b_lsf + b_out;
-    if (ws->cap < need)
-        HIP_TRY(rox::regrow(ws->buf, ws->cap, need, need));
-    char *p = ws->buf;
-    double *d_pitch = (double *)p;      p += b_pitch;
-    double *d_freq = (double *)p;       p += b_freq;
-    double *rowpart = (double *)p;      p += b_part;
-    double *colpart = (double *)p;      p += b_part;
-    double *lsf = (double *)p;          p += b_lsf;
-    double *scratch_otf = (double *)p;
+    const int64_t chunk = rox::chunk_for(total, per_plane, kMtfScratchBytes);
+    double *d_pitch, *d_freq, *rowpart, *colpart, *lsf, *scratch_otf;
+    rox::Layout L;
+    L.add(d_pitch, rox::up256(sizeof(double) * (size_t)total)).add(d_freq, rox::up256(sizeof(double) * (size_t)Q));
+    L.add(rowpart, rox::up256(sizeof(double) * (size_t)nt * M * chunk));
+    L.add(colpart, rox::up256(sizeof(double) * (size_t)nt * M * chunk));
+    L.add(lsf, rox::up256(sizeof(double) * 2 * (size_t)M * chunk));
+    L.add(scratch_otf, dev_dst ? 0 : sizeof(double) * (size_t)otf_el * chunk);
+    HIP_TRY(ws->reserve(L.size()));
+    L.carve(ws->buf);
 
     // pitch and freqs -> pinned block (once the previous call's copy has read it) -> device
-    if (!ws->ev)
-        HIP_TRY(hipEventCreateWithFlags(&ws->ev, hipEventDisableTiming));
-    else
-        HIP_TRY(hipEventSynchronize(ws->ev));
-    const size_t n_stage = (size_t)total + (size_t)Q;
-    if (ws->h_cap < n_stage)
-        HIP_TRY(rox::regrow(ws->h_stage, ws->h_cap, n_stage, sizeof(double) * n_stage, hipHostMallocDefault));
-    memcpy(ws->h_stage, pitch, sizeof(double) * (size_t)total);
-    memcpy(ws->h_stage + total, freqs, sizeof(double) * (size_t)Q);
-    HIP_TRY(hipMemcpyAsync(d_pitch, ws->h_stage, sizeof(double) * (size_t)total, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_freq, ws->h_stage + total, sizeof(double) * (size_t)Q, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipEventRecord(ws->ev, st));
+    HIP_TRY(ws->stage.acquire(sizeof(double) * ((size_t)total + (size_t)Q)));
+    double *h_stage = (double *)ws->stage.h;
+    memcpy(h_stage, pitch, sizeof(double) * (size_t)total);
+    memcpy(h_stage + total, freqs, sizeof(double) * (size_t)Q);
+    HIP_TRY(hipMemcpyAsync(d_pitch, h_stage, sizeof(double) * (size_t)total, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_freq, h_stage + total, sizeof(double) * (size_t)Q, hipMemcpyHostToDevice, st));
+    HIP_TRY(ws->stage.record(st));
 
     for (int64_t p0 = 0; p0 < total; p0 += chunk) {
         const int64_t c = std::min(chunk, total - p0);

@@ -481,14 +481,9 @@ constexpr size_t kFocusPsfScratchBytes = size_t(256) << 20;
 // F and the plane blocks are zero-padded to the GEMM tiles, so they sit at offsets that depend
 // on the shape alone; the per-call region behind them may overwrite plane blocks a later, larger
 // call then zeroes again (`clean` counts the plane blocks known to be zero-padded).
-struct FocusWorkspace {
-    char *buf = nullptr;
-    size_t cap = 0;
+struct FocusWorkspace : rox::Workspace {
     int64_t shape[2] = {0, 0};      // (n, M) F was formed for
     int64_t clean = 0;
-    double *h_scale = nullptr;      // pinned staging of wave_scale, reused once ev has passed
-    size_t h_cap = 0;
-    hipEvent_t ev = nullptr;
 };
 rox::PerStream<FocusWorkspace> g_focus_ws;
 
@@ -501,10 +496,8 @@ extern "C" int rox_focus_psf(int32_t n_items, int32_t n_planes, const double *ro
     static const char kE[] = "rox_focus_psf";
     const char *const kHipWhere = kFocusWhere;
     // every argument check comes before anything touches a device
-    if (n_items < 1 || n_items > ROX_MAX_FOCUS_ITEMS)
-        return rox::host_fail(ROX_E_ARG, "%s: n_items %d outside [1, %d]", kE, n_items, ROX_MAX_FOCUS_ITEMS);
-    if (n_planes < 1 || n_planes > ROX_MAX_FOCUS_PLANES)
-        return rox::host_fail(ROX_E_ARG, "%s: n_planes %d outside [1, %d]", kE, n_planes, ROX_MAX_FOCUS_PLANES);
+    ROX_TRY(rox::check_range(kE, "n_items", n_items, 1, ROX_MAX_FOCUS_ITEMS));
+    ROX_TRY(rox::check_range(kE, "n_planes", n_planes, 1, ROX_MAX_FOCUS_PLANES));
     if (ndim < 2 || (ndim & 1))
         return rox::host_fail(ROX_E_ARG, "%s: ndim %d must be even and >= 2", kE, ndim);
     const int n = ndim, M = maxdim;
@@ -524,11 +517,8 @@ extern "C" int rox_focus_psf(int32_t n_items, int32_t n_planes, const double *ro
         return rox::host_fail(ROX_E_ARG, "%s: psf and stats are both null", kE);
 
     hipStream_t st = (hipStream_t)stream;
-    int device = 0;
-    HIP_TRY(hipGetDevice(&device));
-    auto *slot = g_focus_ws.get(device, st);
-    if (!slot)
-        return rox::host_fail(ROX_E_NOMEM, "%s: out of host memory", kE);
+    rox::PerStream<FocusWorkspace>::Slot *slot;
+    ROX_TRY(g_focus_ws.take(st, kHipWhere, &slot));
     std::lock_guard<std::mutex> turn(slot->mu);
     FocusWorkspace *ws = &slot->data;
 
@@ -539,31 +529,26 @@ extern "C" int rox_focus_psf(int32_t n_items, int32_t n_planes, const double *ro
     const int64_t psf_el = (int64_t)M * M;
     const int64_t nblk = ((int64_t)n * n + kFocusBlock - 1) / kFocusBlock;
     const int64_t total = (int64_t)n_items * n_planes;
-    auto up256 = [](size_t b) { return (b + 255) & ~size_t(255); };
     const size_t per_plane = sizeof(double) * (size_t)(blk_el + (psf ? 0 : psf_el) + 3 * nblk) + 8;
-    const int64_t chunk = std::max<int64_t>(
-        1, std::min<int64_t>({total, (int64_t)(kFocusPsfScratchBytes / per_plane), 65535}));
+    const int64_t chunk = rox::chunk_for(total, per_plane, kFocusPsfScratchBytes);
+    double *fr, *blocks, *partial, *d_scale, *scratch_psf;
+    unsigned long long *maxbits;
+    rox_focus_psf_stats *d_stats;
     const size_t b_f = sizeof(double) * 2 * (size_t)f_el;
-    const size_t b_blocks = sizeof(double) * (size_t)blk_el * chunk;
-    const size_t b_max = up256(sizeof(unsigned long long) * chunk);
-    const size_t b_part = up256(sizeof(double) * 3 * (size_t)nblk * chunk);
-    const size_t b_stats = up256(sizeof(rox_focus_psf_stats) * (size_t)total);
-    const size_t b_scale = up256(sizeof(double) * (size_t)n_items);
-    const size_t b_psf = psf ? 0 : sizeof(double) * (size_t)psf_el * chunk;
-    const size_t need = b_f + b_blocks + b_max + b_part + b_stats + b_scale + b_psf;
-    if (ws->cap < need) {
-        HIP_TRY(rox::regrow(ws->buf, ws->cap, need, need));
+    rox::Layout L;
+    L.add(fr, b_f).add(blocks, sizeof(double) * (size_t)blk_el * chunk);
+    L.add(maxbits, rox::up256(sizeof(unsigned long long) * chunk));
+    L.add(partial, rox::up256(sizeof(double) * 3 * (size_t)nblk * chunk));
+    L.add(d_stats, rox::up256(sizeof(rox_focus_psf_stats) * (size_t)total));
+    L.add(d_scale, rox::up256(sizeof(double) * (size_t)n_items));
+    L.add(scratch_psf, psf ? 0 : sizeof(double) * (size_t)psf_el * chunk);
+    if (ws->cap < L.size()) {
+        HIP_TRY(rox::regrow(ws->buf, ws->cap, L.size(), L.size()));
         ws->shape[0] = ws->shape[1] = 0;
         ws->clean = 0;
     }
-    double *fr = (double *)ws->buf, *fi = fr + f_el;
-    double *blocks = fr + 2 * f_el;
-    char *p = ws->buf + b_f + b_blocks;
-    unsigned long long *maxbits = (unsigned long long *)p;  p += b_max;
-    double *partial = (double *)p;                          p += b_part;
-    rox_focus_psf_stats *d_stats = (rox_focus_psf_stats *)p; p += b_stats;
-    double *d_scale = (double *)p;                          p += b_scale;
-    double *scratch_psf = (double *)p;
+    L.carve(ws->buf);
+    double *fi = fr + f_el;
 
     // F (and zeroed plane blocks) for this shape; plane blocks beyond `clean` are zeroed first
     const bool new_shape = ws->shape[0] != n || ws->shape[1] != M;
@@ -585,25 +570,13 @@ extern "C" int rox_focus_psf(int32_t n_items, int32_t n_planes, const double *ro
     }
 
     // wave_scale -> pinned block (once the previous call's copy has read it) -> device
-    if (!ws->ev)
-        HIP_TRY(hipEventCreateWithFlags(&ws->ev, hipEventDisableTiming));
-    else
-        HIP_TRY(hipEventSynchronize(ws->ev));
-    if (ws->h_cap < (size_t)n_items)
-        HIP_TRY(rox::regrow(ws->h_scale, ws->h_cap, (size_t)n_items, sizeof(double) * (size_t)n_items,
-                            hipHostMallocDefault));
-    memcpy(ws->h_scale, wave_scale, sizeof(double) * (size_t)n_items);
-    HIP_TRY(hipMemcpyAsync(d_scale, ws->h_scale, sizeof(double) * (size_t)n_items, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipEventRecord(ws->ev, st));
+    const size_t b_scale = sizeof(double) * (size_t)n_items;
+    HIP_TRY(ws->stage.acquire(b_scale));
+    memcpy(ws->stage.h, wave_scale, b_scale);
+    HIP_TRY(hipMemcpyAsync(d_scale, ws->stage.h, b_scale, hipMemcpyHostToDevice, st));
+    HIP_TRY(ws->stage.record(st));
 
-    bool dev_dst = false;
-    if (stats) {
-        hipPointerAttribute_t at;
-        if (hipPointerGetAttributes(&at, stats) == hipSuccess)
-            dev_dst = at.type == hipMemoryTypeDevice;
-        else
-            (void)hipGetLastError();
-    }
+    const bool dev_dst = stats && rox::is_device(stats);
     rox_focus_psf_stats *out_stats = dev_dst ? stats : d_stats;
     const bool small = M <= 512;
     const int W = small ? 32 : kTile;

@@ -1,10 +1,15 @@
 // rox_host.hpp -- host-side helpers shared by the translation units that define C entry points
-// (roxtrace.hip, psf.hip, spotstats.hip): the error path, grow-only scratch blocks, and scratch
-// kept per (device, stream).
+// (roxtrace.hip, spotstats.hip and the analyses psf.hip, mtf.hip, ee.hip, zernike.hip): the error
+// path and the argument checks, grow-only scratch blocks, scratch kept per (device, stream), the
+// pinned staging of host inputs and the carving of one workspace block.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cassert>
+#include <cmath>
+#include <cstdint>
 #include <mutex>
 #include <new>
 #include <vector>
@@ -24,6 +29,80 @@ int host_fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3
         if (e_ != hipSuccess)                                                                     \
             return rox::host_fail(ROX_E_HIP, "%s%s: %s", kHipWhere, #expr, hipGetErrorString(e_)); \
     } while (0)
+
+// Returns the ROX_E_* code of expr from the enclosing function when it is not 0.
+#define ROX_TRY(expr)                                                                             \
+    do {                                                                                          \
+        if (const int rc_ = (expr))                                                               \
+            return rc_;                                                                           \
+    } while (0)
+
+// ---- argument checks: 0, or ROX_E_ARG with a message that starts with the entry's name e
+
+// "<e>: <name> <v> outside [lo, hi]"
+inline int check_range(const char *e, const char *name, int v, int lo, int hi)
+{
+    if (v < lo || v > hi)
+        return host_fail(ROX_E_ARG, "%s: %s %d outside [%d, %d]", e, name, v, lo, hi);
+    return 0;
+}
+
+// pixel pitches [total]: finite and > 0
+inline int check_pitch(const char *e, int64_t total, const double *pitch)
+{
+    for (int64_t i = 0; i < total; ++i)
+        if (!(std::isfinite(pitch[i]) && pitch[i] > 0.0))
+            return host_fail(ROX_E_ARG, "%s: pitch[%lld] = %g is not finite and > 0", e, (long long)i, pitch[i]);
+    return 0;
+}
+
+// radii [total][nr]: finite, >= 0, non-decreasing per plane
+inline int check_radii(const char *e, int64_t total, int32_t nr, const double *radii)
+{
+    for (int64_t z = 0; z < total; ++z)
+        for (int32_t j = 0; j < nr; ++j) {
+            const double r = radii[z * nr + j];
+            if (!(std::isfinite(r) && r >= 0.0))
+                return host_fail(ROX_E_ARG, "%s: radii[%lld] = %g is not finite and >= 0", e,
+                                 (long long)(z * nr + j), r);
+            if (j && r < radii[z * nr + j - 1])
+                return host_fail(ROX_E_ARG, "%s: radii[%lld] = %g decreases within its plane", e,
+                                 (long long)(z * nr + j), r);
+        }
+    return 0;
+}
+
+// centers [total][2] (null: none): finite
+inline int check_centers(const char *e, int64_t total, const double *centers)
+{
+    if (centers)
+        for (int64_t i = 0; i < 2 * total; ++i)
+            if (!std::isfinite(centers[i]))
+                return host_fail(ROX_E_ARG, "%s: centers[%lld] = %g is not finite", e, (long long)i, centers[i]);
+    return 0;
+}
+
+// ---- sizes and pointers
+
+inline size_t up256(size_t b) { return (b + 255) & ~size_t(255); }
+
+// Whether p is device memory.  A pointer HIP does not know (pageable host memory) is not, and
+// the error of its failed query is cleared.
+inline bool is_device(const void *p)
+{
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) == hipSuccess)
+        return at.type == hipMemoryTypeDevice;
+    (void)hipGetLastError();
+    return false;
+}
+
+// Planes per launch when each takes per_plane bytes of a scratch capped at cap bytes: at least
+// one, at most total and 65535 (a grid dimension).
+inline int64_t chunk_for(int64_t total, size_t per_plane, size_t cap)
+{
+    return std::max<int64_t>(1, std::min<int64_t>({total, (int64_t)(cap / per_plane), 65535}));
+}
 
 // Grow-only scratch blocks: a pointer p and its capacity cap, in whatever unit the caller counts.
 // `kind` is kDeviceBlock (hipMalloc) or the hipHostMalloc flags of a pinned block.
@@ -84,6 +163,18 @@ class PerStream {
         T data;
     };
 
+    // The slot of the current device and stream st in *out, or ROX_E_HIP / ROX_E_NOMEM with a
+    // message that starts with `where`.
+    int take(hipStream_t st, const char *where, Slot **out)
+    {
+        int device = 0;
+        const hipError_t e = hipGetDevice(&device);
+        if (e != hipSuccess)
+            return host_fail(ROX_E_HIP, "%shipGetDevice(&device): %s", where, hipGetErrorString(e));
+        *out = get(device, st);
+        return *out ? 0 : host_fail(ROX_E_NOMEM, "%sout of host memory", where);
+    }
+
     // nullptr when out of host memory
     Slot *get(int device, hipStream_t st)
     {
@@ -103,6 +194,73 @@ class PerStream {
   private:
     std::mutex mu_;
     std::vector<Slot *> slots_;
+};
+
+// A pinned block the host fills and copies to the device from.  ev is recorded after the last
+// copy that reads the block, and the next call waits for it before it writes the block again.
+struct Staging {
+    char *h = nullptr;
+    size_t cap = 0;                 // bytes
+    hipEvent_t ev = nullptr;
+
+    // At least `bytes` of h, free to write: the event is made on first use and waited for after.
+    // A block too small is replaced by one of `grow` bytes (default: `bytes`).
+    hipError_t acquire(size_t bytes, size_t grow = 0)
+    {
+        hipError_t e = ev ? hipEventSynchronize(ev) : hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+        if (e == hipSuccess && cap < bytes) {
+            const size_t n = grow ? grow : bytes;
+            e = regrow(h, cap, n, n, hipHostMallocDefault);
+        }
+        return e;
+    }
+
+    // after the last copy that reads h
+    hipError_t record(hipStream_t st) { return hipEventRecord(ev, st); }
+};
+
+// The state of an analysis entry per (device, stream): a grow-only device block and the staging
+// of the call's host inputs.
+struct Workspace {
+    char *buf = nullptr;
+    size_t cap = 0;
+    Staging stage;
+
+    // at least `need` bytes of buf; a new block (its old contents lost) when it grows
+    hipError_t reserve(size_t need) { return cap < need ? regrow(buf, cap, need, need) : hipSuccess; }
+};
+
+// One block as consecutive regions, in the order they are added: size() is the block's bytes and
+// carve(base) points each region's pointer into the block at base.
+class Layout {
+  public:
+    template <class T>
+    Layout &add(T *&p, size_t bytes)
+    {
+        assert(n_ < kMaxRegions);
+        regions_[n_++] = {&p, bytes, [](void *q, char *at) { *static_cast<T **>(q) = reinterpret_cast<T *>(at); }};
+        size_ += bytes;
+        return *this;
+    }
+    size_t size() const { return size_; }
+    void carve(char *base) const
+    {
+        for (int i = 0; i < n_; ++i) {
+            regions_[i].set(regions_[i].p, base);
+            base += regions_[i].bytes;
+        }
+    }
+
+  private:
+    static constexpr int kMaxRegions = 16;
+    struct Region {
+        void *p;
+        size_t bytes;
+        void (*set)(void *p, char *at);
+    };
+    Region regions_[kMaxRegions];
+    int n_ = 0;
+    size_t size_ = 0;
 };
 
 }  // namespace rox

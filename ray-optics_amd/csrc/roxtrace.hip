@@ -227,18 +227,14 @@ struct StreamCtx {
     char *d_focus = nullptr;
     size_t focus_cap = 0;
     // ... and the pinned block the planes are copied from (the caller's array may be pageable
-    // and is free to go when the call returns): rewritten only after the copy that last read
-    // it has completed (focus_ev)
-    rox_focus_plane *h_focus = nullptr;
-    int32_t h_focus_cap = 0;
-    hipEvent_t focus_ev = nullptr;
+    // and is free to go when the call returns)
+    Staging h_focus;
     // rox_trace_through_focus_grids (grow-only): the device block -- items, planes and axis
-    // parameters (copied in one transfer from the pinned block h_fbatch, rewritten only after
-    // that copy has completed: fbatch_ev), then the pupil axes, the statistics and the partial
-    // records of one launch
-    char *d_fbatch = nullptr, *h_fbatch = nullptr;
-    size_t d_fbatch_cap = 0, h_fbatch_cap = 0;
-    hipEvent_t fbatch_ev = nullptr;
+    // parameters (copied in one transfer from the pinned block h_fbatch), then the pupil axes,
+    // the statistics and the partial records of one launch
+    char *d_fbatch = nullptr;
+    size_t d_fbatch_cap = 0;
+    Staging h_fbatch;
     // Everything a pupil-grid call does between reading / rewriting the cached axes
     // (prepare_grid) and handing its launches to the stream is one critical section per
     // stream: two host threads enqueueing on the SAME stream take turns (their launches run
@@ -667,14 +663,7 @@ bool want_two_pass(const rox_system *sys, int inst, int64_t n_rays, const void *
         return forced == 1;
     (void)sys;
     (void)inst;
-    if (n_rays < kTwoPassMinRays)
-        return false;
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, dst) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return at.type == hipMemoryTypeDevice;
+    return n_rays >= kTwoPassMinRays && is_device(dst);
 }
 
 int ensure_pack_scratch(StreamCtx *cx, int64_t rays, bool need_status)
@@ -1412,13 +1401,13 @@ int rox_system_destroy(rox_system *sys)
         (void)hipFree(c->d_btickets);
         (void)hipFree(c->d_btiles);
         (void)hipFree(c->d_focus);
-        (void)hipHostFree(c->h_focus);
-        if (c->focus_ev)
-            (void)hipEventDestroy(c->focus_ev);
+        (void)hipHostFree(c->h_focus.h);
+        if (c->h_focus.ev)
+            (void)hipEventDestroy(c->h_focus.ev);
         (void)hipFree(c->d_fbatch);
-        (void)hipHostFree(c->h_fbatch);
-        if (c->fbatch_ev)
-            (void)hipEventDestroy(c->fbatch_ev);
+        (void)hipHostFree(c->h_fbatch.h);
+        if (c->h_fbatch.ev)
+            (void)hipEventDestroy(c->h_fbatch.ev);
         for (hipEvent_t ev : c->item_ev)
             if (ev)
                 (void)hipEventDestroy(ev);
@@ -1514,9 +1503,7 @@ int rox_trace_through_focus(rox_system *sys, const rox_field *fld, const rox_gri
     // every argument check comes before anything touches a device
     if (!fld || !grid || !opts)
         return fail(ROX_E_ARG, "rox_trace_through_focus: null argument");
-    if (n_planes <= 0 || n_planes > ROX_MAX_FOCUS_PLANES)
-        return fail(ROX_E_ARG, "rox_trace_through_focus: n_planes %d outside [1, %d]", n_planes,
-                    ROX_MAX_FOCUS_PLANES);
+    ROX_TRY(check_range("rox_trace_through_focus", "n_planes", n_planes, 1, ROX_MAX_FOCUS_PLANES));
     if (!planes)
         return fail(ROX_E_ARG, "rox_trace_through_focus: planes is null");
     if (!rows && !stats)
@@ -1554,9 +1541,9 @@ int rox_trace_through_focus(rox_system *sys, const rox_field *fld, const rox_gri
     const int bs_max = block_of(MODE_FOCUS, F_ALL) > block_of(MODE_FOCUS, 0) ? block_of(MODE_FOCUS, F_ALL)
                                                                                : block_of(MODE_FOCUS, 0);
     const int64_t cap_blocks = (int64_t)sys->num_cus * kFocusBlocksPerCu;
-    const size_t b_planes = ((size_t)n_planes * sizeof(rox_focus_plane) + 255) & ~size_t(255);
+    const size_t b_planes = up256((size_t)n_planes * sizeof(rox_focus_plane));
     const size_t b_part = stats ? (size_t)cap_blocks * (bs_max / 64) * n_planes * sizeof(FocusAcc) : 0;
-    const size_t b_stats = ((size_t)n_planes * sizeof(rox_focus_stats) + 255) & ~size_t(255);
+    const size_t b_stats = up256((size_t)n_planes * sizeof(rox_focus_stats));
     const size_t need = b_planes + b_part + b_stats;
     if (need > cx->focus_cap)
         HIP_TRY(regrow(cx->d_focus, cx->focus_cap, need, need));
@@ -1596,29 +1583,20 @@ int rox_trace_through_focus(rox_system *sys, const rox_field *fld, const rox_gri
     if (blocks > cap_blocks)
         blocks = cap_blocks;
     k.grid = dim3((unsigned)blocks);
-    if (!cx->focus_ev)
-        HIP_TRY(hipEventCreateWithFlags(&cx->focus_ev, hipEventDisableTiming));
-    else
-        HIP_TRY(hipEventSynchronize(cx->focus_ev));     // the previous call's copy has read h_focus
-    if (n_planes > cx->h_focus_cap)
-        HIP_TRY(regrow(cx->h_focus, cx->h_focus_cap, ROX_MAX_FOCUS_PLANES,
-                       sizeof(rox_focus_plane) * ROX_MAX_FOCUS_PLANES, hipHostMallocDefault));
-    memcpy(cx->h_focus, planes, sizeof(rox_focus_plane) * (size_t)n_planes);
-    HIP_TRY(hipMemcpyAsync(d_planes, cx->h_focus, sizeof(rox_focus_plane) * (size_t)n_planes,
+    // (the block is made for ROX_MAX_FOCUS_PLANES planes at once)
+    HIP_TRY(cx->h_focus.acquire(sizeof(rox_focus_plane) * (size_t)n_planes,
+                                sizeof(rox_focus_plane) * ROX_MAX_FOCUS_PLANES));
+    memcpy(cx->h_focus.h, planes, sizeof(rox_focus_plane) * (size_t)n_planes);
+    HIP_TRY(hipMemcpyAsync(d_planes, cx->h_focus.h, sizeof(rox_focus_plane) * (size_t)n_planes,
                            hipMemcpyHostToDevice, st));
-    HIP_TRY(hipEventRecord(cx->focus_ev, st));
+    HIP_TRY(cx->h_focus.record(st));
     if (stats)      // every wave merges into its records: they start at n = 0
         HIP_TRY(hipMemsetAsync(d_part, 0, (size_t)blocks * (bs / 64) * n_planes * sizeof(FocusAcc), st));
     trace_fns(inst, k).focus(k, f);
     HIP_TRY(hipGetLastError());
     if (!stats)
         return 0;
-    hipPointerAttribute_t at;
-    bool dev_dst = false;
-    if (hipPointerGetAttributes(&at, stats) == hipSuccess)
-        dev_dst = at.type == hipMemoryTypeDevice;
-    else
-        (void)hipGetLastError();
+    const bool dev_dst = is_device(stats);
     hipLaunchKernelGGL(focus_finish_kernel<false>, dim3((unsigned)n_planes), dim3(kFocusFinishBlock), 0, st,
                        (const FocusAcc *)d_part,
                        blocks * (bs / 64), n_planes, dev_dst ? stats : d_stats);
@@ -1646,10 +1624,8 @@ int rox_trace_through_focus_grids(rox_system *sys, int32_t n_items, const rox_fi
 {
     static const char kE[] = "rox_trace_through_focus_grids";
     // every argument check comes before anything touches a device
-    if (n_items < 1 || n_items > ROX_MAX_FOCUS_ITEMS)
-        return fail(ROX_E_ARG, "%s: n_items %d outside [1, %d]", kE, n_items, ROX_MAX_FOCUS_ITEMS);
-    if (n_planes < 1 || n_planes > ROX_MAX_FOCUS_PLANES)
-        return fail(ROX_E_ARG, "%s: n_planes %d outside [1, %d]", kE, n_planes, ROX_MAX_FOCUS_PLANES);
+    ROX_TRY(check_range(kE, "n_items", n_items, 1, ROX_MAX_FOCUS_ITEMS));
+    ROX_TRY(check_range(kE, "n_planes", n_planes, 1, ROX_MAX_FOCUS_PLANES));
     if (!flds || !wvl_idx || !grids || !opts || !planes)
         return fail(ROX_E_ARG, "%s: null array (flds, wvl_idx, grids, opts or planes)", kE);
     if (!rows && !stats)
@@ -1752,7 +1728,6 @@ int rox_trace_through_focus_grids(rox_system *sys, int32_t n_items, const rox_fi
     const int32_t n_slots = (int32_t)(prm.size() / 4);
 
     // device block: [items][planes][axis parameters] (staged) [axes][statistics][partial records]
-    auto up256 = [](size_t b) { return (b + 255) & ~size_t(255); };
     const size_t b_items = up256(sizeof(FocusArgs) * (size_t)n_items);
     const size_t b_planes = up256(sizeof(rox_focus_plane) * (size_t)n_items * n_planes);
     const size_t b_prm = up256(sizeof(double) * prm.size());
@@ -1783,29 +1758,18 @@ int rox_trace_through_focus_grids(rox_system *sys, int32_t n_items, const rox_fi
     }
 
     // stage through the pinned block (once the previous call's copy has read it), one copy
-    if (!cx->fbatch_ev)
-        HIP_TRY(hipEventCreateWithFlags(&cx->fbatch_ev, hipEventDisableTiming));
-    else
-        HIP_TRY(hipEventSynchronize(cx->fbatch_ev));
-    if (staged > cx->h_fbatch_cap)
-        HIP_TRY(regrow(cx->h_fbatch, cx->h_fbatch_cap, staged, staged, hipHostMallocDefault));
-    memcpy(cx->h_fbatch, items.data(), sizeof(FocusArgs) * (size_t)n_items);
-    memcpy(cx->h_fbatch + b_items, planes, sizeof(rox_focus_plane) * (size_t)n_items * n_planes);
-    memcpy(cx->h_fbatch + b_items + b_planes, prm.data(), sizeof(double) * prm.size());
-    HIP_TRY(hipMemcpyAsync(cx->d_fbatch, cx->h_fbatch, staged, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipEventRecord(cx->fbatch_ev, st));
+    HIP_TRY(cx->h_fbatch.acquire(staged));
+    char *h = cx->h_fbatch.h;
+    memcpy(h, items.data(), sizeof(FocusArgs) * (size_t)n_items);
+    memcpy(h + b_items, planes, sizeof(rox_focus_plane) * (size_t)n_items * n_planes);
+    memcpy(h + b_items + b_planes, prm.data(), sizeof(double) * prm.size());
+    HIP_TRY(hipMemcpyAsync(cx->d_fbatch, h, staged, hipMemcpyHostToDevice, st));
+    HIP_TRY(cx->h_fbatch.record(st));
     hipLaunchKernelGGL(pupil_axes_slots_kernel, dim3((unsigned)((2 * n_slots + 63) / 64)), dim3(64), 0, st,
                        (const double *)d_prm, n_slots, g0.num, d_axes);
     HIP_TRY(hipGetLastError());
 
-    bool dev_dst = false;
-    if (stats) {
-        hipPointerAttribute_t at;
-        if (hipPointerGetAttributes(&at, stats) == hipSuccess)
-            dev_dst = at.type == hipMemoryTypeDevice;
-        else
-            (void)hipGetLastError();
-    }
+    const bool dev_dst = stats && is_device(stats);
     for (int32_t i0 = 0; i0 < n_items; i0 += per_launch) {
         const int32_t n = std::min(per_launch, n_items - i0);
         if (stats)      // every wave merges into its records: they start at n = 0

@@ -474,25 +474,7 @@ __global__ void __launch_bounds__(kBlock) zk_finish(const ItemDev *items, const 
 }
 
 // ---- host ---------------------------------------------------------------------------------------
-struct ZkWorkspace {
-    char *buf = nullptr;
-    size_t cap = 0;
-    char *h_stage = nullptr;        // pinned staging of the host inputs, reused once ev has passed
-    size_t h_cap = 0;
-    hipEvent_t ev = nullptr;
-};
-rox::PerStream<ZkWorkspace> g_zk_ws;
-
-size_t up256(size_t b) { return (b + 255) & ~size_t(255); }
-
-bool is_device(const void *p)
-{
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) == hipSuccess)
-        return at.type == hipMemoryTypeDevice;
-    (void)hipGetLastError();
-    return false;
-}
+rox::PerStream<rox::Workspace> g_zk_ws;
 
 // (n-k)! / (k! ((n+m)/2-k)! ((n-m)/2-k)!) as an exact integer (n <= 20: 20! < 2^64), then a double
 double radial_coef(int n, int m, int k)
@@ -514,12 +496,9 @@ extern "C" int rox_focus_zernike(int32_t n_items, int32_t n_planes, const double
                                  double *coef, rox_zernike_stats *stats, void *stream)
 {
     static const char kE[] = "rox_focus_zernike";
-    if (n_items < 1 || n_items > ROX_MAX_FOCUS_ITEMS)
-        return rox::host_fail(ROX_E_ARG, "%s: n_items %d outside [1, %d]", kE, n_items, ROX_MAX_FOCUS_ITEMS);
-    if (n_planes < 1 || n_planes > ROX_MAX_FOCUS_PLANES)
-        return rox::host_fail(ROX_E_ARG, "%s: n_planes %d outside [1, %d]", kE, n_planes, ROX_MAX_FOCUS_PLANES);
-    if (n_terms < 1 || n_terms > ROX_MAX_ZERNIKE_TERMS)
-        return rox::host_fail(ROX_E_ARG, "%s: n_terms %d outside [1, %d]", kE, n_terms, ROX_MAX_ZERNIKE_TERMS);
+    ROX_TRY(rox::check_range(kE, "n_items", n_items, 1, ROX_MAX_FOCUS_ITEMS));
+    ROX_TRY(rox::check_range(kE, "n_planes", n_planes, 1, ROX_MAX_FOCUS_PLANES));
+    ROX_TRY(rox::check_range(kE, "n_terms", n_terms, 1, ROX_MAX_ZERNIKE_TERMS));
     if (!rows || !status || !grids || !wave_scale || !terms)
         return rox::host_fail(ROX_E_ARG, "%s: null rows, status, grids, wave_scale or terms", kE);
     if (!coef && !stats)
@@ -556,13 +535,10 @@ extern "C" int rox_focus_zernike(int32_t n_items, int32_t n_planes, const double
     }
 
     hipStream_t st = (hipStream_t)stream;
-    int device = 0;
-    HIP_TRY(hipGetDevice(&device));
-    rox::PerStream<ZkWorkspace>::Slot *slot = g_zk_ws.get(device, st);
-    if (!slot)
-        return rox::host_fail(ROX_E_NOMEM, "%sout of host memory", kHipWhere);
+    rox::PerStream<rox::Workspace>::Slot *slot;
+    ROX_TRY(g_zk_ws.take(st, kHipWhere, &slot));
     std::lock_guard<std::mutex> turn(slot->mu);
-    ZkWorkspace *ws = &slot->data;
+    rox::Workspace *ws = &slot->data;
 
     const int J = n_terms, K = n_planes;
     const int JP = (J + 1 + 15) & ~15;
@@ -590,54 +566,41 @@ extern "C" int rox_focus_zernike(int32_t n_items, int32_t n_planes, const double
     const size_t per_item = sizeof(ItemDev) + sizeof(double) * (kMaxChunks * rec + rec + (size_t)J * J + J + (size_t)2 * K * J + K) +
                             sizeof(ItemFit) + sizeof(double) * kMaxChunks * K * 4 + sizeof(int64_t) * kMaxChunks * 2 +
                             sizeof(rox_zernike_stats) * K + sizeof(double) * 2 * 16384;
-    const int32_t per_launch = (int32_t)std::max<size_t>(1, std::min<size_t>(n_items, kScratchBytes / per_item));
+    // (n_items <= ROX_MAX_FOCUS_ITEMS: chunk_for's grid bound never binds)
+    const int32_t per_launch = (int32_t)rox::chunk_for(n_items, per_item, kScratchBytes);
 
-    const size_t b_terms = up256(sizeof(TermDev) * J), b_tc = up256(sizeof(double) * tc.size());
-    const size_t b_items = up256(sizeof(ItemDev) * n_items);
-    const size_t b_axes = up256(sizeof(double) * (size_t)axes_total);
-    const size_t b_part = up256(sizeof(double) * kMaxChunks * rec * per_launch);
-    const size_t b_sums = up256(sizeof(double) * rec * per_launch);
-    const size_t b_fac = up256(sizeof(double) * ((size_t)J * (J + 1) / 2 + J) * per_launch);
-    const size_t b_fits = up256(sizeof(ItemFit) * per_launch);
-    const size_t b_coef = up256(sizeof(double) * (size_t)K * J * per_launch);
-    const size_t b_mean = up256(sizeof(double) * (size_t)K * per_launch);
-    const size_t b_spart = up256(sizeof(double) * kMaxChunks * K * 4 * per_launch);
-    const size_t b_cpart = up256(sizeof(int64_t) * kMaxChunks * 2 * per_launch);
-    const size_t b_stats = up256(sizeof(rox_zernike_stats) * (size_t)K * per_launch);
-    const size_t staged = b_terms + b_tc + b_axes;
-    const size_t stage_bytes = staged + b_items;
-    const size_t need = stage_bytes + b_part + b_sums + b_fac + b_fits + 2 * b_coef + b_mean + b_spart + b_cpart + b_stats;
+    // [terms][term coefficients][axes][items] are staged and copied in one transfer
+    TermDev *d_terms;
+    double *d_tc, *d_axes, *d_part, *d_sums, *d_fac, *d_coef, *d_tmp, *d_mean, *d_spart;
+    ItemDev *d_items;
+    ItemFit *d_fits;
+    int64_t *d_cpart;
+    rox_zernike_stats *d_stats;
+    rox::Layout L;
+    L.add(d_terms, rox::up256(sizeof(TermDev) * J)).add(d_tc, rox::up256(sizeof(double) * tc.size()));
+    L.add(d_axes, rox::up256(sizeof(double) * (size_t)axes_total));
+    L.add(d_items, rox::up256(sizeof(ItemDev) * n_items));
+    const size_t stage_bytes = L.size();
+    L.add(d_part, rox::up256(sizeof(double) * kMaxChunks * rec * per_launch));
+    L.add(d_sums, rox::up256(sizeof(double) * rec * per_launch));
+    L.add(d_fac, rox::up256(sizeof(double) * ((size_t)J * (J + 1) / 2 + J) * per_launch));
+    L.add(d_fits, rox::up256(sizeof(ItemFit) * per_launch));
+    L.add(d_coef, rox::up256(sizeof(double) * (size_t)K * J * per_launch));
+    L.add(d_tmp, rox::up256(sizeof(double) * (size_t)K * J * per_launch));
+    L.add(d_mean, rox::up256(sizeof(double) * (size_t)K * per_launch));
+    L.add(d_spart, rox::up256(sizeof(double) * kMaxChunks * K * 4 * per_launch));
+    L.add(d_cpart, rox::up256(sizeof(int64_t) * kMaxChunks * 2 * per_launch));
+    L.add(d_stats, rox::up256(sizeof(rox_zernike_stats) * (size_t)K * per_launch));
+    HIP_TRY(ws->reserve(L.size()));
+    HIP_TRY(ws->stage.acquire(stage_bytes));
+    L.carve(ws->buf);
 
-    if (ws->cap < need)
-        HIP_TRY(rox::regrow(ws->buf, ws->cap, need, need));
-    if (!ws->ev)
-        HIP_TRY(hipEventCreateWithFlags(&ws->ev, hipEventDisableTiming));
-    else
-        HIP_TRY(hipEventSynchronize(ws->ev));
-    if (ws->h_cap < stage_bytes)
-        HIP_TRY(rox::regrow(ws->h_stage, ws->h_cap, stage_bytes, stage_bytes, hipHostMallocDefault));
-
-    char *p = ws->buf;
-    TermDev *d_terms = (TermDev *)p;            p += b_terms;
-    double *d_tc = (double *)p;                 p += b_tc;
-    double *d_axes = (double *)p;               p += b_axes;
-    ItemDev *d_items = (ItemDev *)p;            p += b_items;
-    double *d_part = (double *)p;               p += b_part;
-    double *d_sums = (double *)p;               p += b_sums;
-    double *d_fac = (double *)p;                p += b_fac;
-    ItemFit *d_fits = (ItemFit *)p;             p += b_fits;
-    double *d_coef = (double *)p;               p += b_coef;
-    double *d_tmp = (double *)p;                p += b_coef;
-    double *d_mean = (double *)p;               p += b_mean;
-    double *d_spart = (double *)p;              p += b_spart;
-    int64_t *d_cpart = (int64_t *)p;            p += b_cpart;
-    rox_zernike_stats *d_stats = (rox_zernike_stats *)p;
-
-    char *h = ws->h_stage;
-    memcpy(h, th.data(), sizeof(TermDev) * J);
-    memcpy(h + b_terms, tc.data(), sizeof(double) * tc.size());
-    double *h_axes = (double *)(h + b_terms + b_tc);
-    ItemDev *h_items = (ItemDev *)(h + staged);
+    char *h = ws->stage.h;                      // the staged regions at their device offsets
+    auto host = [&](const void *d) { return h + ((const char *)d - ws->buf); };
+    memcpy(host(d_terms), th.data(), sizeof(TermDev) * J);
+    memcpy(host(d_tc), tc.data(), sizeof(double) * tc.size());
+    double *h_axes = (double *)host(d_axes);
+    ItemDev *h_items = (ItemDev *)host(d_items);
     int64_t ax_off = 0;
     for (int32_t i = 0; i < n_items; ++i) {
         const rox_grid &g = grids[i];
@@ -665,9 +628,9 @@ extern "C" int rox_focus_zernike(int32_t n_items, int32_t n_planes, const double
         it.span = (span + kTile - 1) / kTile * kTile;
     }
     HIP_TRY(hipMemcpyAsync(ws->buf, h, stage_bytes, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipEventRecord(ws->ev, st));
+    HIP_TRY(ws->stage.record(st));
 
-    const bool host_dst = (coef && !is_device(coef)) || (stats && !is_device(stats));
+    const bool host_dst = (coef && !rox::is_device(coef)) || (stats && !rox::is_device(stats));
     const size_t lds_pass = sizeof(double) * (kTile * (kMaxJP + kPG + 1) + (size_t)kPG * J);
     const size_t lds_solve = sizeof(double) * ((size_t)J * (J + 1) / 2 + J);
     for (int32_t i0 = 0; i0 < n_items; i0 += per_launch) {

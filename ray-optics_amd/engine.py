@@ -172,6 +172,11 @@ class FocusRows:
         return self.rows.cpu().numpy(), self.status.cpu().numpy()
 
 
+def _f64(x, shape):
+    """x as a C-contiguous float64 array broadcast to shape"""
+    return np.ascontiguousarray(np.broadcast_to(np.asarray(x, dtype=np.float64), shape))
+
+
 def padded_ld(R):
     """row pitch (in doubles) of the SoA packet buffer.  Rows exactly 2^k bytes
     apart put one ray's 130 packet components on the same HBM channel; a pitch
@@ -941,6 +946,37 @@ class TraceEngine:
             return stats
         return stats, FocusRows(rows[:, :, :, :R], status[:, :R])
 
+    def _focus_rows(self, focus_rows, what):
+        """the [n_items][K][3][ld] rows and [n_items][ld] status of a through-focus launch (a
+        single scan gains the item axis) -> (rows, status, n_items, K, ld)"""
+        rows, status = focus_rows.rows, focus_rows.status
+        if rows.dim() == 3:
+            rows, status = rows.unsqueeze(0), status.unsqueeze(0)
+        n_items, K = int(rows.shape[0]), int(rows.shape[1])
+        ld = int(rows.stride(2))
+        if rows.dtype != self.torch.float64 or rows.stride(3) != 1 or rows.stride(1) != 3 * ld or \
+                rows.stride(0) != K * 3 * ld or status.stride(-1) != 1 or \
+                (n_items > 1 and status.stride(0) != ld):
+            raise EngineError(f'{what} reads the [n_items][K][3][ld] rows and [n_items][ld] status '
+                              'of a through-focus launch')
+        return rows, status, n_items, K, ld
+
+    def _psf_stack(self, psf, what):
+        """the contiguous float64 [n_items][K][M][M] PSFs of focus_psf -> (n_items, K, M)"""
+        if psf.dim() != 4 or psf.dtype != self.torch.float64 or not psf.is_contiguous() or \
+                int(psf.shape[2]) != int(psf.shape[3]):
+            raise EngineError(f'{what} reads the contiguous float64 [n_items][K][M][M] PSFs of focus_psf')
+        return int(psf.shape[0]), int(psf.shape[1]), int(psf.shape[2])
+
+    def _out(self, on_device, shape, dtype, tdtype, tshape=None):
+        """an array a C entry writes -> (array, pointer): a torch tensor on this engine's device
+        (of shape ``tshape``, default ``shape``) with ``on_device``, else a NumPy array"""
+        if on_device:
+            a = self.torch.empty(shape if tshape is None else tshape, dtype=tdtype, device=self.device)
+            return a, a.data_ptr()
+        a = np.empty(shape, dtype=dtype)
+        return a, a.ctypes.data
+
     @_in_flight
     def focus_psf(self, focus_rows, ndim, maxdim, wave_scale, want_psf=True):
         """rox_focus_psf over the rows of a through-focus launch (``focus_rows``: the FocusRows
@@ -950,18 +986,8 @@ class TraceEngine:
         the PSFs as a float64 tensor in HBM [n_items, K, maxdim, maxdim] (None without
         ``want_psf``) and a FOCUS_PSF_STATS_DTYPE array [n_items, K] (n, strehl, psf_peak)."""
         t = self.torch
-        rows, status = focus_rows.rows, focus_rows.status
-        single = rows.dim() == 3
-        if single:
-            rows, status = rows.unsqueeze(0), status.unsqueeze(0)
-        n_items, K = int(rows.shape[0]), int(rows.shape[1])
-        ld = int(rows.stride(2))
-        if rows.dtype != t.float64 or rows.stride(3) != 1 or rows.stride(1) != 3 * ld or \
-                rows.stride(0) != K * 3 * ld or status.stride(-1) != 1 or \
-                (n_items > 1 and status.stride(0) != ld):
-            raise EngineError('focus_psf reads the [n_items][K][3][ld] rows and [n_items][ld] status '
-                              'of a through-focus launch')
-        scale = np.ascontiguousarray(np.broadcast_to(np.asarray(wave_scale, dtype=np.float64), (n_items,)))
+        rows, status, n_items, K, ld = self._focus_rows(focus_rows, 'focus_psf')
+        scale = _f64(wave_scale, (n_items,))
         ndim, maxdim = int(ndim), int(maxdim)
         if ndim * ndim > int(rows.shape[3]) or ndim * ndim > int(status.shape[-1]):
             raise EngineError(f'focus_psf: a {ndim} x {ndim} grid needs {ndim * ndim} rays, the rows hold '
@@ -984,19 +1010,11 @@ class TraceEngine:
         ``on_device`` a complex128 tensor of that shape in HBM.  NaN above a plane's Nyquist
         frequency and on planes no ray reached."""
         t = self.torch
-        if psf.dim() != 4 or psf.dtype != t.float64 or not psf.is_contiguous() or \
-                int(psf.shape[2]) != int(psf.shape[3]):
-            raise EngineError('focus_mtf reads the contiguous float64 [n_items][K][M][M] PSFs of focus_psf')
-        n_items, K, M = int(psf.shape[0]), int(psf.shape[1]), int(psf.shape[2])
-        p = np.ascontiguousarray(np.broadcast_to(np.asarray(pitch, dtype=np.float64), (n_items, K)))
+        n_items, K, M = self._psf_stack(psf, 'focus_mtf')
+        p = _f64(pitch, (n_items, K))
         f = np.ascontiguousarray(np.asarray(freqs, dtype=np.float64).reshape(-1))
         Q = int(f.size)
-        if on_device:
-            out = t.empty((n_items, K, 2, Q, 2), dtype=t.float64, device=self.device)
-            ptr = out.data_ptr()
-        else:
-            out = np.empty((n_items, K, 2, Q, 2), dtype=np.float64)
-            ptr = out.ctypes.data
+        out, ptr = self._out(on_device, (n_items, K, 2, Q, 2), np.float64, t.float64)
         with t.cuda.device(self.device):
             _check(self.lib.rox_focus_mtf(n_items, K, psf.data_ptr(), M, p.ctypes.data, Q, f.ctypes.data,
                                           ptr, self._stream()), 'rox_focus_mtf')
@@ -1017,45 +1035,26 @@ class TraceEngine:
         ray arrived), int64 [n_items, K] -- NumPy, or torch tensors in HBM with ``on_device``;
         None for what was not asked."""
         t = self.torch
-        rows, status = focus_rows.rows, focus_rows.status
-        if rows.dim() == 3:
-            rows, status = rows.unsqueeze(0), status.unsqueeze(0)
-        n_items, K = int(rows.shape[0]), int(rows.shape[1])
-        ld = int(rows.stride(2))
-        if rows.dtype != t.float64 or rows.stride(3) != 1 or rows.stride(1) != 3 * ld or \
-                rows.stride(0) != K * 3 * ld or status.stride(-1) != 1 or \
-                (n_items > 1 and status.stride(0) != ld):
-            raise EngineError('focus_ee reads the [n_items][K][3][ld] rows and [n_items][ld] status '
-                              'of a through-focus launch')
+        rows, status, n_items, K, ld = self._focus_rows(focus_rows, 'focus_ee')
         n_rays = int(n_rays)
         if not 1 <= n_rays <= min(int(rows.shape[3]), int(status.shape[-1])):
             raise EngineError(f'focus_ee: n_rays {n_rays} outside [1, {int(rows.shape[3])}]')
         if radii is None and fractions is None:
             raise EngineError('focus_ee: radii or fractions (or both)')
-        c = None
-        if centers is not None:
-            c = np.ascontiguousarray(np.broadcast_to(np.asarray(centers, dtype=np.float64), (n_items, K, 2)))
+        c = _f64(centers, (n_items, K, 2)) if centers is not None else None
         r = f = None
         Nr = Nf = 0
         if radii is not None:
             r = np.asarray(radii, dtype=np.float64)
             Nr = int(r.shape[-1]) if r.ndim else 1
-            r = np.ascontiguousarray(np.broadcast_to(r, (n_items, K, Nr)))
+            r = _f64(r, (n_items, K, Nr))
         if fractions is not None:
             f = np.ascontiguousarray(np.asarray(fractions, dtype=np.float64).reshape(-1))
             Nf = int(f.size)
-
-        def out(shape, dtype, tdtype, want):
-            if not want:
-                return None, None
-            if on_device:
-                a = t.empty(shape, dtype=tdtype, device=self.device)
-                return a, a.data_ptr()
-            a = np.empty(shape, dtype=dtype)
-            return a, a.ctypes.data
-        counts, p_counts = out((n_items, K, Nr), np.int64, t.int64, r is not None)
-        eer, p_eer = out((n_items, K, Nf), np.float64, t.float64, f is not None)
-        n_ok, p_nok = out((n_items, K), np.int64, t.int64, True)
+        none = (None, None)
+        counts, p_counts = self._out(on_device, (n_items, K, Nr), np.int64, t.int64) if r is not None else none
+        eer, p_eer = self._out(on_device, (n_items, K, Nf), np.float64, t.float64) if f is not None else none
+        n_ok, p_nok = self._out(on_device, (n_items, K), np.int64, t.int64)
         with t.cuda.device(self.device):
             _check(self.lib.rox_focus_ee(n_items, K, rows.data_ptr(), ld, status.data_ptr(), n_rays,
                                          c.ctypes.data if c is not None else None, Nr,
@@ -1077,16 +1076,7 @@ class TraceEngine:
         HBM and a torch uint8 tensor [n_items, K, 56] of the raw records (``zernike_stats_view``
         reads it on the host)."""
         t = self.torch
-        rows, status = focus_rows.rows, focus_rows.status
-        if rows.dim() == 3:
-            rows, status = rows.unsqueeze(0), status.unsqueeze(0)
-        n_items, K = int(rows.shape[0]), int(rows.shape[1])
-        ld = int(rows.stride(2))
-        if rows.dtype != t.float64 or rows.stride(3) != 1 or rows.stride(1) != 3 * ld or \
-                rows.stride(0) != K * 3 * ld or status.stride(-1) != 1 or \
-                (n_items > 1 and status.stride(0) != ld):
-            raise EngineError('focus_zernike reads the [n_items][K][3][ld] rows and [n_items][ld] '
-                              'status of a through-focus launch')
+        rows, status, n_items, K, ld = self._focus_rows(focus_rows, 'focus_zernike')
         if isinstance(grids, abi.Grid):
             grids = [grids] * n_items
         grids = list(grids)
@@ -1100,18 +1090,11 @@ class TraceEngine:
         J = len(tl)
         g_arr = (abi.Grid * max(n_items, 1))(*grids)
         z_arr = (abi.ZernikeTerm * max(J, 1))(*tl)
-        ws = np.ascontiguousarray(np.broadcast_to(np.asarray(wave_scale, dtype=np.float64), (n_items,)))
-        c = None
-        if circle is not None:
-            c = np.ascontiguousarray(np.broadcast_to(np.asarray(circle, dtype=np.float64), (n_items, 3)))
-        if on_device:
-            coef = t.empty((n_items, K, J), dtype=t.float64, device=self.device)
-            stats = t.empty((n_items, K, C.sizeof(abi.ZernikeStats)), dtype=t.uint8, device=self.device)
-            p_coef, p_stats = coef.data_ptr(), stats.data_ptr()
-        else:
-            coef = np.empty((n_items, K, J), dtype=np.float64)
-            stats = np.empty((n_items, K), dtype=ZERNIKE_STATS_DTYPE)
-            p_coef, p_stats = coef.ctypes.data, stats.ctypes.data
+        ws = _f64(wave_scale, (n_items,))
+        c = _f64(circle, (n_items, 3)) if circle is not None else None
+        coef, p_coef = self._out(on_device, (n_items, K, J), np.float64, t.float64)
+        stats, p_stats = self._out(on_device, (n_items, K), ZERNIKE_STATS_DTYPE, t.uint8,
+                                   (n_items, K, C.sizeof(abi.ZernikeStats)))
         with t.cuda.device(self.device):
             _check(self.lib.rox_focus_zernike(n_items, K, rows.data_ptr(), ld, status.data_ptr(), g_arr,
                                               c.ctypes.data if c is not None else None, ws.ctypes.data, J,
@@ -1129,17 +1112,12 @@ class TraceEngine:
         ``(ee, centroid)``: float64 [n_items, K, Nr] (NaN on planes no ray reached) and
         [n_items, K, 2] (None without ``want_centroid``)."""
         t = self.torch
-        if psf.dim() != 4 or psf.dtype != t.float64 or not psf.is_contiguous() or \
-                int(psf.shape[2]) != int(psf.shape[3]):
-            raise EngineError('focus_psf_ee reads the contiguous float64 [n_items][K][M][M] PSFs of focus_psf')
-        n_items, K, M = int(psf.shape[0]), int(psf.shape[1]), int(psf.shape[2])
-        p = np.ascontiguousarray(np.broadcast_to(np.asarray(pitch, dtype=np.float64), (n_items, K)))
+        n_items, K, M = self._psf_stack(psf, 'focus_psf_ee')
+        p = _f64(pitch, (n_items, K))
         r = np.asarray(radii, dtype=np.float64)
         Nr = int(r.shape[-1]) if r.ndim else 1
-        r = np.ascontiguousarray(np.broadcast_to(r, (n_items, K, Nr)))
-        c = None
-        if centers is not None:
-            c = np.ascontiguousarray(np.broadcast_to(np.asarray(centers, dtype=np.float64), (n_items, K, 2)))
+        r = _f64(r, (n_items, K, Nr))
+        c = _f64(centers, (n_items, K, 2)) if centers is not None else None
         ee = np.empty((n_items, K, Nr), dtype=np.float64)
         cen = np.empty((n_items, K, 2), dtype=np.float64) if want_centroid else None
         with t.cuda.device(self.device):
