@@ -765,6 +765,60 @@ int rox_focus_zernike(int32_t n_items, int32_t n_planes, const double *rows, int
                       const double *wave_scale, int32_t n_terms, const rox_zernike_term *terms,
                       double *coef, rox_zernike_stats *stats, void *stream);
 
+/* Beam footprints: per-surface reductions of the ROX_OUT_FULL packets of finished launches --
+ * how large the beam is on every interface, where it lands, how steeply it arrives and where
+ * rays are lost -- computed where the packets are (HBM).
+ *   trace_flags  the rox_opts.flags the packets were traced with; only ROX_FILTER_PHANTOMS is
+ *          read: it decides n_seg = rox_system_num_segments(sys, trace_flags) and which
+ *          interface a slot holds.
+ *   outs   HOST [n_items] of DEVICE pointers: the rox_out of each FULL launch (an item of
+ *          rox_trace_pupil_grids, a rox_trace_pupil_grid or rox_trace_rays call).  seg
+ *          [n_seg][10][ld], status, fail_surf and ld are read, of the first n_rays rays.
+ *   Records.  With nb[s] = the number of slots before interface s, ray r has nseg(r) records:
+ *          n_seg when its status is ROX_OK; 0 when fail_surf <= 0 (or not an interface);
+ *          nb[fail_surf - 1] + 1 when ROX_MISSED_SURFACE; nb[fail_surf] + 1 otherwise, the last
+ *          of those being the partial record [inc_pt, before_dir, 0, normal].  Slot k of ray r
+ *          is read only when k < nseg(r).  A full segment counts always, a partial record only
+ *          with ROX_FP_PARTIAL (the reference's `len(ray) > i` test in
+ *          vigcalc.max_aperture_at_surf, rayoptics/raytr/vigcalc.py:31-42); with
+ *          ROX_FP_OK_ONLY only rays with status ROX_OK count.
+ *   fp     optional, host or device [n_items][n_seg] rox_footprint.
+ *   half_width  HOST [n_seg], finite and > 0 (read only with maps).
+ *   maps   optional, host or device [n_items][n_seg][n_bins][n_bins] uint32:
+ *          numpy.histogram2d(x, y, bins=n_bins, range=[[-h, h], [-h, h]]) of the counted
+ *          records of the slot, h = half_width[k] (x is the first axis).  Edge j is
+ *          -h + j * (2h / n_bins) (one quotient, one product, one sum), the last edge h; a value
+ *          is placed by comparison with the edges: bins are half-open, the last one closed,
+ *          values outside are dropped.  n_bins in [1, 512].  Integer atomics: exact.
+ * fp and maps may not both be NULL.  n_items in [1, ROX_MAX_FOCUS_ITEMS], n_rays in
+ * [1, 2^28], ld >= n_rays.  No floating-point atomics: per-wave partial records merged in a fixed
+ * order (Chan / Golub / LeVeque for the centroid and the RMS); identical calls give bit-identical
+ * results, host and device destinations alike.  Argument errors return ROX_E_ARG naming the
+ * parameter and item before anything is enqueued and leave the outputs untouched.  Scratch is
+ * bounded per launch; larger jobs run as consecutive launches with the same results.
+ * Asynchronous on `stream` unless an output is host memory.                                 */
+#define ROX_FP_PARTIAL 1u
+#define ROX_FP_OK_ONLY 2u
+typedef struct rox_footprint {
+    int64_t n;               /* records counted                                              */
+    int64_t n_fail[5];       /* rays that failed at this slot's interface, by status (slot
+                                nb[fail_surf]; index 0 unused and 0); no flag changes it     */
+    int64_t n_inc;           /* segments in cos_inc_min / cos_inc_sum                        */
+    double min[2], max[2];   /* bounding box of (p.x, p.y); empty: +inf / -inf               */
+    double r2_max;           /* max of x*x + y*y (two products, one sum; no FMA): an exact
+                                selection, sqrt left to the caller; empty: -inf              */
+    double cx, cy;           /* centroid                                                     */
+    double rms_r;            /* sqrt(sum((x - cx)^2 + (y - cy)^2) / n)                       */
+    double cos_inc_min;      /* over full segments, slot k >= 1: min and sum of |b4 . nrml|, */
+    double cos_inc_sum;      /*   b4 = slot k-1's direction taken into slot k's frame by the
+                                rt (in its rt_order) of every interface in between           */
+    double cos_exit_min;     /* over full segments: min of |d . nrml|                        */
+} rox_footprint;             /* 144 bytes; cx .. cos_exit_min are NaN where nothing counted   */
+int rox_surface_footprints(rox_system *sys, uint32_t trace_flags, uint32_t fp_flags,
+                           int32_t n_items, const rox_out *outs, int64_t n_rays,
+                           rox_footprint *fp, const double *half_width, int32_t n_bins,
+                           uint32_t *maps, void *stream);
+
 /* chief-ray aiming ------------------------------------------------------- */
 /* One problem per (field, wavelength): trace.iterate_ray
  * (rayoptics/raytr/trace.py:313-415) as trace.aim_chief_ray calls it

@@ -196,6 +196,19 @@ class ZernikeStats(C.Structure):
                 ('fit', C.c_int32), ('reserved', C.c_int32)]
 
 
+class Footprint(C.Structure):
+    """rox_footprint: the beam of one item on one FULL-packet slot"""
+    _fields_ = [('n', C.c_int64), ('n_fail', C.c_int64 * 5), ('n_inc', C.c_int64),
+                ('min', C.c_double * 2), ('max', C.c_double * 2), ('r2_max', C.c_double),
+                ('cx', C.c_double), ('cy', C.c_double), ('rms_r', C.c_double),
+                ('cos_inc_min', C.c_double), ('cos_inc_sum', C.c_double), ('cos_exit_min', C.c_double)]
+
+
+FP_PARTIAL, FP_OK_ONLY = 1, 2
+MAX_FOOTPRINT_BINS = 512    # include/roxtrace.h rox_surface_footprints
+MAX_FOOTPRINT_RAYS = 1 << 28
+
+
 class Vig(C.Structure):
     _fields_ = [('fld', Field), ('start_dir', C.c_double * 2), ('unit_dir', C.c_double * 2),
                 ('xy', C.c_int32), ('wvl_idx', C.c_int32), ('stop_surf', C.c_int32),
@@ -223,6 +236,7 @@ assert C.sizeof(FocusStats) == 72
 assert C.sizeof(FocusPsfStats) == 32
 assert C.sizeof(ZernikeTerm) == 16
 assert C.sizeof(ZernikeStats) == 56
+assert C.sizeof(Footprint) == 144
 
 # every symbol include/roxtrace.h declares (checked by tests/test_abi.py) ...
 EXPORTS = ('rox_abi_version', 'rox_device_count', 'rox_set_device',
@@ -234,7 +248,7 @@ EXPORTS = ('rox_abi_version', 'rox_device_count', 'rox_set_device',
            'rox_pin_host_memory', 'rox_unpin_host_memory', 'rox_copy_async', 'rox_synchronize',
            'rox_spot_stats', 'rox_trace_through_focus', 'rox_trace_through_focus_grids',
            'rox_focus_psf', 'rox_focus_mtf', 'rox_focus_ee', 'rox_focus_psf_ee',
-           'rox_focus_zernike')
+           'rox_focus_zernike', 'rox_surface_footprints')
 # ... and the measurement / self-test helpers of include/roxtrace_diag.h
 DIAG_EXPORTS = ('rox_time_pupil_grid', 'rox_selftest_fp64', 'rox_diag_pack_launches')
 
@@ -307,6 +321,8 @@ def declare(lib):
     lib.rox_focus_zernike.restype = C.c_int
     lib.rox_focus_zernike.argtypes = [i32, i32, vp, i64, vp, P(Grid), vp, vp, i32, P(ZernikeTerm),
                                       vp, vp, vp]
+    lib.rox_surface_footprints.restype = C.c_int
+    lib.rox_surface_footprints.argtypes = [vp, C.c_uint32, C.c_uint32, i32, P(Out), i64, vp, vp, i32, vp, vp]
     lib.rox_time_pupil_grid.restype = C.c_int
     lib.rox_time_pupil_grid.argtypes = [vp, P(Field), P(Grid), i32, P(Opts),
                                         P(Out), vp, i32, P(dbl)]

@@ -1006,6 +1006,119 @@ def through_focus_map(opt_model, focs, flds=None, wvls=None, num_rays=21, xy=Non
                            image_pts.reshape(F, W, K, 2), host_rows, status)
 
 
+# ---- beam footprints on every surface ---------------------------------------------
+# the half width of a surface's map: its semi-diameter times this margin, so that the record that
+# set the semi-diameter lies strictly inside the last bin
+FOOTPRINT_MAP_MARGIN = 1.0 + 2.0 ** -20
+
+
+class BeamFootprints:
+    """what :func:`beam_footprints` returns.
+
+    ``records``       [F, W, n_seg] rox_footprint records (engine.FOOTPRINT_DTYPE)
+    ``slot_ifc``      [n_seg] the interface index of each slot
+    ``semi_diameter`` [n_seg] sqrt(max r2_max) over the items; 0 where no record was counted
+    ``bbox``          [n_seg, 2, 2] the union bounding box (min, max) x (x, y)
+    ``max_aoi``       [n_seg] the largest angle of incidence in degrees (NaN: none), produced by
+                      item ``max_aoi_item`` [n_seg, 2] = (field, wavelength) (-1: none)
+    ``lost_by_field`` [F, n_seg, 5] rays lost at each slot by status, summed over wavelengths;
+                      ``lost`` [n_seg, 5] their sum
+    ``maps``          [F, W, n_seg, B, B] or None; ``field_maps`` [F, n_seg, B, B] summed over
+                      wavelengths, ``union_map`` [n_seg, B, B] and ``overlap`` [n_seg, B, B] the
+                      number of fields that light each bin; ``half_width`` [n_seg] of the maps
+    ``results``       the device packets, with ``keep_packets``"""
+
+    def __init__(self, records, slot_ifc, n_ifcs, trace_flags, maps=None, half_width=None, results=None):
+        self.records = records
+        self.slot_ifc = np.asarray(slot_ifc)
+        self.n_ifcs = int(n_ifcs)
+        self.trace_flags = int(trace_flags)
+        self.results = results
+        F, W, n_seg = records.shape
+        flat = records.reshape(F * W, n_seg)
+        r2 = flat['r2_max'].max(axis=0)
+        self.semi_diameter = np.sqrt(np.where(r2 >= 0.0, r2, 0.0))
+        self.bbox = np.stack([flat['min'].min(axis=0), flat['max'].max(axis=0)], axis=1)
+        cmin = np.where(np.isnan(flat['cos_inc_min']), np.inf, flat['cos_inc_min'])
+        item = cmin.argmin(axis=0)
+        best = cmin.min(axis=0)
+        some = np.isfinite(best)
+        self.max_aoi = np.where(some, np.degrees(np.arccos(np.clip(np.where(some, best, 1.0), -1.0, 1.0))), np.nan)
+        self.max_aoi_item = np.where(some[:, None], np.stack([item // W, item % W], axis=1), -1)
+        self.lost_by_field = records['n_fail'].sum(axis=1)
+        self.lost = self.lost_by_field.sum(axis=0)
+        self.maps = maps
+        self.half_width = half_width
+        self.field_maps = self.union_map = self.overlap = None
+        if maps is not None:
+            self.field_maps = maps.astype(np.int64).sum(axis=1)
+            self.union_map = self.field_maps.sum(axis=0)
+            self.overlap = (self.field_maps > 0).sum(axis=0)
+
+    def clear_apertures(self, margin=0.0):
+        """the semi-diameter per interface index times (1 + margin), ready for
+        ``ifc.set_max_aperture`` (0 for an interface without a slot or a record); the model is
+        not touched"""
+        margin = float(margin)
+        if not (np.isfinite(margin) and margin >= 0.0):
+            raise ValueError(f'clear_apertures: margin {margin} is not finite and >= 0')
+        out = np.zeros(self.n_ifcs)
+        out[self.slot_ifc] = self.semi_diameter * (1.0 + margin)
+        return out
+
+
+def beam_footprints(opt_model, flds=None, wvls=None, num_rays=64, maps=0, check_apertures=False, partial=True,
+                    ok_only=False, keep_packets=False):
+    """The beam on every surface from a dense pupil grid, on the device: one FULL launch
+    (rox_trace_pupil_grids) over every (field, wavelength) -- ``num_rays`` x ``num_rays`` rays
+    over each field's vignetted pupil (the unit pupil box with apply_vignetting, as the spot
+    diagram figures trace it) -- whose packets stay in HBM, then one rox_surface_footprints call
+    over them: what vigcalc.set_clear_apertures asks of four rim rays per field
+    (rayoptics/raytr/vigcalc.py:31-63), asked of every ray.  ``maps`` > 0 adds a second call for
+    ``maps`` x ``maps`` histograms of the landing points per (field, wavelength, surface) over
+    [-h, h]^2, h = the surface's semi-diameter just found times FOOTPRINT_MAP_MARGIN (1 + 2^-20:
+    the farthest record falls inside the last bin, not on its closed edge); a surface without a
+    record gets h = 1.  ``partial`` / ``ok_only`` select the records as the entry documents.
+    Defaults as the through-focus maps: the fields of osp['fov'], the wavelengths of osp['wvls']
+    (a workloads.TableModel has no osp: pass them).  Returns :class:`BeamFootprints`."""
+    from .engine import make_opts
+    num_rays, maps = int(num_rays), int(maps)
+    if num_rays < 1 or num_rays * num_rays > abi.MAX_FOOTPRINT_RAYS:
+        raise ValueError(f'beam_footprints: num_rays {num_rays} outside [1, 16384]')
+    if not 0 <= maps <= abi.MAX_FOOTPRINT_BINS:
+        raise ValueError(f'beam_footprints: maps {maps} outside [0, {abi.MAX_FOOTPRINT_BINS}]')
+    flds, wvls, _fw, _sw, _ref = _map_spec(opt_model, flds, wvls, None, None,
+                                           wvls[0] if wvls is not None and len(wvls) else None, 'beam_footprints')
+    F, W = len(flds), len(wvls)
+    fs, wis, opts_list = [], [], []
+    eng = None
+    for fld in flds:
+        for wvl in wvls:
+            kw = dict(check_apertures=bool(check_apertures), apply_vignetting=True)
+            eng, f, wi, opts = _launch_setup(opt_model, fld, wvl, kw, abi.OUT_FULL)
+            fs.append(f)
+            wis.append(wi)
+            opts_list.append(opts)
+    flags = int(opts_list[0].flags)
+    if any(int(o.flags) != flags for o in opts_list):
+        raise ValueError('beam_footprints: the fields do not share their trace flags')
+    grid = make_grid((-1., -1.), (1., 1.), num_rays)
+    results = eng.trace_pupil_grids(fs, wis, grid, opts_list, want_pupil=False)
+    rec, _none = eng.surface_footprints(results, flags, partial=partial, ok_only=ok_only)
+    n_seg = rec.shape[1]
+    tbl = eng.table
+    slot_ifc = eng.slot_interfaces(flags)
+    hmaps = hw = None
+    if maps:
+        r2 = rec['r2_max'].max(axis=0)
+        hw = np.where(r2 > 0.0, np.sqrt(np.where(r2 > 0.0, r2, 1.0)) * FOOTPRINT_MAP_MARGIN, 1.0)
+        _rec, hmaps = eng.surface_footprints(results, flags, partial=partial, ok_only=ok_only, half_width=hw,
+                                             n_bins=maps, want_records=False)
+        hmaps = hmaps.reshape(F, W, n_seg, maps, maps)
+    return BeamFootprints(rec.reshape(F, W, n_seg), slot_ifc, tbl.n_ifcs, flags, hmaps, hw,
+                          results if keep_packets else None)
+
+
 # ---- MTF through focus ----------------------------------------------------------
 # the PSF stack through_focus_mtf holds at once: larger maps run rox_focus_psf / rox_focus_mtf
 # over consecutive groups of items (the results do not depend on the grouping)

@@ -21,6 +21,12 @@ namespace rox {
 // sets rox_last_error() from a printf format (roxtrace.hip) and returns code
 int host_fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 
+// the host copy of a system's rows (roxtrace.hip); n_ifcs receives their number
+const rox_surface *system_rows(const rox_system *sys, int32_t *n_ifcs);
+// m[i] = the FULL-packet slot of interface i (-1: a filtered phantom) and m[n_ifcs + i] = the
+// number of slots before it, with or without ROX_FILTER_PHANTOMS; n_seg = the number of slots
+void system_slot_map(const rox_system *sys, bool filter, std::vector<int32_t> &m, int32_t &n_seg);
+
 // Returns ROX_E_HIP with "<kHipWhere><expr>: <HIP error>" from the enclosing function when expr
 // fails.  Every translation unit that uses it defines kHipWhere, the prefix of its messages.
 #define HIP_TRY(expr)                                                                             \

@@ -1196,6 +1196,17 @@ void phase_consts(const rox_surface *rows, int N, const double *n_table, const d
 }  // namespace
 
 // ---------------------------------------------------------------------- C ABI
+const rox_surface *rox::system_rows(const rox_system *sys, int32_t *n_ifcs)
+{
+    *n_ifcs = sys->n_ifcs;
+    return sys->rows.data();
+}
+
+void rox::system_slot_map(const rox_system *sys, bool filter, std::vector<int32_t> &m, int32_t &n_seg)
+{
+    slot_map(sys, filter, m, n_seg);
+}
+
 extern "C" {
 
 int rox_abi_version(void) { return ROX_ABI_VERSION; }

@@ -144,6 +144,22 @@ FOCUS_PSF_STATS_DTYPE = np.dtype([(name, np.int64 if name == 'n' else np.float64
 assert FOCUS_PSF_STATS_DTYPE.itemsize == C.sizeof(abi.FocusPsfStats)
 
 
+# rox_footprint: what surface_footprints returns
+FOOTPRINT_DTYPE = np.dtype([('n', np.int64), ('n_fail', np.int64, (5,)), ('n_inc', np.int64),
+                            ('min', np.float64, (2,)), ('max', np.float64, (2,)), ('r2_max', np.float64),
+                            ('cx', np.float64), ('cy', np.float64), ('rms_r', np.float64),
+                            ('cos_inc_min', np.float64), ('cos_inc_sum', np.float64),
+                            ('cos_exit_min', np.float64)])
+assert FOOTPRINT_DTYPE.itemsize == C.sizeof(abi.Footprint)
+
+
+def footprint_view(records):
+    """the uint8 tensor [n_items, n_seg, 144] surface_footprints(on_device=True) returns -> a
+    FOOTPRINT_DTYPE array [n_items, n_seg] on the host"""
+    a = np.ascontiguousarray(records.cpu().numpy() if hasattr(records, 'cpu') else records)
+    return a.view(FOOTPRINT_DTYPE).reshape(a.shape[:-1])
+
+
 # rox_zernike_stats: what focus_zernike returns
 ZERNIKE_STATS_DTYPE = np.dtype([('n', np.int64), ('n_outside', np.int64), ('rms', np.float64),
                                 ('rms_residual', np.float64), ('pv_residual', np.float64),
@@ -1100,6 +1116,67 @@ class TraceEngine:
                                               c.ctypes.data if c is not None else None, ws.ctypes.data, J,
                                               z_arr, p_coef, p_stats, self._stream()), 'rox_focus_zernike')
         return coef, stats
+
+    def slot_interfaces(self, flags=0):
+        """the interface index of every FULL-packet slot: with ROX_FILTER_PHANTOMS in ``flags``
+        the phantom interfaces between object and image have none (raytrace.py:185-188)"""
+        N = self.table.n_ifcs
+        filt = bool(int(flags) & abi.FILTER_PHANTOMS)
+        return [i for i, row in enumerate(self.table.rows)
+                if not (filt and row.mode == abi.PHANTOM and 0 < i < N - 1)]
+
+    @_in_flight
+    def surface_footprints(self, results, trace_flags, partial=True, ok_only=False, half_width=None, n_bins=0,
+                           on_device=False, want_records=True):
+        """rox_surface_footprints over the FULL packets of finished launches (``results``: the list
+        of DeviceResult trace_pupil_grids(..., OUT_FULL) returns, or a single one, still in HBM;
+        ``trace_flags``: the rox_opts.flags they were traced with): per (item, slot) the count,
+        bounding box, largest radius squared, centroid, RMS radius, extreme cosines of incidence
+        and exit and the rays lost there.  ``partial``: the partial record of a BLOCKED / TIR /
+        EVANESCENT ray counts; ``ok_only``: only rays with status OK count.  With ``n_bins`` > 0,
+        ``half_width`` ([n_seg]) and numpy.histogram2d maps of the landing points over
+        [-half_width[k], half_width[k]]^2.  Returns ``(records, maps)``: a FOOTPRINT_DTYPE array
+        [n_items, n_seg] (None without ``want_records``) and uint32 [n_items, n_seg, n_bins,
+        n_bins] or None -- NumPy, or with ``on_device`` a torch uint8 tensor [n_items, n_seg, 144]
+        of the raw records (``footprint_view`` reads it on the host) and an int32 tensor of the
+        map's bit patterns."""
+        t = self.torch
+        if isinstance(results, DeviceResult):
+            results = [results]
+        results = list(results)
+        n_items = len(results)
+        if not 1 <= n_items <= abi.MAX_FOCUS_ITEMS:
+            raise EngineError(f'surface_footprints: 1 to {abi.MAX_FOCUS_ITEMS} items, got {n_items}')
+        n_seg = self.num_segments(int(trace_flags))
+        R = int(results[0].R)
+        for i, r in enumerate(results):
+            if r.out_mode != abi.OUT_FULL or int(r.seg.shape[0]) != n_seg or int(r.R) != R:
+                raise EngineError(f'surface_footprints: item {i} is not a FULL packet of {n_seg} segments and '
+                                  f'{R} rays')
+        n_bins = int(n_bins)
+        if not want_records and n_bins <= 0:
+            raise EngineError('surface_footprints: records or maps (or both)')
+        hw = None
+        if n_bins > 0:
+            if n_bins > abi.MAX_FOOTPRINT_BINS:
+                raise EngineError(f'surface_footprints: n_bins {n_bins} outside [1, {abi.MAX_FOOTPRINT_BINS}]')
+            if half_width is None:
+                raise EngineError('surface_footprints: maps need half_width')
+            hw = _f64(half_width, (n_seg,))
+            if not (np.isfinite(hw).all() and (hw > 0).all()):
+                raise EngineError('surface_footprints: half_width must be finite and > 0')
+        flags = (abi.FP_PARTIAL if partial else 0) | (abi.FP_OK_ONLY if ok_only else 0)
+        outs = (abi.Out * n_items)(*[r.out_struct() for r in results])
+        none = (None, None)
+        rec, p_rec = self._out(on_device, (n_items, n_seg), FOOTPRINT_DTYPE, t.uint8,
+                               (n_items, n_seg, C.sizeof(abi.Footprint))) if want_records else none
+        maps, p_maps = self._out(on_device, (n_items, n_seg, n_bins, n_bins), np.uint32, t.int32) \
+            if n_bins > 0 else none
+        with t.cuda.device(self.device):
+            _check(self.lib.rox_surface_footprints(self._handle, int(trace_flags), flags, n_items, outs, R,
+                                                   p_rec, hw.ctypes.data if hw is not None else None, n_bins,
+                                                   p_maps, self._stream()), 'rox_surface_footprints')
+        return rec, maps
 
     @_in_flight
     def focus_psf_ee(self, psf, pitch, centers, radii, want_centroid=True):
