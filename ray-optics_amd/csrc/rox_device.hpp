@@ -2759,25 +2759,18 @@ ROX_KERNEL_ALIGNED trace_kernel_batch(const BatchArgs b)
     trace_tiles<OUT_MODE, GEN_PUPIL, false, FEAT, SMALL>(items[blockIdx.y]);
 }
 
-// the through-focus kernel: pupil grids at one wavelength, regular workgroups only
-template <int FEAT>
-__global__ void __launch_bounds__(block_of(MODE_FOCUS, FEAT), min_waves_of(MODE_FOCUS, FEAT))
-ROX_KERNEL_ALIGNED focus_kernel(const FocusArgs a)
-{
-    trace_tiles<MODE_FOCUS, GEN_PUPIL, false, FEAT, false>(a);
-}
-
-// The batched through-focus kernel (rox_trace_through_focus_grids): blockIdx.y picks the item,
-// blockIdx.x strides over that item's tiles exactly as focus_kernel's workgroups do over the one
-// grid -- same workgroup count per item, each item's partial records indexed by blockIdx.x --
-// so every item's rows and statistics are those of its single call.  The items sit in device
+// The through-focus kernel (rox_trace_through_focus with one item, rox_trace_through_focus_grids
+// with several): pupil grids at one wavelength each, regular workgroups only.  blockIdx.y picks
+// the item, blockIdx.x strides over that item's tiles -- the workgroup count per item and the
+// partial records, indexed by blockIdx.x, depend on the item's grid alone, so an item's rows and
+// statistics are the same whichever items are launched beside it.  The items sit in device
 // memory and are read through the constant address space (trace_kernel_batch's scalar loads);
 // none travel in the kernel argument: the planes need an upload in front of the kernel anyway,
 // and the items ride in the same copy.
 typedef const __attribute__((address_space(4))) FocusArgs *ConstFocusArgs;
 template <int FEAT>
 __global__ void __launch_bounds__(block_of(MODE_FOCUS, FEAT), min_waves_of(MODE_FOCUS, FEAT))
-ROX_KERNEL_ALIGNED focus_kernel_batch(const FocusArgs *items)
+ROX_KERNEL_ALIGNED focus_kernel(const FocusArgs *items)
 {
     trace_tiles<MODE_FOCUS, GEN_PUPIL, false, FEAT, false>(((ConstFocusArgs)items)[blockIdx.y]);
 }
@@ -2857,24 +2850,13 @@ inline void launch_instance(const LaunchCfg &k, const TraceArgs &a)
         launch_mode<GEN_RAYS, false, FEAT>(k, a);
 }
 
-// the through-focus kernel of one feature instance (the table source of its reduced-output modes)
+// the through-focus kernel of one feature instance (the table source of its reduced-output
+// modes): `items` is a DEVICE array of k.grid.y FocusArgs
 template <int FEAT>
-inline void launch_instance_focus(const LaunchCfg &k, const FocusArgs &a)
+inline void launch_instance_focus(const LaunchCfg &k, const FocusArgs *items)
 {
     constexpr int FR = FEAT | gtab_of(FEAT, (FEAT & F_FAST) != 0, ROX_OUT_HITS);
     auto kern = focus_kernel<FR>;
-    if (k.lds > kDefaultDynLds)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds);
-    hipLaunchKernelGGL(kern, k.grid, dim3(block_of(MODE_FOCUS, FR)), k.lds, k.stream, a);
-}
-
-// ... and its batched form: `items` is a DEVICE array of k.grid.y FocusArgs
-template <int FEAT>
-inline void launch_instance_focus_batch(const LaunchCfg &k, const FocusArgs *items)
-{
-    constexpr int FR = FEAT | gtab_of(FEAT, (FEAT & F_FAST) != 0, ROX_OUT_HITS);
-    auto kern = focus_kernel_batch<FR>;
     if (k.lds > kDefaultDynLds)
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds);
@@ -2936,20 +2918,18 @@ inline void launch_instance_batch(const LaunchCfg &k, const TraceArgs *items)
     }
 }
 
-// The host entry points of one trace instance: the plain, batched, through-focus and batched
-// through-focus launches of launch_instance*<FEAT>.  ROX_TRACE_INSTANCE defines them as one table entry trace_<name>
+// The host entry points of one trace instance: the plain, batched and through-focus launches of
+// launch_instance*<FEAT>.  ROX_TRACE_INSTANCE defines them as one table entry trace_<name>
 // in the instance's own translation unit.  (The entries are not const: clang would emit a const
 // namespace-scope object into the device code object as well.)
 struct TraceInstanceFns {
     void (*launch)(const LaunchCfg &, const TraceArgs &);
     void (*batch)(const LaunchCfg &, const TraceArgs *);
-    void (*focus)(const LaunchCfg &, const FocusArgs &);
-    void (*focus_batch)(const LaunchCfg &, const FocusArgs *);
+    void (*focus)(const LaunchCfg &, const FocusArgs *);
 };
 #define ROX_TRACE_INSTANCE(name, FEAT)                                                          \
     TraceInstanceFns trace_##name = {launch_instance<FEAT>, launch_instance_batch<FEAT>, \
-                                     launch_instance_focus<FEAT>,                         \
-                                     launch_instance_focus_batch<FEAT>};
+                                     launch_instance_focus<FEAT>};
 
 // The feature instances that are compiled, X(name, FEAT) in kInstances order: one translation
 // unit each, csrc/inst_<name>.hip (trace_<name>), and a tolerance-mode twin csrc/fast_<name>.hip

@@ -48,7 +48,7 @@ __global__ void pupil_axes_kernel(double x0, double y0, double sx, double sy, in
     }
 }
 
-// ... the axes of several grid definitions at once (rox_trace_through_focus_grids): thread 2 s
+// ... the axes of several grid definitions at once (rox_trace_through_focus[_grids]): thread 2 s
 // walks slot s's x axis and thread 2 s + 1 its y axis, prm[s] = (x0, y0, sx, sy), into
 // axes[s][2][num] -- each value the same repeated `+=` as pupil_axes_kernel's
 __global__ void pupil_axes_slots_kernel(const double *prm, int n_slots, int num, double *axes)
@@ -223,18 +223,17 @@ struct StreamCtx {
     uint64_t *d_btiles = nullptr;       // ... and [items][tiles] look-back states
     int64_t btickets_cap = 0, btiles_cap = 0;
     uint32_t bepoch = 0;
-    // rox_trace_through_focus: planes, partial records and statistics of a call (grow-only)
+    // rox_trace_through_focus[_grids] (grow-only): the device block -- the pupil axes, then items,
+    // planes and axis parameters (copied in one transfer from the pinned block h_focus: the
+    // caller's arrays may be pageable and are free to go when the call returns), the statistics
+    // and the partial records of one launch
     char *d_focus = nullptr;
     size_t focus_cap = 0;
-    // ... and the pinned block the planes are copied from (the caller's array may be pageable
-    // and is free to go when the call returns)
     Staging h_focus;
-    // rox_trace_through_focus_grids (grow-only): the device block -- items, planes and axis
-    // parameters (copied in one transfer from the pinned block h_fbatch), then the pupil axes,
-    // the statistics and the partial records of one launch
-    char *d_fbatch = nullptr;
-    size_t d_fbatch_cap = 0;
-    Staging h_fbatch;
+    // ... the axis parameters and num of the axes at the head of the block (none after a regrow):
+    // a call that repeats them byte for byte does not walk the axes again
+    std::vector<double> focus_prm;
+    int32_t focus_num = 0;
     // Everything a pupil-grid call does between reading / rewriting the cached axes
     // (prepare_grid) and handing its launches to the stream is one critical section per
     // stream: two host threads enqueueing on the SAME stream take turns (their launches run
@@ -1107,7 +1106,7 @@ int prepare_grid(rox_system *sys, const rox_field *fld, const rox_grid *grid, in
 constexpr int kFocusBlocksPerCu = 2;
 constexpr int kFocusFinishBlock = 256;
 
-// the finishing pass: block k merges plane k's partial records -- thread t the records t, t + 256,
+// the finishing pass: a block merges one plane's partial records -- thread t the records t, t + 256,
 // ... in turn, then the lanes pairwise (the lower lane's first), then the four waves in order --
 // and forms its statistics
 __device__ inline FocusAcc shfl_xor_acc(const FocusAcc &a, int o)
@@ -1120,17 +1119,14 @@ __device__ inline FocusAcc shfl_xor_acc(const FocusAcc &a, int o)
     return r;
 }
 
-// BATCH (rox_trace_through_focus_grids): block (k, i) merges plane k of item i = blockIdx.y, whose
-// n_rec x n_planes records follow item i - 1's and whose statistics go to out[i][n_planes] --
-// within an item the very merges of a single call
-template <bool BATCH>
+// Block (k, i) merges plane k of item i = blockIdx.y, whose n_rec x n_planes records follow item
+// i - 1's and whose statistics go to out[i][n_planes]: an item's merges do not depend on the items
+// beside it
 __global__ void __launch_bounds__(kFocusFinishBlock)
 focus_finish_kernel(const FocusAcc *partial, int64_t n_rec, int32_t n_planes, rox_focus_stats *out)
 {
-    if (BATCH) {
-        partial += (size_t)blockIdx.y * n_rec * n_planes;
-        out += (size_t)blockIdx.y * n_planes;
-    }
+    partial += (size_t)blockIdx.y * n_rec * n_planes;
+    out += (size_t)blockIdx.y * n_planes;
     const int k = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     FocusAcc v{};
     for (int64_t i = threadIdx.x; i < n_rec; i += kFocusFinishBlock)
@@ -1415,10 +1411,6 @@ int rox_system_destroy(rox_system *sys)
         (void)hipHostFree(c->h_focus.h);
         if (c->h_focus.ev)
             (void)hipEventDestroy(c->h_focus.ev);
-        (void)hipFree(c->d_fbatch);
-        (void)hipHostFree(c->h_fbatch.h);
-        if (c->h_fbatch.ev)
-            (void)hipEventDestroy(c->h_fbatch.ev);
         for (hipEvent_t ev : c->item_ev)
             if (ev)
                 (void)hipEventDestroy(ev);
@@ -1505,182 +1497,35 @@ int rox_trace_pupil_grid(rox_system *sys, const rox_field *fld, const rox_grid *
     return rc ? rc : unstage_out(s, st);
 }
 
-// One trace of a pupil grid, evaluated at n_planes focus positions (include/roxtrace.h).
-int rox_trace_through_focus(rox_system *sys, const rox_field *fld, const rox_grid *grid,
-                            int32_t wvl_idx, const rox_opts *opts, int32_t n_planes,
-                            const rox_focus_plane *planes, double *rows, int64_t ld, uint8_t *status,
-                            rox_focus_stats *stats, void *stream)
-{
-    // every argument check comes before anything touches a device
-    if (!fld || !grid || !opts)
-        return fail(ROX_E_ARG, "rox_trace_through_focus: null argument");
-    ROX_TRY(check_range("rox_trace_through_focus", "n_planes", n_planes, 1, ROX_MAX_FOCUS_PLANES));
-    if (!planes)
-        return fail(ROX_E_ARG, "rox_trace_through_focus: planes is null");
-    if (!rows && !stats)
-        return fail(ROX_E_ARG, "rox_trace_through_focus: rows and stats are both null");
-    if (opts->out_mode != ROX_OUT_FAN)
-        return fail(ROX_E_ARG, "rox_trace_through_focus: out_mode must be ROX_OUT_FAN (got %d)", opts->out_mode);
-    if (opts->flags & (ROX_HOST_POINTERS | ROX_HITS_APPEND))
-        return fail(ROX_E_ARG, "rox_trace_through_focus: device pointers only, no ROX_HOST_POINTERS / "
-                               "ROX_HITS_APPEND");
-    if (grid->num < 1)
-        return fail(ROX_E_ARG, "rox_trace_through_focus: grid.num must be >= 1");
-    const int64_t R = grid->kind == ROX_GRID_FAN ? grid->num
-                    : (int64_t)(grid->row_count > 0 ? grid->row_count : grid->num) * grid->num;
-    if (rows && ld < R)
-        return fail(ROX_E_ARG, "rox_trace_through_focus: ld (%lld) < rays (%lld)", (long long)ld, (long long)R);
-    if (R > (int64_t(1) << 28))
-        return fail(ROX_E_UNSUPPORTED, "rox_trace_through_focus: %lld rays (max 2^28 per call)", (long long)R);
-    for (int32_t p = 0; p < n_planes; ++p) {
-        const rox_wavefront &w = planes[p].wf;
-        if (!(w.ref_radius != 0.0) || w.kind < ROX_WF_FINITE || w.kind > ROX_WF_INF_SPLIT)
-            return fail(ROX_E_ARG, "rox_trace_through_focus: plane %d: bad wf (ref_radius %g, kind %d)", p,
-                        w.ref_radius, w.kind);
-    }
-    if (!sys)
-        return fail(ROX_E_ARG, "rox_trace_through_focus: null system");
-    if (wvl_idx < 0 || wvl_idx >= sys->n_wvls)
-        return fail(ROX_E_ARG, "rox_trace_through_focus: wvl_idx %d out of range", wvl_idx);
+}  // extern "C"
 
-    hipStream_t st = (hipStream_t)stream;
-    auto enq = enqueue_lock(sys, st);
-    StreamCtx *cx = ctx_for(sys, st);
-    if (!cx)
-        return fail(ROX_E_NOMEM, "out of host memory");
-    // planes, then the partial records, then the statistics (when they go to host memory)
-    const int bs_max = block_of(MODE_FOCUS, F_ALL) > block_of(MODE_FOCUS, 0) ? block_of(MODE_FOCUS, F_ALL)
-                                                                               : block_of(MODE_FOCUS, 0);
-    const int64_t cap_blocks = (int64_t)sys->num_cus * kFocusBlocksPerCu;
-    const size_t b_planes = up256((size_t)n_planes * sizeof(rox_focus_plane));
-    const size_t b_part = stats ? (size_t)cap_blocks * (bs_max / 64) * n_planes * sizeof(FocusAcc) : 0;
-    const size_t b_stats = up256((size_t)n_planes * sizeof(rox_focus_stats));
-    const size_t need = b_planes + b_part + b_stats;
-    if (need > cx->focus_cap)
-        HIP_TRY(regrow(cx->d_focus, cx->focus_cap, need, need));
-    rox_focus_plane *d_planes = (rox_focus_plane *)cx->d_focus;
-    double *d_part = (double *)(cx->d_focus + b_planes);
-    rox_focus_stats *d_stats = (rox_focus_stats *)(cx->d_focus + b_planes + b_part);
+namespace {
 
-    // a FAN launch's arguments (plane 0 in rox_opts: prepare_grid validates them as such; the
-    // kernel reads planes[]); a stats-only call names the scratch as seg, which is never written
-    rox_opts o = *opts;
-    o.foc = planes[0].foc;
-    o.image_pt[0] = planes[0].image_pt[0];
-    o.image_pt[1] = planes[0].image_pt[1];
-    o.wf = planes[0].wf;
-    rox_out out{};
-    out.seg = rows ? rows : d_part;
-    out.ld = rows ? ld : R;
-    out.status = status;
-    FocusArgs f;
-    int rc = prepare_grid(sys, fld, grid, wvl_idx, &o, &out, st, f);
-    if (rc)
-        return rc;
-    LaunchCfg k;
-    int inst;
-    rc = launch_setup(sys, f, GEN_PUPIL, false, st, k, inst);
-    if (rc)
-        return rc;
-    f.out.seg = nullptr;
-    f.ray_base = 0;
-    f.in_ld = R;
-    f.planes = d_planes;
-    f.n_planes = n_planes;
-    f.focus_rows = rows;
-    f.partial = stats ? d_part : nullptr;
-    const int bs = block_of(MODE_FOCUS, kInstances[inst]);
-    int64_t blocks = (R + bs - 1) / bs;
-    if (blocks > cap_blocks)
-        blocks = cap_blocks;
-    k.grid = dim3((unsigned)blocks);
-    // (the block is made for ROX_MAX_FOCUS_PLANES planes at once)
-    HIP_TRY(cx->h_focus.acquire(sizeof(rox_focus_plane) * (size_t)n_planes,
-                                sizeof(rox_focus_plane) * ROX_MAX_FOCUS_PLANES));
-    memcpy(cx->h_focus.h, planes, sizeof(rox_focus_plane) * (size_t)n_planes);
-    HIP_TRY(hipMemcpyAsync(d_planes, cx->h_focus.h, sizeof(rox_focus_plane) * (size_t)n_planes,
-                           hipMemcpyHostToDevice, st));
-    HIP_TRY(cx->h_focus.record(st));
-    if (stats)      // every wave merges into its records: they start at n = 0
-        HIP_TRY(hipMemsetAsync(d_part, 0, (size_t)blocks * (bs / 64) * n_planes * sizeof(FocusAcc), st));
-    trace_fns(inst, k).focus(k, f);
-    HIP_TRY(hipGetLastError());
-    if (!stats)
-        return 0;
-    const bool dev_dst = is_device(stats);
-    hipLaunchKernelGGL(focus_finish_kernel<false>, dim3((unsigned)n_planes), dim3(kFocusFinishBlock), 0, st,
-                       (const FocusAcc *)d_part,
-                       blocks * (bs / 64), n_planes, dev_dst ? stats : d_stats);
-    HIP_TRY(hipGetLastError());
-    if (dev_dst)
-        return 0;
-    HIP_TRY(hipMemcpyAsync(stats, d_stats, sizeof(rox_focus_stats) * (size_t)n_planes, hipMemcpyDeviceToHost, st));
-    enq.unlock();
-    HIP_TRY(hipStreamSynchronize(st));
-    return 0;
-}
-
-// Partial records of one batched through-focus launch stay under this many bytes: an item of a
+// Partial records of one through-focus launch stay under this many bytes: an item of a
 // large grid at K = 256 holds 512 workgroups x 8 waves x 256 planes x 72 B = 75 MB of them, so
 // the host splits a batch into consecutive launches of whole items (each item's workgroups,
 // records and merges are the same either way).
 constexpr size_t kFocusBatchPartialBytes = size_t(256) << 20;
 
-// n_items through-focus scans in one launch (include/roxtrace.h): item i is rox_trace_through_focus
-// with flds[i], grids[i], wvl_idx[i], opts[i] and planes[i][n_planes].
-int rox_trace_through_focus_grids(rox_system *sys, int32_t n_items, const rox_field *flds,
-                                  const int32_t *wvl_idx, const rox_grid *grids, const rox_opts *opts,
-                                  int32_t n_planes, const rox_focus_plane *planes, double *rows,
-                                  int64_t ld, uint8_t *status, rox_focus_stats *stats, void *stream)
+// rays of one through-focus item (grid.num >= 1; grid_args checks the row block)
+int64_t focus_rays(const rox_grid &g)
 {
-    static const char kE[] = "rox_trace_through_focus_grids";
-    // every argument check comes before anything touches a device
-    ROX_TRY(check_range(kE, "n_items", n_items, 1, ROX_MAX_FOCUS_ITEMS));
-    ROX_TRY(check_range(kE, "n_planes", n_planes, 1, ROX_MAX_FOCUS_PLANES));
-    if (!flds || !wvl_idx || !grids || !opts || !planes)
-        return fail(ROX_E_ARG, "%s: null array (flds, wvl_idx, grids, opts or planes)", kE);
-    if (!rows && !stats)
-        return fail(ROX_E_ARG, "%s: rows and stats are both null", kE);
-    const rox_grid &g0 = grids[0];
-    if (g0.num < 1)
-        return fail(ROX_E_ARG, "%s: item 0: grid.num must be >= 1", kE);
-    const bool fan = g0.kind == ROX_GRID_FAN;
-    const int64_t R = fan ? g0.num : (int64_t)(g0.row_count > 0 ? g0.row_count : g0.num) * g0.num;
-    if ((rows || status) && ld < R)
-        return fail(ROX_E_ARG, "%s: ld (%lld) < rays (%lld)", kE, (long long)ld, (long long)R);
-    if (R > (int64_t(1) << 28))
-        return fail(ROX_E_UNSUPPORTED, "%s: %lld rays (max 2^28 per item)", kE, (long long)R);
-    const rox_opts &o0 = opts[0];
-    for (int32_t i = 0; i < n_items; ++i) {
-        const rox_grid &g = grids[i];
-        if (g.kind != g0.kind || g.num != g0.num ||
-            (!fan && (g.row_begin != g0.row_begin || g.row_count != g0.row_count)))
-            return fail(ROX_E_ARG, "%s: item %d: grid kind, num and row block must match item 0's", kE, i);
-        const rox_opts &o = opts[i];
-        if (o.out_mode != ROX_OUT_FAN)
-            return fail(ROX_E_ARG, "%s: item %d: out_mode must be ROX_OUT_FAN (got %d)", kE, i, o.out_mode);
-        if (o.flags & (ROX_HOST_POINTERS | ROX_HITS_APPEND))
-            return fail(ROX_E_ARG, "%s: item %d: device pointers only, no ROX_HOST_POINTERS / "
-                                   "ROX_HITS_APPEND", kE, i);
-        if (((o.flags ^ o0.flags) & (ROX_FILTER_PHANTOMS | ROX_FAST_FP64)) ||
-            o.first_surf != o0.first_surf || o.last_surf != o0.last_surf)
-            return fail(ROX_E_ARG, "%s: item %d: ROX_FILTER_PHANTOMS, ROX_FAST_FP64, first_surf and "
-                                   "last_surf must match item 0's", kE, i);
-        for (int32_t p = 0; p < n_planes; ++p) {
-            const rox_wavefront &w = planes[(size_t)i * n_planes + p].wf;
-            if (!(w.ref_radius != 0.0) || w.kind < ROX_WF_FINITE || w.kind > ROX_WF_INF_SPLIT)
-                return fail(ROX_E_ARG, "%s: item %d plane %d: bad wf (ref_radius %g, kind %d)", kE, i, p,
-                            w.ref_radius, w.kind);
-        }
-    }
-    if (!sys)
-        return fail(ROX_E_ARG, "%s: null system", kE);
-    for (int32_t i = 0; i < n_items; ++i)
-        if (wvl_idx[i] < 0 || wvl_idx[i] >= sys->n_wvls)
-            return fail(ROX_E_ARG, "%s: item %d: wvl_idx %d out of range", kE, i, wvl_idx[i]);
+    return g.kind == ROX_GRID_FAN ? g.num : (int64_t)(g.row_count > 0 ? g.row_count : g.num) * g.num;
+}
 
-    // the items, validated one by one as the single call validates its launch (plane 0 in
-    // rox_opts; a stats-only item names a dummy seg, which the kernel never writes)
+// What both through-focus entries do once their own argument checks have passed: n_items scans
+// (grids of one kind, num and row block, R rays each) in one launch, or in a few launches of
+// whole items.  A per-item failure of grid_args is returned as it stands, or behind
+// "<item_prefix>: item %d: " where the entry gives a prefix.
+int trace_focus_items(rox_system *sys, int32_t n_items, const rox_field *flds, const int32_t *wvl_idx,
+                      const rox_grid *grids, const rox_opts *opts, int32_t n_planes,
+                      const rox_focus_plane *planes, double *rows, int64_t ld, uint8_t *status,
+                      rox_focus_stats *stats, hipStream_t st, const char *item_prefix)
+{
+    // the items, validated one by one as a FAN launch's arguments are (plane 0 in rox_opts; the
+    // kernel reads planes[]); a stats-only item names a dummy seg, which the kernel never writes
+    const rox_grid &g0 = grids[0];
+    const int64_t R = focus_rays(g0);
     std::vector<FocusArgs> items((size_t)n_items);
     double dummy = 0.0;
     for (int32_t i = 0; i < n_items; ++i) {
@@ -1696,13 +1541,14 @@ int rox_trace_through_focus_grids(rox_system *sys, int32_t n_items, const rox_fi
         out.status = status ? status + (size_t)i * ld : nullptr;
         const int rc = grid_args(sys, &flds[i], &grids[i], wvl_idx[i], &o, &out, items[i]);
         if (rc) {
+            if (!item_prefix)
+                return rc;
             char msg[sizeof g_err];
             memcpy(msg, g_err, sizeof msg);
-            return fail(rc, "%s: item %d: %s", kE, i, msg);
+            return fail(rc, "%s: item %d: %s", item_prefix, i, msg);
         }
     }
 
-    hipStream_t st = (hipStream_t)stream;
     auto enq = enqueue_lock(sys, st);
     StreamCtx *cx = ctx_for(sys, st);
     if (!cx)
@@ -1738,22 +1584,26 @@ int rox_trace_through_focus_grids(rox_system *sys, int32_t n_items, const rox_fi
     }
     const int32_t n_slots = (int32_t)(prm.size() / 4);
 
-    // device block: [items][planes][axis parameters] (staged) [axes][statistics][partial records]
+    // device block: [axes] [items][planes][axis parameters] (staged) [statistics][partial records]
+    // -- the axes in front, where the same axis parameters and num put them again
+    const size_t b_axes = up256(sizeof(double) * 2 * (size_t)n_slots * g0.num);
     const size_t b_items = up256(sizeof(FocusArgs) * (size_t)n_items);
     const size_t b_planes = up256(sizeof(rox_focus_plane) * (size_t)n_items * n_planes);
     const size_t b_prm = up256(sizeof(double) * prm.size());
-    const size_t b_axes = up256(sizeof(double) * 2 * (size_t)n_slots * g0.num);
     const size_t b_stats = stats ? up256(sizeof(rox_focus_stats) * (size_t)n_items * n_planes) : 0;
     const size_t staged = b_items + b_planes + b_prm;
-    const size_t need = staged + b_axes + b_stats + item_part * (size_t)per_launch;
-    if (need > cx->d_fbatch_cap)
-        HIP_TRY(regrow(cx->d_fbatch, cx->d_fbatch_cap, need, need));
-    FocusArgs *d_items = (FocusArgs *)cx->d_fbatch;
-    rox_focus_plane *d_planes = (rox_focus_plane *)(cx->d_fbatch + b_items);
-    double *d_prm = (double *)(cx->d_fbatch + b_items + b_planes);
-    double *d_axes = (double *)(cx->d_fbatch + staged);
-    rox_focus_stats *d_stats = (rox_focus_stats *)(cx->d_fbatch + staged + b_axes);
-    char *d_part = cx->d_fbatch + staged + b_axes + b_stats;
+    const size_t need = b_axes + staged + b_stats + item_part * (size_t)per_launch;
+    if (need > cx->focus_cap) {
+        cx->focus_prm.clear();                  // the new block holds no axes
+        HIP_TRY(regrow(cx->d_focus, cx->focus_cap, need, need));
+    }
+    double *d_axes = (double *)cx->d_focus;
+    char *d_staged = cx->d_focus + b_axes;
+    FocusArgs *d_items = (FocusArgs *)d_staged;
+    rox_focus_plane *d_planes = (rox_focus_plane *)(d_staged + b_items);
+    double *d_prm = (double *)(d_staged + b_items + b_planes);
+    rox_focus_stats *d_stats = (rox_focus_stats *)(d_staged + staged);
+    char *d_part = d_staged + staged + b_stats;
 
     for (int32_t i = 0; i < n_items; ++i) {
         FocusArgs &f = items[i];
@@ -1769,16 +1619,23 @@ int rox_trace_through_focus_grids(rox_system *sys, int32_t n_items, const rox_fi
     }
 
     // stage through the pinned block (once the previous call's copy has read it), one copy
-    HIP_TRY(cx->h_fbatch.acquire(staged));
-    char *h = cx->h_fbatch.h;
+    HIP_TRY(cx->h_focus.acquire(staged));
+    char *h = cx->h_focus.h;
     memcpy(h, items.data(), sizeof(FocusArgs) * (size_t)n_items);
     memcpy(h + b_items, planes, sizeof(rox_focus_plane) * (size_t)n_items * n_planes);
     memcpy(h + b_items + b_planes, prm.data(), sizeof(double) * prm.size());
-    HIP_TRY(hipMemcpyAsync(cx->d_fbatch, h, staged, hipMemcpyHostToDevice, st));
-    HIP_TRY(cx->h_fbatch.record(st));
-    hipLaunchKernelGGL(pupil_axes_slots_kernel, dim3((unsigned)((2 * n_slots + 63) / 64)), dim3(64), 0, st,
-                       (const double *)d_prm, n_slots, g0.num, d_axes);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(d_staged, h, staged, hipMemcpyHostToDevice, st));
+    HIP_TRY(cx->h_focus.record(st));
+    // the axes, unless the block holds them from the previous call on this context
+    if (cx->focus_num != g0.num || cx->focus_prm.size() != prm.size() ||
+        memcmp(cx->focus_prm.data(), prm.data(), sizeof(double) * prm.size()) != 0) {
+        cx->focus_prm.clear();
+        hipLaunchKernelGGL(pupil_axes_slots_kernel, dim3((unsigned)((2 * n_slots + 63) / 64)), dim3(64), 0,
+                           st, (const double *)d_prm, n_slots, g0.num, d_axes);
+        HIP_TRY(hipGetLastError());
+        cx->focus_prm = prm;
+        cx->focus_num = g0.num;
+    }
 
     const bool dev_dst = stats && is_device(stats);
     for (int32_t i0 = 0; i0 < n_items; i0 += per_launch) {
@@ -1786,11 +1643,11 @@ int rox_trace_through_focus_grids(rox_system *sys, int32_t n_items, const rox_fi
         if (stats)      // every wave merges into its records: they start at n = 0
             HIP_TRY(hipMemsetAsync(d_part, 0, item_part * (size_t)n, st));
         k.grid = dim3((unsigned)blocks, (unsigned)n);
-        trace_fns(inst, k).focus_batch(k, d_items + i0);
+        trace_fns(inst, k).focus(k, d_items + i0);
         HIP_TRY(hipGetLastError());
         if (!stats)
             continue;
-        hipLaunchKernelGGL(focus_finish_kernel<true>, dim3((unsigned)n_planes, (unsigned)n),
+        hipLaunchKernelGGL(focus_finish_kernel, dim3((unsigned)n_planes, (unsigned)n),
                            dim3(kFocusFinishBlock), 0, st, (const FocusAcc *)d_part, n_rec, n_planes,
                            (dev_dst ? stats : d_stats) + (size_t)i0 * n_planes);
         HIP_TRY(hipGetLastError());
@@ -1802,6 +1659,108 @@ int rox_trace_through_focus_grids(rox_system *sys, int32_t n_items, const rox_fi
     enq.unlock();
     HIP_TRY(hipStreamSynchronize(st));
     return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+// One trace of a pupil grid, evaluated at n_planes focus positions (include/roxtrace.h).
+int rox_trace_through_focus(rox_system *sys, const rox_field *fld, const rox_grid *grid,
+                            int32_t wvl_idx, const rox_opts *opts, int32_t n_planes,
+                            const rox_focus_plane *planes, double *rows, int64_t ld, uint8_t *status,
+                            rox_focus_stats *stats, void *stream)
+{
+    // every argument check comes before anything touches a device
+    if (!fld || !grid || !opts)
+        return fail(ROX_E_ARG, "rox_trace_through_focus: null argument");
+    ROX_TRY(check_range("rox_trace_through_focus", "n_planes", n_planes, 1, ROX_MAX_FOCUS_PLANES));
+    if (!planes)
+        return fail(ROX_E_ARG, "rox_trace_through_focus: planes is null");
+    if (!rows && !stats)
+        return fail(ROX_E_ARG, "rox_trace_through_focus: rows and stats are both null");
+    if (opts->out_mode != ROX_OUT_FAN)
+        return fail(ROX_E_ARG, "rox_trace_through_focus: out_mode must be ROX_OUT_FAN (got %d)", opts->out_mode);
+    if (opts->flags & (ROX_HOST_POINTERS | ROX_HITS_APPEND))
+        return fail(ROX_E_ARG, "rox_trace_through_focus: device pointers only, no ROX_HOST_POINTERS / "
+                               "ROX_HITS_APPEND");
+    if (grid->num < 1)
+        return fail(ROX_E_ARG, "rox_trace_through_focus: grid.num must be >= 1");
+    const int64_t R = focus_rays(*grid);
+    if (rows && ld < R)
+        return fail(ROX_E_ARG, "rox_trace_through_focus: ld (%lld) < rays (%lld)", (long long)ld, (long long)R);
+    if (R > (int64_t(1) << 28))
+        return fail(ROX_E_UNSUPPORTED, "rox_trace_through_focus: %lld rays (max 2^28 per call)", (long long)R);
+    for (int32_t p = 0; p < n_planes; ++p) {
+        const rox_wavefront &w = planes[p].wf;
+        if (!(w.ref_radius != 0.0) || w.kind < ROX_WF_FINITE || w.kind > ROX_WF_INF_SPLIT)
+            return fail(ROX_E_ARG, "rox_trace_through_focus: plane %d: bad wf (ref_radius %g, kind %d)", p,
+                        w.ref_radius, w.kind);
+    }
+    if (!sys)
+        return fail(ROX_E_ARG, "rox_trace_through_focus: null system");
+    if (wvl_idx < 0 || wvl_idx >= sys->n_wvls)
+        return fail(ROX_E_ARG, "rox_trace_through_focus: wvl_idx %d out of range", wvl_idx);
+
+    return trace_focus_items(sys, 1, fld, &wvl_idx, grid, opts, n_planes, planes, rows, ld, status, stats,
+                             (hipStream_t)stream, nullptr);
+}
+
+// n_items through-focus scans in one launch (include/roxtrace.h): item i is rox_trace_through_focus
+// with flds[i], grids[i], wvl_idx[i], opts[i] and planes[i][n_planes] -- which is this with one item.
+int rox_trace_through_focus_grids(rox_system *sys, int32_t n_items, const rox_field *flds,
+                                  const int32_t *wvl_idx, const rox_grid *grids, const rox_opts *opts,
+                                  int32_t n_planes, const rox_focus_plane *planes, double *rows,
+                                  int64_t ld, uint8_t *status, rox_focus_stats *stats, void *stream)
+{
+    static const char kE[] = "rox_trace_through_focus_grids";
+    // every argument check comes before anything touches a device
+    ROX_TRY(check_range(kE, "n_items", n_items, 1, ROX_MAX_FOCUS_ITEMS));
+    ROX_TRY(check_range(kE, "n_planes", n_planes, 1, ROX_MAX_FOCUS_PLANES));
+    if (!flds || !wvl_idx || !grids || !opts || !planes)
+        return fail(ROX_E_ARG, "%s: null array (flds, wvl_idx, grids, opts or planes)", kE);
+    if (!rows && !stats)
+        return fail(ROX_E_ARG, "%s: rows and stats are both null", kE);
+    const rox_grid &g0 = grids[0];
+    if (g0.num < 1)
+        return fail(ROX_E_ARG, "%s: item 0: grid.num must be >= 1", kE);
+    const bool fan = g0.kind == ROX_GRID_FAN;
+    const int64_t R = focus_rays(g0);
+    if ((rows || status) && ld < R)
+        return fail(ROX_E_ARG, "%s: ld (%lld) < rays (%lld)", kE, (long long)ld, (long long)R);
+    if (R > (int64_t(1) << 28))
+        return fail(ROX_E_UNSUPPORTED, "%s: %lld rays (max 2^28 per item)", kE, (long long)R);
+    const rox_opts &o0 = opts[0];
+    for (int32_t i = 0; i < n_items; ++i) {
+        const rox_grid &g = grids[i];
+        if (g.kind != g0.kind || g.num != g0.num ||
+            (!fan && (g.row_begin != g0.row_begin || g.row_count != g0.row_count)))
+            return fail(ROX_E_ARG, "%s: item %d: grid kind, num and row block must match item 0's", kE, i);
+        const rox_opts &o = opts[i];
+        if (o.out_mode != ROX_OUT_FAN)
+            return fail(ROX_E_ARG, "%s: item %d: out_mode must be ROX_OUT_FAN (got %d)", kE, i, o.out_mode);
+        if (o.flags & (ROX_HOST_POINTERS | ROX_HITS_APPEND))
+            return fail(ROX_E_ARG, "%s: item %d: device pointers only, no ROX_HOST_POINTERS / "
+                                   "ROX_HITS_APPEND", kE, i);
+        if (((o.flags ^ o0.flags) & (ROX_FILTER_PHANTOMS | ROX_FAST_FP64)) ||
+            o.first_surf != o0.first_surf || o.last_surf != o0.last_surf)
+            return fail(ROX_E_ARG, "%s: item %d: ROX_FILTER_PHANTOMS, ROX_FAST_FP64, first_surf and "
+                                   "last_surf must match item 0's", kE, i);
+        for (int32_t p = 0; p < n_planes; ++p) {
+            const rox_wavefront &w = planes[(size_t)i * n_planes + p].wf;
+            if (!(w.ref_radius != 0.0) || w.kind < ROX_WF_FINITE || w.kind > ROX_WF_INF_SPLIT)
+                return fail(ROX_E_ARG, "%s: item %d plane %d: bad wf (ref_radius %g, kind %d)", kE, i, p,
+                            w.ref_radius, w.kind);
+        }
+    }
+    if (!sys)
+        return fail(ROX_E_ARG, "%s: null system", kE);
+    for (int32_t i = 0; i < n_items; ++i)
+        if (wvl_idx[i] < 0 || wvl_idx[i] >= sys->n_wvls)
+            return fail(ROX_E_ARG, "%s: item %d: wvl_idx %d out of range", kE, i, wvl_idx[i]);
+
+    return trace_focus_items(sys, n_items, flds, wvl_idx, grids, opts, n_planes, planes, rows, ld, status,
+                             stats, (hipStream_t)stream, kE);
 }
 
 // Several pupil grids of one system in ONE launch: item i traces `grid` for field flds[i]

@@ -252,6 +252,94 @@ def test_python_map_on_the_fixture(name):
                                       equal_nan=True), (name, f, w, j)
 
 
+def _device_stats_call(eng, fld, wi, grid, opts, planes, batched):
+    """a stats-only call with its statistics in a device tensor, through the single entry or as a
+    one-item batch: the raw bytes of the statistics"""
+    import torch
+    from rayoptics_amd.engine import load_library, FOCUS_STATS_DTYPE
+    lib = load_library()
+    K = len(planes)
+    dev = torch.zeros((K * FOCUS_STATS_DTYPE.itemsize,), dtype=torch.uint8, device=eng.device)
+    p_arr = (abi.FocusPlane * K)(*planes)
+    with torch.cuda.device(eng.device):
+        if batched:
+            rc = lib.rox_trace_through_focus_grids(
+                eng._handle, 1, C.byref(fld), (C.c_int32 * 1)(wi), C.byref(grid), C.byref(opts), K, p_arr,
+                None, 0, None, C.c_void_p(dev.data_ptr()), eng._stream())
+        else:
+            rc = lib.rox_trace_through_focus(
+                eng._handle, C.byref(fld), C.byref(grid), wi, C.byref(opts), K, p_arr,
+                None, 0, None, C.c_void_p(dev.data_ptr()), eng._stream())
+        assert rc == 0, lib.rox_last_error()
+        torch.cuda.synchronize()
+    return dev.cpu().numpy().tobytes()
+
+
+def test_single_and_batched_calls_share_one_workspace():
+    """both entries carve the same per-stream block: a single call of 13 x 13 rays (a partial last
+    wave) at K = 3, a batch of 4 items at K = 5 (rows and host statistics) and a stats-only single
+    call of 8 x 8 rays at K = 1 into a device tensor give the same rows, status and statistics
+    bytes whichever comes first on the engine's stream, and each single call equals item 0 of a
+    one-item batch -- rows-only and stats-only calls included"""
+    from rayoptics_amd.engine import TraceEngine, make_grid
+    tbl, flds, W = _workload('dblgauss_c2')
+    N = tbl.n_ifcs
+    opts = fan_opts(SPOT, N)
+    wfs = golden_wavefronts()
+    g13, g8 = make_grid((-1., -1.), (1., 1.), 13), make_grid((-0.9, -0.8), (0.7, 1.), 8)
+    p3, p1 = make_planes(3, wfs, seed=61), make_planes(1, wfs, seed=62)
+    fl, wi, p5 = items_of(flds, W, 4, 5, seed=63)
+    g4 = boxes(4, 21, seed=12)
+
+    def first(eng):
+        s, fr = eng.trace_pupil_grid_focus(flds[1], g13, 1, opts, p3, want_rows=True)
+        return fr.to_host() + (s.tobytes(),)
+
+    def second(eng):
+        s, fr = eng.trace_pupil_grids_focus(fl, wi, g4, [opts] * 4, p5, want_rows=True)
+        return fr.to_host() + (s.tobytes(),)
+
+    def third(eng):
+        return (_device_stats_call(eng, flds[2], 0, g8, opts, p1, batched=False),)
+
+    def same(a, b, what):
+        assert len(a) == len(b)
+        for x, y in zip(a, b):
+            if isinstance(x, bytes):
+                assert x == y, f'{what}: statistics differ'
+            else:
+                assert np.array_equal(x, y, equal_nan=x.dtype.kind == 'f'), f'{what}: rows or status differ'
+
+    calls = [first, second, third]
+    eng = TraceEngine(tbl)
+    forward = [c(eng) for c in calls]
+    eng.close()
+    eng = TraceEngine(tbl)
+    backward = [c(eng) for c in reversed(calls)][::-1]
+    for i, (a, b) in enumerate(zip(forward, backward)):
+        same(a, b, f'call {i + 1} in either order')
+    assert int((forward[0][1] == abi.OK).sum()) > 20 and int((forward[1][1] == abi.OK).sum()) > 200
+
+    # ... and the single entry == a batch of one item, on the workspace the calls above left
+    s, fr = eng.trace_pupil_grids_focus([flds[1]], [1], [g13], [opts], [p3], want_rows=True)
+    r, st = fr.to_host()
+    same(forward[0], (r[0], st[0], s[0].tobytes()), 'single call against a one-item batch')
+    assert forward[2][0] == _device_stats_call(eng, flds[2], 0, g8, opts, p1, batched=True)
+    _n, only_rows = eng.trace_pupil_grid_focus(flds[1], g13, 1, opts, p3, want_rows=True, want_stats=False)
+    _n, batch_rows = eng.trace_pupil_grids_focus([flds[1]], [1], [g13], [opts], [p3], want_rows=True,
+                                                 want_stats=False)
+    assert _n is None
+    same(only_rows.to_host(), tuple(x[0] for x in batch_rows.to_host()), 'rows-only call')
+    same(only_rows.to_host(), forward[0][:2], 'rows-only call against rows and statistics')
+    # the small call's host statistics right behind the batch, whose partial records were larger
+    same(second(eng), forward[1], 'the batch once more')
+    assert eng.trace_pupil_grid_focus(flds[2], g8, 0, opts, p1).tobytes() == forward[2][0]
+    only_stats = eng.trace_pupil_grid_focus(flds[1], g13, 1, opts, p3)
+    assert only_stats.tobytes() == forward[0][2]
+    assert only_stats.tobytes() == eng.trace_pupil_grids_focus([flds[1]], [1], [g13], [opts], [p3])[0].tobytes()
+    eng.close()
+
+
 def test_argument_errors_with_a_system_leave_the_stream_usable():
     """a wvl_idx outside the system's wavelengths names its item; nothing was enqueued, and the
     next call on the stream gives what it gives on its own"""
