@@ -1,7 +1,7 @@
 // rox_device.hpp -- device code of the sequential real-ray trace for gfx950
 // (MI355X, CDNA4): arithmetic, surface intersection, phase elements, packet
 // stores and the trace kernel template.  Included by every kernel-instance
-// translation unit (inst_*.hip) and by the host side (roxtrace.hip).
+// translation unit (inst_*.hip) and by the host side (launch.hip and the entry units).
 //
 // Hot path of mjhoptics/ray-optics restated as hand-written HIP (reference
 // paths relative to /root/reference/src/):
@@ -116,7 +116,7 @@
 // at every surface for its slowest wave with nothing else to run; four 256-thread workgroups
 // per CU, out of step with each other, avoid that (round 3, when these instances always ran
 // 256: phone lens 319 -> 290 us).  Since round 5 the choice is made per SYSTEM at launch
-// (roxtrace.hip want_small(): by the share of Newton interfaces): the large workgroup is the
+// (launch.hip want_small(): by the share of Newton interfaces): the large workgroup is the
 // regular one here too and the ROX_BLOCK_SMALL kernels are the alternative.
 #ifndef ROX_BLOCK_FULL_POLY
 #define ROX_BLOCK_FULL_POLY 1024
@@ -151,7 +151,7 @@ constexpr int kWaves = kBlock / 64;
 // (feat & kFeatNewton: the instance carries Newton code -- F_EVEN | F_RADIAL | F_TOROID)
 constexpr int kFeatNewton = 1 | 2 | 4;
 constexpr int kFeatFast = 64;       // F_FAST: a tolerance-mode instance (ROX_FAST_FP64; reduced-output modes only)
-// `small`: the launch does not fill the chip several times over (roxtrace.hip want_small()): it
+// `small`: the launch does not fill the chip several times over (launch.hip want_small()): it
 // runs in workgroups of ROX_BLOCK_SMALL threads, which spread over the CUs wave by wave instead
 // of sixteen (FULL) or eight waves at a time.  A CU holds 5 waves per SIMD of the lean FULL
 // instance (84 VGPRs) but only ONE 1024-thread workgroup (4 per SIMD); BASELINE configs[3]
@@ -2340,7 +2340,7 @@ __host__ __device__ inline int64_t compact_tiles(int64_t n_rays, int32_t want_sm
 // two passes over its lanes (butterfly sums), and one lane merges that into the wave's partial
 // record of the plane (Chan, Golub & LeVeque's pairwise update): an OPD of -472 waves that
 // varies by 0.02 keeps its RMS, which sum(w^2)/n - mean^2 loses in cancellation.  No atomics, a
-// fixed order of merges -- the finishing pass (roxtrace.hip) merges the records in index order
+// fixed order of merges -- the finishing pass (focus.hip) merges the records in index order
 // -- so two identical calls give bit-identical statistics.
 struct FocusAcc {
     double n;               // rays with status OK

@@ -1,7 +1,8 @@
 // rox_host.hpp -- host-side helpers shared by the translation units that define C entry points
-// (roxtrace.hip, spotstats.hip and the analyses psf.hip, mtf.hip, ee.hip, zernike.hip): the error
-// path and the argument checks, grow-only scratch blocks, scratch kept per (device, stream), the
-// pinned staging of host inputs and the carving of one workspace block.
+// (roxtrace.hip and the units its header lists, spotstats.hip and the analyses psf.hip, mtf.hip,
+// ee.hip, zernike.hip, footprint.hip): the error path and the argument checks, the environment
+// switches, grow-only scratch blocks, scratch kept per (device, stream), the pinned staging of
+// host inputs and the carving of one workspace block.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -10,6 +11,7 @@
 #include <cassert>
 #include <cmath>
 #include <cstdint>
+#include <cstdlib>
 #include <mutex>
 #include <new>
 #include <vector>
@@ -88,8 +90,22 @@ inline int check_centers(const char *e, int64_t total, const double *centers)
     return 0;
 }
 
+// ---- environment switches.  One that is "read once" initialises a function-local static const
+// with these; the documenting comment stays with the policy function that holds it.
+
+// the integer value of environment variable `name`; dflt when it is unset or empty
+inline long long env_int(const char *name, long long dflt)
+{
+    const char *e = getenv(name);
+    return (e && *e) ? atoll(e) : dflt;
+}
+
+// whether `name` is set to a non-zero integer
+inline bool env_flag(const char *name) { return env_int(name, 0) != 0; }
+
 // ---- sizes and pointers
 
+inline size_t up16(size_t b) { return (b + 15) & ~size_t(15); }
 inline size_t up256(size_t b) { return (b + 255) & ~size_t(255); }
 
 // Whether p is device memory.  A pointer HIP does not know (pageable host memory) is not, and

@@ -248,7 +248,7 @@ def test_full_packets_in_tolerance_mode_against_the_oracle(name):
 
 def test_full_tolerance_kernels_on_every_workload():
     """The host sends a FULL launch to the tolerance-mode kernels only for systems made mostly of
-    aspheres (roxtrace.hip use_fast(); of the workloads above: the phone lens) -- elsewhere they
+    aspheres (launch.hip use_fast(); of the workloads above: the phone lens) -- elsewhere they
     are slower than the store-bound exact kernels.  ROX_FAST_FP64_FULL=1 (read once by the
     library: a subprocess) sends every FULL launch with the flag there: the test above, on every
     workload, against the same bar; and the phone lens indeed runs on them by default (its

@@ -1,4 +1,4 @@
-"""-m gpu, round 5: the small-workgroup kernels (roxtrace.hip want_small) give the bytes the
+"""-m gpu, round 5: the small-workgroup kernels (launch.hip want_small) give the bytes the
 large-workgroup kernels give; the reworked asphere evaluation against the oracle at full size;
 many threads over more models than the session keeps handles for."""
 import os

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Workgroup size of a pupil launch vs launch size (roxtrace.hip want_small()).
+"""Workgroup size of a pupil launch vs launch size (launch.hip want_small()).
 
     ROX_SMALL_BLOCKS=0|1 python tools/block_rule_sweep.py [--shapes ...] >> profiles/r05_block_rule.jsonl
 
