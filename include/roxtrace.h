@@ -686,6 +686,45 @@ int rox_focus_ee(int32_t n_items, int32_t n_planes, const double *rows, int64_t 
                  int32_t n_frac, const double *fractions, double *ee_radius,
                  int64_t *n_ok, void *stream);
 
+/* Geometric MTF and line spread through focus: the OTF of the ray spot along given directions,
+ * and the histogram of the rays projected on them, for every plane of a through-focus scan.
+ *   rows, status  DEVICE [n_items][n_planes][3][ld] and [n_items][ld] (the through-focus
+ *          layouts): components 0 and 1 are x abr and y abr about the plane's image point.  Only
+ *          the first n_rays rays count, and of those only the ones with status ROX_OK; the rows
+ *          of a failed ray are never read.
+ *   dirs   HOST [n_items][n_dir][2] = (ex, ey), finite and not both zero; unit vectors are
+ *          expected but not checked.  u = ex*x + ey*y: two IEEE binary64 products and one sum,
+ *          no contraction into FMA, so (1, 0) and (0, 1) give exactly x and y.
+ *   freqs  HOST [n_freq], each finite and >= 0 (cycles per system unit), in any spacing; there
+ *          is no Nyquist limit (read only with otf).
+ *   otf    optional, host or device [n_items][n_planes][n_dir][n_freq][2] = (re, im):
+ *          OTF_d(nu) = (1/n) sum_ok exp(-2 pi i nu u), the phase convention of rox_focus_mtf
+ *          (the low-frequency phase is -2 pi nu times the spot centroid along the direction).
+ *          Per term t = nu*u (one product), r = t - rint(t) (exact), then sincospi(2 r);
+ *          re = sum cos and im = -sum sin, each reduced in a fixed order without atomics, then
+ *          one IEEE division by n.  nu = 0 gives exactly (1, 0).  NaN where n == 0.
+ *   edges  HOST [n_items][n_planes][n_dir][n_bins + 1], finite and strictly increasing per
+ *          (item, plane, direction) (read only with lsf).
+ *   lsf    optional, host or device [n_items][n_planes][n_dir][n_bins]: the number of OK rays
+ *          whose u lies in each bin as numpy.histogram(u, edges) decides it: half-open bins,
+ *          the last one closed, rays outside not counted.  Exact.
+ *   n_ok   optional, host or device [n_items][n_planes]: the OK ray count n.
+ * otf and lsf may not both be NULL.  n_items in [1, ROX_MAX_FOCUS_ITEMS], n_planes in
+ * [1, ROX_MAX_FOCUS_PLANES], n_rays in [1, ld], n_dir in [1, ROX_MAX_GMTF_DIRS], n_freq in
+ * [0, ROX_MAX_MTF_FREQS] (>= 1 with otf), n_bins in [0, ROX_MAX_LSF_BINS] (>= 1 with lsf).
+ * Identical calls give bit-identical results, host and device destinations alike.  Argument
+ * errors return ROX_E_ARG naming the parameter (and the index of a bad element) before anything
+ * is enqueued.  Scratch is bounded per launch; larger jobs run as consecutive launches with the
+ * same results.  Asynchronous on `stream` unless an output is host memory.                    */
+#define ROX_MAX_GMTF_DIRS   8
+#define ROX_MAX_LSF_BINS 4096
+int rox_focus_gmtf(int32_t n_items, int32_t n_planes, const double *rows, int64_t ld,
+                   const uint8_t *status, int64_t n_rays,
+                   int32_t n_dir, const double *dirs,
+                   int32_t n_freq, const double *freqs, double *otf,
+                   int32_t n_bins, const double *edges, int64_t *lsf,
+                   int64_t *n_ok, void *stream);
+
 /* Encircled energy through focus, diffraction: the fraction of every PSF rox_focus_psf writes
  * that lies within given radii.  Orientation as rox_focus_mtf: pixel (j, l) sits at image
  * (X, Y) = (-p (j - M/2), -p (l - M/2)) about the plane's image point, M = maxdim.

@@ -179,6 +179,8 @@ MAX_FOCUS_ITEMS = 1024      # include/roxtrace.h ROX_MAX_FOCUS_ITEMS
 MAX_MTF_FREQS = 1024        # include/roxtrace.h ROX_MAX_MTF_FREQS
 MAX_EE_RADII = 1024         # include/roxtrace.h ROX_MAX_EE_RADII
 MAX_EE_FRACTIONS = 64       # include/roxtrace.h ROX_MAX_EE_FRACTIONS
+MAX_GMTF_DIRS = 8           # include/roxtrace.h ROX_MAX_GMTF_DIRS
+MAX_LSF_BINS = 4096         # include/roxtrace.h ROX_MAX_LSF_BINS
 MAX_ZERNIKE_TERMS = 91      # include/roxtrace.h ROX_MAX_ZERNIKE_TERMS
 MAX_ZERNIKE_ORDER = 20      # include/roxtrace.h ROX_MAX_ZERNIKE_ORDER
 
@@ -247,7 +249,7 @@ EXPORTS = ('rox_abi_version', 'rox_device_count', 'rox_set_device',
            'rox_iterate_pupil_rays', 'rox_calc_psf',
            'rox_pin_host_memory', 'rox_unpin_host_memory', 'rox_copy_async', 'rox_synchronize',
            'rox_spot_stats', 'rox_trace_through_focus', 'rox_trace_through_focus_grids',
-           'rox_focus_psf', 'rox_focus_mtf', 'rox_focus_ee', 'rox_focus_psf_ee',
+           'rox_focus_psf', 'rox_focus_mtf', 'rox_focus_ee', 'rox_focus_gmtf', 'rox_focus_psf_ee',
            'rox_focus_zernike', 'rox_surface_footprints')
 # ... and the measurement / self-test helpers of include/roxtrace_diag.h
 DIAG_EXPORTS = ('rox_time_pupil_grid', 'rox_selftest_fp64', 'rox_diag_pack_launches')
@@ -316,6 +318,8 @@ def declare(lib):
     lib.rox_focus_mtf.argtypes = [i32, i32, vp, i32, vp, i32, vp, vp, vp]
     lib.rox_focus_ee.restype = C.c_int
     lib.rox_focus_ee.argtypes = [i32, i32, vp, i64, vp, i64, vp, i32, vp, vp, i32, vp, vp, vp, vp]
+    lib.rox_focus_gmtf.restype = C.c_int
+    lib.rox_focus_gmtf.argtypes = [i32, i32, vp, i64, vp, i64, i32, vp, i32, vp, vp, i32, vp, vp, vp, vp]
     lib.rox_focus_psf_ee.restype = C.c_int
     lib.rox_focus_psf_ee.argtypes = [i32, i32, vp, i32, vp, vp, i32, vp, vp, vp, vp]
     lib.rox_focus_zernike.restype = C.c_int

@@ -18,6 +18,8 @@
                         of a through_focus scan, from the rows in HBM (rox_focus_psf)
   through_focus_mtf  (new) the MTF through focus along image x and y, per field and
                         polychromatic, from the PSFs in HBM (rox_focus_mtf)
+  through_focus_gmtf (new) the geometric MTF and line spread through focus along any
+                        direction, from the rays in HBM (rox_focus_gmtf)
 """
 import numpy as np
 
@@ -1154,7 +1156,7 @@ def _default_pitch(opt_model, wvls, num_rays, maxdim, radii, shape, what):
     return np.array([[x[1] for x in xs] for xs in scal], dtype=np.float64).reshape(shape)
 
 
-def poly_otf_merge(otf, image_pts, spectral_wts, ref_index, freqs):
+def poly_otf_merge(otf, image_pts, spectral_wts, ref_index, freqs, dirs=None):
     """the polychromatic line OTFs [K, 2, Q] of one field from its per-wavelength OTFs.
 
     otf         [W, K, 2, Q] complex: each wavelength's line OTFs along image x and y, phase
@@ -1165,12 +1167,21 @@ def poly_otf_merge(otf, image_pts, spectral_wts, ref_index, freqs):
     poly_otf(nu) = sum_w s_w exp(-2 pi i nu D_w) OTF_w(nu) / sum_w s_w, D_w the component of
     image_pt_w - image_pt_ref along the direction, so lateral colour counts.  Entries whose OTF is
     NaN are skipped and the remaining weights renormalised; none left -> NaN.  One wavelength
-    gives its own OTF exactly (its weight is 1 and its phase factor exp(0) = 1)."""
+    gives its own OTF exactly (its weight is 1 and its phase factor exp(0) = 1).
+
+    ``dirs`` [D, 2] = (ex, ey): the OTFs are [W, K, D, Q] along these directions (the geometric
+    OTFs of rox_focus_gmtf) and D_w = ex * dx + ey * dy of image_pt_w - image_pt_ref.  None: x
+    and y."""
     otf = np.asarray(otf, dtype=np.complex128)
     W, K, _two, Q = otf.shape
     ip = np.asarray(image_pts, dtype=np.float64).reshape(W, K, 2)
     nu = np.asarray(freqs, dtype=np.float64).reshape(Q)
     delta = ip - ip[ref_index][None]                                    # [W, K, 2]
+    if dirs is not None:
+        e = np.asarray(dirs, dtype=np.float64).reshape(-1, 2)
+        if e.shape[0] != otf.shape[2]:
+            raise ValueError(f'poly_otf_merge: {e.shape[0]} directions for OTFs along {otf.shape[2]}')
+        delta = e[:, 0] * delta[..., 0:1] + e[:, 1] * delta[..., 1:2]   # [W, K, D]
     shifted = np.exp(-2j * np.pi * delta[..., None] * nu) * otf          # [W, K, 2, Q]
     ok = ~np.isnan(otf)
     s = np.where(ok, np.asarray(spectral_wts, dtype=np.float64).reshape(W, 1, 1, 1), 0.0)
@@ -1318,6 +1329,225 @@ def through_focus_mtf(opt_model, focs, freqs, flds=None, wvls=None, num_rays=32,
             out_psf = np.concatenate(psfs).reshape(F, W, K, maxdim, maxdim)
     return ThroughFocusMTF(focs, nu, wvls, field_wts, spectral_wts, ref_wvl, otf, pitch, image_pts, strehl,
                            out_psf)
+
+
+# ---- geometric MTF and line spread through focus -------------------------------------------
+def gmtf_directions(directions, image_pts_ref):
+    """the direction vectors [F, D, 2] of :func:`through_focus_gmtf`: each of ``directions`` is
+    'x' = (1, 0), 'y' = (0, 1), 't' (tangential: the unit vector from the axis to the field's
+    image point ``image_pts_ref[f]``, (0, 1) for a field on the axis), 's' (sagittal:
+    (t_y, -t_x)) or an explicit (ex, ey), taken as given -- a unit vector keeps the frequencies in
+    cycles per system unit.  Returns (dirs, labels)."""
+    what = 'through_focus_gmtf'
+    if isinstance(directions, str):
+        directions = (directions,)
+    directions = list(directions)
+    if not 1 <= len(directions) <= abi.MAX_GMTF_DIRS:
+        raise ValueError(f'{what}: 1 to {abi.MAX_GMTF_DIRS} directions, got {len(directions)}')
+    ip = np.asarray(image_pts_ref, dtype=np.float64).reshape(-1, 2)
+    F = ip.shape[0]
+    r = np.hypot(ip[:, 0], ip[:, 1])
+    on_axis = ~(r > 0)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        t = np.where(on_axis[:, None], np.array([0.0, 1.0]), ip / r[:, None])
+    sag = np.stack([t[:, 1], -t[:, 0]], axis=-1) + 0.0                  # (+ 0.0: no -0)
+    dirs = np.empty((F, len(directions), 2))
+    labels = []
+    for d, spec in enumerate(directions):
+        if isinstance(spec, str):
+            if spec not in ('x', 'y', 't', 's'):
+                raise ValueError(f"{what}: a direction is 'x', 'y', 't', 's' or (ex, ey), got {spec!r}")
+            dirs[:, d] = {'x': np.array([1.0, 0.0]), 'y': np.array([0.0, 1.0]), 't': t, 's': sag}[spec]
+            labels.append(spec)
+            continue
+        try:
+            v = np.asarray(spec, dtype=np.float64)
+        except (TypeError, ValueError):
+            v = np.empty(0)
+        if v.shape != (2,) or not np.isfinite(v).all() or not v.any():
+            raise ValueError(f"{what}: a direction is 'x', 'y', 't', 's' or a finite non-zero (ex, ey), got {spec!r}")
+        dirs[:, d] = v
+        labels.append((float(v[0]), float(v[1])))
+    return dirs, labels
+
+
+def lsf_edges(center, half_width, bins):
+    """[..., bins + 1] edges of ``bins`` equal bins over center -+ half_width"""
+    c = np.asarray(center, dtype=np.float64)[..., None]
+    h = np.asarray(half_width, dtype=np.float64)[..., None]
+    return c + h * np.linspace(-1.0, 1.0, int(bins) + 1)
+
+
+def poly_lsf_merge(lsf, n_ok, spectral_wts):
+    """[W, K, D, B] ray counts per bin and [W, K] ray totals of one field ->
+    sum_w s_w lsf_w / n_w / sum_w s_w [K, D, B], the unit-energy line spread whose transform
+    :func:`poly_otf_merge` gives; wavelengths with no ray are skipped and the rest renormalised,
+    none left -> NaN"""
+    lsf = np.asarray(lsf, dtype=np.float64)
+    n = np.asarray(n_ok, dtype=np.float64)
+    W = n.shape[0]
+    s = np.where(n > 0, np.asarray(spectral_wts, dtype=np.float64).reshape(W, 1), 0.0)     # [W, K]
+    total = s.sum(axis=0)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        per = np.where(n[..., None, None] > 0, lsf / n[..., None, None], 0.0)
+        out = (s[..., None, None] * per).sum(axis=0) / total[:, None, None]
+    return np.where(total[:, None, None] > 0, out, np.nan)
+
+
+class ThroughFocusGMTF:
+    """what :func:`through_focus_gmtf` returns.
+
+    focs, freqs, wvls, field_wts, spectral_wts, ref_wvl, directions   as used
+    dirs        [F, D, 2] each field's direction vectors (ex, ey)
+    otf         [F, W, K, D, Q] complex: the geometric OTF of each spot along each direction --
+                rox_focus_gmtf: the mean of exp(-2 pi i nu u) over the rays, u = ex x + ey y about
+                the plane's image point; NaN on planes no ray reached
+    mtf         [F, W, K, D, Q] abs(otf)
+    n_ok        [F, W, K] OK rays per plane
+    image_pts   [F, W, K, 2] each plane's image point
+    poly_otf / poly_mtf [F, K, D, Q]: :func:`poly_otf_merge` of each field's wavelengths along
+                its directions
+    best_focus  [F, D, Q] (+ ``_kind``): :func:`best_focus` of -poly_mtf per field, direction
+                and frequency
+    best_focus_all [Q] (+ ``_kind``): the same of the field-weighted mean over the directions
+    tangential / sagittal [F, K, Q]: poly_mtf along 't' / 's', for every field (None when that
+                direction was not asked for)
+    With ``lsf_bins`` (else None):
+    lsf         [F, W, K, D, B] ray counts per bin
+    lsf_edges   [F, K, D, B + 1] the bin edges along each direction, in the reference
+                wavelength's coordinates (about its image point)
+    poly_lsf    [F, K, D, B] :func:`poly_lsf_merge` of each field's wavelengths: the fraction of
+                the light in each bin
+    esf         [F, K, D, B] its cumulative sum (the edge spread at each bin's right edge)
+    lsf_inside  [F, K, D] the fraction of the light inside the edges"""
+
+    def __init__(self, focs, freqs, wvls, field_wts, spectral_wts, ref_wvl, directions, dirs, otf, n_ok,
+                 image_pts, lsf=None, lsf_edges=None):
+        self.focs = np.asarray(focs, dtype=np.float64)
+        self.freqs = np.asarray(freqs, dtype=np.float64)
+        self.wvls = list(wvls)
+        self.field_wts = np.asarray(field_wts, dtype=np.float64)
+        self.spectral_wts = np.asarray(spectral_wts, dtype=np.float64)
+        self.ref_wvl = ref_wvl
+        self.directions = list(directions)
+        self.dirs = np.asarray(dirs, dtype=np.float64)
+        self.otf = otf
+        self.mtf = np.abs(otf)
+        self.n_ok = n_ok
+        self.image_pts = image_pts
+        F, _W, K, D, Q = otf.shape
+        ref = self.wvls.index(ref_wvl)
+        self.poly_otf = np.stack([poly_otf_merge(otf[f], image_pts[f], self.spectral_wts, ref, self.freqs,
+                                                 dirs=self.dirs[f]) for f in range(F)])
+        self.poly_mtf = np.abs(self.poly_otf)
+        self.best_focus = np.empty((F, D, Q))
+        self.best_focus_kind = np.empty((F, D, Q), dtype=object)
+        for f in range(F):
+            for d in range(D):
+                for q in range(Q):
+                    self.best_focus[f, d, q], self.best_focus_kind[f, d, q] = best_focus(
+                        self.focs, -self.poly_mtf[f, :, d, q])
+        mean = self.poly_mtf.mean(axis=2)                                   # [F, K, Q] every direction
+        wt = self.field_wts[:, None, None]
+        curve = (wt * mean).sum(axis=0) / self.field_wts.sum()              # [K, Q]
+        res = [best_focus(self.focs, -curve[:, q]) for q in range(Q)]
+        self.best_focus_all = np.array([r[0] for r in res])
+        self.best_focus_all_kind = np.array([r[1] for r in res], dtype=object)
+        self.lsf = lsf
+        self.lsf_edges = lsf_edges
+        self.poly_lsf = self.esf = self.lsf_inside = None
+        if lsf is not None:
+            self.poly_lsf = np.stack([poly_lsf_merge(lsf[f], n_ok[f], self.spectral_wts) for f in range(F)])
+            self.esf = np.cumsum(self.poly_lsf, axis=-1)
+            self.lsf_inside = self.poly_lsf.sum(axis=-1)
+
+    def _along(self, label):
+        if label not in self.directions:
+            return None
+        return self.poly_mtf[:, :, self.directions.index(label), :]
+
+    @property
+    def tangential(self):
+        """[F, K, Q] the polychromatic MTF along each field's tangential direction"""
+        return self._along('t')
+
+    @property
+    def sagittal(self):
+        """[F, K, Q] the polychromatic MTF along each field's sagittal direction"""
+        return self._along('s')
+
+
+def through_focus_gmtf(opt_model, focs, freqs, flds=None, wvls=None, num_rays=64,
+                       directions=('x', 'y', 't', 's'), lsf_bins=0, lsf_half_width=None, field_wts=None,
+                       spectral_wts=None, ref_wvl=None, **kwargs):
+    """The geometric MTF through focus -- the transform of the ray spot, the tool for a lens far
+    from the diffraction limit -- of every field at every wavelength, and its polychromatic merge
+    per field, on the device: one rox_trace_through_focus_grids launch traces each item's square
+    pupil grid (``num_rays`` across) and evaluates it at every focus, and one rox_focus_gmtf call
+    sums exp(-2 pi i nu u) over the rows in HBM, at any ``freqs`` (cycles per system unit; no
+    Nyquist limit) and along any ``directions`` (:func:`gmtf_directions`: 'x', 'y', 't', 's' or
+    (ex, ey); 't' of a field points from the axis to its image point at ``ref_wvl`` and the focus
+    nearest 0).  Fields, wavelengths and weights default as in :func:`through_focus_map`.
+
+    ``lsf_bins`` > 0 adds the line spread function: the rays of each plane binned along each
+    direction into ``lsf_bins`` equal bins over -+ ``lsf_half_width`` about the field's
+    polychromatic spot centroid (:func:`poly_merge`, lateral colour included); the default half
+    width is 3 times the field's largest polychromatic RMS spot over the foci.
+    Returns a :class:`ThroughFocusGMTF`."""
+    from .engine import grid_rays
+    what = 'through_focus_gmtf'
+    focs = _check_focs(focs, what)
+    nu = _check_freqs(freqs, what)
+    num_rays = int(num_rays)
+    if num_rays < 1:
+        raise ValueError(f'{what}: num_rays must be >= 1, got {num_rays}')
+    lsf_bins = int(lsf_bins)
+    if not 0 <= lsf_bins <= abi.MAX_LSF_BINS:
+        raise ValueError(f'{what}: lsf_bins {lsf_bins} outside [0, {abi.MAX_LSF_BINS}]')
+    if lsf_half_width is not None:
+        hw = np.asarray(lsf_half_width, dtype=np.float64)
+        if hw.ndim > 1 or not (np.isfinite(hw).all() and (hw > 0).all()):
+            raise ValueError(f'{what}: lsf_half_width must be finite and > 0 (one, or one per field)')
+    gmtf_directions(directions, [(0.0, 0.0)])                               # checked before any device work
+    flds, wvls, field_wts, spectral_wts, ref_wvl = _map_spec(opt_model, flds, wvls, field_wts, spectral_wts,
+                                                             ref_wvl, what)
+    F, W, K = len(flds), len(wvls), len(focs)
+    if lsf_half_width is not None and hw.ndim == 1 and hw.size != F:
+        raise ValueError(f'{what}: lsf_half_width must be finite and > 0 (one, or one per field)')
+    s = np.asarray(spectral_wts, dtype=np.float64)
+    eng, fs, wis, grids, opts_list, planes = _map_items(opt_model, flds, wvls, focs, None, num_rays, kwargs)
+    R = grid_rays(grids[0])
+    image_pts = _image_pts(planes).reshape(F, W, K, 2)
+    ref = wvls.index(ref_wvl)
+    k0 = int(np.argmin(np.abs(focs)))
+    dirs, labels = gmtf_directions(directions, image_pts[:, ref, k0])
+    D = len(labels)
+    stats, dev_rows = eng.trace_pupil_grids_focus(fs, wis, grids, opts_list, planes, want_rows=True)
+    item_dirs = np.repeat(dirs, W, axis=0)                                  # [F W, D, 2]
+    edges = ref_edges = None
+    if lsf_bins:
+        stats = stats.reshape(F, W, K)
+        pm = [poly_merge(stats[f], image_pts[f], s, ref) for f in range(F)]
+        C = np.stack([np.stack([m['cx'], m['cy']], axis=-1) for m in pm])   # [F, K, 2] absolute
+        if lsf_half_width is None:
+            rms = [m['rms_spot'][np.isfinite(m['rms_spot'])] for m in pm]
+            hw = 3.0 * np.array([r.max() if r.size else np.nan for r in rms])
+            if not (np.isfinite(hw).all() and (hw > 0).all()):
+                raise ValueError(f'{what}: no default lsf_half_width for a field whose spot has no size: pass one')
+        hw = np.broadcast_to(hw, (F,))
+        about = np.nan_to_num(C - image_pts[:, ref])                        # [F, K, 2] in ref coordinates
+        center = dirs[:, None, :, 0] * about[:, :, None, 0] + dirs[:, None, :, 1] * about[:, :, None, 1]
+        ref_edges = lsf_edges(center, hw[:, None, None], lsf_bins)          # [F, K, D, B + 1]
+        # each wavelength's rows are about its own image point
+        delta = image_pts - image_pts[:, ref][:, None]                      # [F, W, K, 2]
+        shift = dirs[:, None, None, :, 0] * delta[..., None, 0] + dirs[:, None, None, :, 1] * delta[..., None, 1]
+        edges = (ref_edges[:, None] - shift[..., None]).reshape(F * W, K, D, lsf_bins + 1)
+        if not (np.diff(edges, axis=-1) > 0).all():
+            raise ValueError(f'{what}: lsf_half_width {hw} over {lsf_bins} bins gives no increasing edges')
+    otf, lsf, n_ok = eng.focus_gmtf(dev_rows, R, item_dirs, nu, edges=edges)
+    return ThroughFocusGMTF(focs, nu, wvls, field_wts, spectral_wts, ref_wvl, labels, dirs,
+                            otf.reshape(F, W, K, D, nu.size), n_ok.reshape(F, W, K), image_pts,
+                            lsf=None if lsf is None else lsf.reshape(F, W, K, D, lsf_bins), lsf_edges=ref_edges)
 
 
 # ---- encircled energy through focus ---------------------------------------------------------

@@ -41,6 +41,7 @@
 #include <cstdint>
 #include <cstring>
 
+#include "rox_bins.hpp"
 #include "rox_host.hpp"
 
 namespace {
@@ -93,20 +94,7 @@ __device__ __forceinline__ int first_edge(const double *e, int n, double d2)
     return lo;
 }
 
-// adds 1 per lane to h[b] for every lane with b >= 0: lanes of the same bin merge first
-__device__ __forceinline__ void wave_count(uint32_t *h, int b)
-{
-    const int lane = threadIdx.x & 63;
-    uint64_t todo = __ballot(b >= 0);
-    while (todo) {
-        const int lead = __builtin_ctzll(todo);
-        const int bl = __shfl(b, lead);
-        const uint64_t same = __ballot(b == bl) & todo;
-        if (lane == lead)
-            atomicAdd(&h[bl], (uint32_t)__popcll(same));
-        todo &= ~same;
-    }
-}
+using rox::wave_count;
 
 // ---- geometric ----------------------------------------------------------------------------------
 struct RayArgs {

@@ -1,0 +1,56 @@
+// rox_bins.hpp -- device helpers shared by the units that histogram rays (spotstats.hip, ee.hip,
+// gmtf.hip): the bin decision of numpy.histogram with explicit edges, and the wave-merged integer
+// count.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+namespace rox {
+
+// bin of v among edges e[0..n] as numpy.histogram with explicit edges decides it:
+// searchsorted(e, v, 'right') - 1, the right-most edge belonging to the last bin; -1 = outside
+__device__ __forceinline__ int bin_of(const double *e, int n, double v)
+{
+    if (!(v >= e[0]) || !(v <= e[n]))
+        return -1;                              // (NaN included)
+    int lo = 0, hi = n;                         // invariant: e[lo] <= v, (hi == n or v < e[hi])
+    // uniform edges (linspace): the proportional guess is right or one off -- two probes
+    const double w = e[n] - e[0];
+    const double t = w > 0.0 ? (v - e[0]) / w * n : 0.0;
+    int g = t < (double)(n - 1) ? (int)t : n - 1;
+    if (e[g] <= v) {
+        lo = g;
+        if (g + 1 <= n && (g + 1 == n || v < e[g + 1]))
+            return g;
+    } else {
+        hi = g;
+    }
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (e[mid] <= v)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+
+// adds 1 per lane to h[b] for every lane with b >= 0: lanes of the same bin merge first.  Every
+// lane of the wave must call it.
+__device__ __forceinline__ void wave_count(uint32_t *h, int b)
+{
+    const int lane = threadIdx.x & 63;
+    uint64_t todo = __ballot(b >= 0);
+    while (todo) {
+        const int lead = __builtin_ctzll(todo);
+        const int bl = __shfl(b, lead);
+        const uint64_t same = __ballot(b == bl) & todo;
+        if (lane == lead)
+            atomicAdd(&h[bl], (uint32_t)__popcll(same));
+        todo &= ~same;
+    }
+}
+
+}  // namespace rox

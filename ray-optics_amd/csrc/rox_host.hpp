@@ -1,6 +1,6 @@
 // rox_host.hpp -- host-side helpers shared by the translation units that define C entry points
 // (roxtrace.hip and the units its header lists, spotstats.hip and the analyses psf.hip, mtf.hip,
-// ee.hip, zernike.hip, footprint.hip): the error path and the argument checks, the environment
+// ee.hip, gmtf.hip, zernike.hip, footprint.hip): the error path and the argument checks, the environment
 // switches, grow-only scratch blocks, scratch kept per (device, stream), the pinned staging of
 // host inputs and the carving of one workspace block.
 #pragma once
@@ -87,6 +87,42 @@ inline int check_centers(const char *e, int64_t total, const double *centers)
         for (int64_t i = 0; i < 2 * total; ++i)
             if (!std::isfinite(centers[i]))
                 return host_fail(ROX_E_ARG, "%s: centers[%lld] = %g is not finite", e, (long long)i, centers[i]);
+    return 0;
+}
+
+// frequencies [n]: finite and >= 0
+inline int check_freqs(const char *e, int32_t n, const double *freqs)
+{
+    for (int32_t q = 0; q < n; ++q)
+        if (!(std::isfinite(freqs[q]) && freqs[q] >= 0.0))
+            return host_fail(ROX_E_ARG, "%s: freqs[%d] = %g is not finite and >= 0", e, q, freqs[q]);
+    return 0;
+}
+
+// directions [n][2] = (ex, ey): finite, not both zero
+inline int check_dirs(const char *e, int64_t n, const double *dirs)
+{
+    for (int64_t i = 0; i < n; ++i) {
+        const double ex = dirs[2 * i], ey = dirs[2 * i + 1];
+        if (!(std::isfinite(ex) && std::isfinite(ey)) || (ex == 0.0 && ey == 0.0))
+            return host_fail(ROX_E_ARG, "%s: dirs[%lld] = (%g, %g) is not finite or is zero", e, (long long)i, ex,
+                             ey);
+    }
+    return 0;
+}
+
+// histogram edges [rows][n_bins + 1]: finite and strictly increasing per row
+inline int check_edges(const char *e, int64_t rows, int32_t n_bins, const double *edges)
+{
+    for (int64_t z = 0; z < rows; ++z)
+        for (int32_t j = 0; j <= n_bins; ++j) {
+            const int64_t i = z * (n_bins + 1) + j;
+            if (!std::isfinite(edges[i]))
+                return host_fail(ROX_E_ARG, "%s: edges[%lld] = %g is not finite", e, (long long)i, edges[i]);
+            if (j && !(edges[i] > edges[i - 1]))
+                return host_fail(ROX_E_ARG, "%s: edges[%lld] = %g does not increase within its row", e,
+                                 (long long)i, edges[i]);
+        }
     return 0;
 }
 

@@ -18,6 +18,7 @@
 #include <cstdint>
 #include <cstring>
 
+#include "rox_bins.hpp"
 #include "rox_device.hpp"
 #include "rox_host.hpp"
 
@@ -40,34 +41,6 @@ struct StatArgs {
     uint32_t *copies;           // [kCopies][nx * ny]
     double *partial;            // [blocks][10]: n, sx, sy, sxx, syy, minx, maxx, miny, maxy, (pad)
 };
-
-// bin of v among edges e[0..n] as numpy.histogram with explicit edges decides it:
-// searchsorted(e, v, 'right') - 1, the right-most edge belonging to the last bin; -1 = outside
-__device__ __forceinline__ int bin_of(const double *e, int n, double v)
-{
-    if (!(v >= e[0]) || !(v <= e[n]))
-        return -1;                              // (NaN included)
-    int lo = 0, hi = n;                         // invariant: e[lo] <= v, (hi == n or v < e[hi])
-    // uniform edges (linspace): the proportional guess is right or one off -- two probes
-    const double w = e[n] - e[0];
-    const double t = w > 0.0 ? (v - e[0]) / w * n : 0.0;
-    int g = t < (double)(n - 1) ? (int)t : n - 1;
-    if (e[g] <= v) {
-        lo = g;
-        if (g + 1 <= n && (g + 1 == n || v < e[g + 1]))
-            return g;
-    } else {
-        hi = g;
-    }
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (e[mid] <= v)
-            lo = mid;
-        else
-            hi = mid;
-    }
-    return lo;
-}
 
 __global__ void __launch_bounds__(kStatBlock) spot_stats_kernel(const StatArgs a)
 {

@@ -1080,6 +1080,52 @@ class TraceEngine:
         return counts, eer, n_ok
 
     @_in_flight
+    def focus_gmtf(self, focus_rows, n_rays, dirs, freqs, edges=None, on_device=False):
+        """rox_focus_gmtf over the rows of a through-focus launch (``focus_rows``: the FocusRows
+        trace_pupil_grid_focus / trace_pupil_grids_focus return, still in HBM): the geometric OTF
+        and the line spread of each plane's spot over the first ``n_rays`` rays with status OK,
+        along the directions ``dirs`` (broadcast to [n_items, D, 2] = (ex, ey); a ray projects to
+        u = ex*x + ey*y).  ``freqs`` ([Q], cycles per system unit; None for no OTF) and ``edges``
+        (broadcast to [n_items, K, D, B + 1], strictly increasing; None for no line spread).
+        Returns ``(otf, lsf, n_ok)``: complex128 [n_items, K, D, Q] = mean exp(-2 pi i nu u) (NaN
+        where no ray arrived), int64 [n_items, K, D, B] = numpy.histogram(u, edges) counts, int64
+        [n_items, K] -- NumPy, or torch tensors in HBM with ``on_device``; None for what was not
+        asked."""
+        t = self.torch
+        rows, status, n_items, K, ld = self._focus_rows(focus_rows, 'focus_gmtf')
+        n_rays = int(n_rays)
+        if not 1 <= n_rays <= min(int(rows.shape[3]), int(status.shape[-1])):
+            raise EngineError(f'focus_gmtf: n_rays {n_rays} outside [1, {int(rows.shape[3])}]')
+        if freqs is None and edges is None:
+            raise EngineError('focus_gmtf: freqs or edges (or both)')
+        dv = np.asarray(dirs, dtype=np.float64)
+        if dv.ndim < 1 or dv.shape[-1] != 2:
+            raise EngineError('focus_gmtf: dirs are (ex, ey) pairs')
+        D = int(dv.shape[-2]) if dv.ndim > 1 else 1
+        dv = _f64(dv, (n_items, D, 2))
+        f = e = None
+        Q = B = 0
+        if freqs is not None:
+            f = np.ascontiguousarray(np.asarray(freqs, dtype=np.float64).reshape(-1))
+            Q = int(f.size)
+        if edges is not None:
+            e = np.asarray(edges, dtype=np.float64)
+            B = int(e.shape[-1]) - 1 if e.ndim else 0
+            e = _f64(e, (n_items, K, D, B + 1))
+        none = (None, None)
+        otf, p_otf = self._out(on_device, (n_items, K, D, Q, 2), np.float64, t.float64) if f is not None else none
+        lsf, p_lsf = self._out(on_device, (n_items, K, D, B), np.int64, t.int64) if e is not None else none
+        n_ok, p_nok = self._out(on_device, (n_items, K), np.int64, t.int64)
+        with t.cuda.device(self.device):
+            _check(self.lib.rox_focus_gmtf(n_items, K, rows.data_ptr(), ld, status.data_ptr(), n_rays, D,
+                                           dv.ctypes.data, Q, f.ctypes.data if f is not None else None, p_otf,
+                                           B, e.ctypes.data if e is not None else None, p_lsf, p_nok,
+                                           self._stream()), 'rox_focus_gmtf')
+        if otf is not None:
+            otf = t.view_as_complex(otf) if on_device else otf.view(np.complex128)[..., 0]
+        return otf, lsf, n_ok
+
+    @_in_flight
     def focus_zernike(self, focus_rows, grids, terms, wave_scale, circle=None, on_device=False):
         """rox_focus_zernike over the rows of a through-focus launch (``focus_rows``: the
         FocusRows trace_pupil_grid_focus / trace_pupil_grids_focus return, still in HBM): the
