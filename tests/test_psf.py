@@ -99,7 +99,7 @@ def test_device_psf_resident_and_large():
     from oracle import oracle
     from rayoptics_amd.engine import calc_psf, load_library
     rng = np.random.default_rng(3)
-    for ndim, maxdim in ((2, 5), (10, 17), (34, 129), (128, 512), (250, 1000)):
+    for ndim, maxdim in ((2, 5), (10, 17), (34, 129), (128, 512), (250, 1000), (10, 17), (10, 20)):
         y, x = np.mgrid[-1:1:ndim * 1j, -1:1:ndim * 1j]
         opd = 1.5 * (x * x + y * y) + 0.4 * x * y * y + 0.05 * rng.standard_normal((ndim, ndim))
         if ndim >= 8:
