@@ -858,6 +858,96 @@ int rox_surface_footprints(rox_system *sys, uint32_t trace_flags, uint32_t fp_fl
                            rox_footprint *fp, const double *half_width, int32_t n_bins,
                            uint32_t *maps, void *stream);
 
+/* Fresnel transmission and polarization ray tracing over the ROX_OUT_FULL packets of finished
+ * launches: how much of the light of every ray arrives, what each surface costs and how strongly
+ * the system polarizes, computed where the packets are (HBM).  Two orthogonal unit field vectors
+ * transverse to the ray are carried from the object slot to the image slot; s and p are
+ * redefined at every interface, so a skew ray mixes them (the product of (Ts + Tp) / 2 per
+ * surface is not the transmission off axis).
+ *   trace_flags, outs, n_rays   as rox_surface_footprints; of a slot's 10 rows d and nrml are
+ *          read, of rays with status ROX_OK only.
+ *   tx_flags   ROX_TX_FIELDS: rows has 10 rows per item, not 4.
+ *   wvl_idx    HOST [n_items]: the wavelength each item was traced at (row of n_table).
+ *   n_coat, coat_kind, coat_value   optional HOST coating tables: coat_kind[n_coat] int32 ROX_COAT_*
+ *          and coat_value[n_coat][2]; n_coat = the system's number of interfaces.  Both NULL
+ *          (n_coat ignored): every interface bare.  coat_value is read where the kind is
+ *          ROX_COAT_FIXED and must then lie in [0, 1].
+ *   rows   optional, host or device [n_items][n_rows][ld_rows], ld_rows >= n_rays; n_rows = 4 or 10.
+ *   surf   optional, host or device [n_items][n_seg] rox_tx_surface.
+ *   item   optional, host or device [n_items] rox_tx_item.
+ * Arithmetic, in operation order (IEEE double, no FMA anywhere in this entry: every step is
+ * one NumPy float64 operation).  Dot products are x*x' + y*y' + z*z' summed left to right;
+ * a cross product u x v is (u.y*v.z - u.z*v.y, u.z*v.x - u.x*v.z, u.x*v.y - u.y*v.x).
+ *   Frames.  A vector v of interface i's frame is taken into the next frame as rt_i . v, rt the
+ *          rox_surface.rt of row i: component a = (rt[a][c0]*v[c0] + rt[a][c1]*v[c1]) +
+ *          rt[a][2]*v[2] with (c0, c1) = (0, 1) for ROX_RT_F_ORDER and (1, 0) for ROX_RT_C_ORDER
+ *          (the interfaces and order of rox_footprint.cos_inc_*, unfused).  From slot k-1 to
+ *          slot k every interface slot_ifc[k-1] .. slot_ifc[k] - 1 is applied in turn, to the
+ *          previous slot's direction (giving b4) and to the carried E1, E2.
+ *   Slot k, interface s = slot_ifc[k]: d = the slot's direction, N = its normal; at slot 0
+ *          b4 = d.  ci = |b4 . N|, ct = |d . N|.
+ *   Slot 0 (the object) sets the state: a = (d.z, 0, -d.x), a = (1, 0, 0) if a.a == 0;
+ *          E1 = a / sqrt(a.a) (the x-like state), E2 = d x E1 (the y-like state), q = 1.
+ *   The last slot (the image) changes nothing.
+ *   Every slot in between has amplitude coefficients ts, tp, a flux factor qs and power
+ *   coefficients Ts, Tp, with n1 = n_table[w][s-1], n2 = n_table[w][s]:
+ *          bare     ROX_TRANSMIT, profile not ROX_THINLENS, ph.kind == ROX_PH_NONE, n1 != n2:
+ *                   A = n1*ci, B = n2*ct, ts = (A + A) / (A + B), tp = (A + A) / (n2*ci + n1*ct),
+ *                   qs = B / A, Ts = qs*(ts*ts), Tp = qs*(tp*tp); ci == 0: ts = tp = qs = 0.
+ *          mirror   ROX_REFLECT: ts = -1, tp = 1, qs = 1, Ts = Tp = 1 (an ideal mirror).
+ *          ideal    ROX_DUMMY and ROX_PHANTOM interfaces, n1 == n2, thin lenses and phase
+ *                   elements (gratings, DOEs, holograms) are COUNTED AS IDEAL: the field is
+ *                   carried through the bend with ts = tp = qs = 1, Ts = Tp = 1.
+ *          Coatings override the model of a ROX_TRANSMIT or ROX_REFLECT interface:
+ *          ROX_COAT_BARE as above; ROX_COAT_IDEAL ts = tp = qs = 1 and Ts = Tp = 1;
+ *          ROX_COAT_FIXED (Ts, Tp) = coat_value[s], ts = sqrt(Ts), tp = sqrt(Tp), qs = 1 (on a
+ *          mirror these are the reflectances).  On a mirror ts is negated, coated or not.
+ *          c = b4 x N; if c.c == 0: c = b4 x (1,0,0) when |b4.x| <= |b4.y|, else b4 x (0,1,0).
+ *          s^ = c / sqrt(c.c), p_in = b4 x s^, p_out = d x s^; for E in (E1, E2):
+ *          E <- (ts*(s^ . E))*s^ + (tp*(p_in . E))*p_out; q <- q*qs.
+ *   Rows of a ray with status ROX_OK, from g11 = E1.E1, g12 = E1.E2, g22 = E2.E2,
+ *          m = (g11 + g22)/2, h = (g11 - g22)/2, r = sqrt(h*h + g12*g12):
+ *          row 0  T = q*m, the transmission of unpolarized light
+ *          row 1  T1 = q*g11    row 2  T2 = q*g22 (the x-like and the y-like input state)
+ *          row 3  D = r/m, the diattenuation (0 when m == 0)
+ *          rows 4-6 E1, rows 7-9 E2 in the image frame (ROX_TX_FIELDS)
+ *          Every row of any other ray is NaN.  Columns n_rays .. ld_rows - 1 are not written.
+ * Records are over the rays with status ROX_OK; minima and maxima are exact selections, sums are
+ * per-wave partial sums merged in a fixed order by a finishing kernel (no floating-point
+ * atomics).  Where nothing counted the sums are 0 and the minima and maxima NaN.
+ * rows, surf and item may not all be NULL.  n_items in [1, ROX_MAX_FOCUS_ITEMS], n_rays in
+ * [1, 2^28], ld >= n_rays.  Identical calls give bit-identical results, host and device
+ * destinations alike.  Argument errors return ROX_E_ARG naming the parameter and item before
+ * anything is enqueued and leave the outputs untouched.  Scratch per launch is 32 MiB or, where
+ * that is more, what one item needs: 64 bytes of partial records per wave of 128 rays and slot
+ * (n_rays * (n_seg + 1) / 2 bytes: 7 MB at 2^20 rays and 13 slots, 1.9 GB at the largest n_rays,
+ * 2^28) plus, for rows bound for host memory, 8 MiB of rows.  Larger jobs run as consecutive
+ * launches over fewer items (and, for rows bound for host memory, fewer rays) with the same
+ * results.  Asynchronous on `stream` unless an output is host memory.
+ * Not modelled: absorption, multilayer coatings, complex (metal) indices, diffraction
+ * efficiency.                                                                               */
+#define ROX_TX_FIELDS 1u
+enum { ROX_COAT_BARE = 0, ROX_COAT_IDEAL = 1, ROX_COAT_FIXED = 2 };
+typedef struct rox_tx_surface {
+    int64_t n;               /* rays counted (status ROX_OK)                                 */
+    double ts_sum, tp_sum;   /* sums of Ts and of Tp at this slot (object and image: 1)      */
+    double t_sum;            /* sum of (Ts + Tp)/2                                            */
+    double ts_min, tp_min;
+    double ci_sum, ci_min;   /* sum and minimum of ci                                        */
+} rox_tx_surface;            /* 64 bytes */
+typedef struct rox_tx_item {
+    int64_t n_ok;            /* rays with status ROX_OK                                      */
+    int64_t n_rays;          /* rays launched (the call's n_rays)                            */
+    double t_sum, t_min, t_max;
+    double t1_sum, t2_sum;
+    double d_sum, d_max;
+} rox_tx_item;               /* 72 bytes */
+int rox_surface_transmission(rox_system *sys, uint32_t trace_flags, uint32_t tx_flags,
+                             int32_t n_items, const rox_out *outs, int64_t n_rays,
+                             const int32_t *wvl_idx, int32_t n_coat, const int32_t *coat_kind,
+                             const double *coat_value, double *rows, int64_t ld_rows,
+                             rox_tx_surface *surf, rox_tx_item *item, void *stream);
+
 /* chief-ray aiming ------------------------------------------------------- */
 /* One problem per (field, wavelength): trace.iterate_ray
  * (rayoptics/raytr/trace.py:313-415) as trace.aim_chief_ray calls it

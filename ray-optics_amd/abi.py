@@ -211,6 +211,23 @@ MAX_FOOTPRINT_BINS = 512    # include/roxtrace.h rox_surface_footprints
 MAX_FOOTPRINT_RAYS = 1 << 28
 
 
+class TxSurface(C.Structure):
+    """rox_tx_surface: what one FULL-packet slot costs the OK rays of one item"""
+    _fields_ = [('n', C.c_int64), ('ts_sum', C.c_double), ('tp_sum', C.c_double), ('t_sum', C.c_double),
+                ('ts_min', C.c_double), ('tp_min', C.c_double), ('ci_sum', C.c_double), ('ci_min', C.c_double)]
+
+
+class TxItem(C.Structure):
+    """rox_tx_item: transmission and diattenuation over the OK rays of one item"""
+    _fields_ = [('n_ok', C.c_int64), ('n_rays', C.c_int64), ('t_sum', C.c_double), ('t_min', C.c_double),
+                ('t_max', C.c_double), ('t1_sum', C.c_double), ('t2_sum', C.c_double), ('d_sum', C.c_double),
+                ('d_max', C.c_double)]
+
+
+TX_FIELDS = 1               # include/roxtrace.h rox_surface_transmission
+COAT_BARE, COAT_IDEAL, COAT_FIXED = 0, 1, 2
+
+
 class Vig(C.Structure):
     _fields_ = [('fld', Field), ('start_dir', C.c_double * 2), ('unit_dir', C.c_double * 2),
                 ('xy', C.c_int32), ('wvl_idx', C.c_int32), ('stop_surf', C.c_int32),
@@ -239,6 +256,8 @@ assert C.sizeof(FocusPsfStats) == 32
 assert C.sizeof(ZernikeTerm) == 16
 assert C.sizeof(ZernikeStats) == 56
 assert C.sizeof(Footprint) == 144
+assert C.sizeof(TxSurface) == 64
+assert C.sizeof(TxItem) == 72
 
 # every symbol include/roxtrace.h declares (checked by tests/test_abi.py) ...
 EXPORTS = ('rox_abi_version', 'rox_device_count', 'rox_set_device',
@@ -250,7 +269,7 @@ EXPORTS = ('rox_abi_version', 'rox_device_count', 'rox_set_device',
            'rox_pin_host_memory', 'rox_unpin_host_memory', 'rox_copy_async', 'rox_synchronize',
            'rox_spot_stats', 'rox_trace_through_focus', 'rox_trace_through_focus_grids',
            'rox_focus_psf', 'rox_focus_mtf', 'rox_focus_ee', 'rox_focus_gmtf', 'rox_focus_psf_ee',
-           'rox_focus_zernike', 'rox_surface_footprints')
+           'rox_focus_zernike', 'rox_surface_footprints', 'rox_surface_transmission')
 # ... and the measurement / self-test helpers of include/roxtrace_diag.h
 DIAG_EXPORTS = ('rox_time_pupil_grid', 'rox_selftest_fp64', 'rox_diag_pack_launches')
 
@@ -327,6 +346,9 @@ def declare(lib):
                                       vp, vp, vp]
     lib.rox_surface_footprints.restype = C.c_int
     lib.rox_surface_footprints.argtypes = [vp, C.c_uint32, C.c_uint32, i32, P(Out), i64, vp, vp, i32, vp, vp]
+    lib.rox_surface_transmission.restype = C.c_int
+    lib.rox_surface_transmission.argtypes = [vp, C.c_uint32, C.c_uint32, i32, P(Out), i64, vp, i32, vp, vp, vp, i64,
+                                             vp, vp, vp]
     lib.rox_time_pupil_grid.restype = C.c_int
     lib.rox_time_pupil_grid.argtypes = [vp, P(Field), P(Grid), i32, P(Opts),
                                         P(Out), vp, i32, P(dbl)]

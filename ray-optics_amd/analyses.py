@@ -1121,6 +1121,191 @@ def beam_footprints(opt_model, flds=None, wvls=None, num_rays=64, maps=0, check_
                           results if keep_packets else None)
 
 
+# ---- Fresnel transmission and polarization over full packets ------------------------
+def _weighted_mean(v, s):
+    """[F, W] values merged over wavelengths with the weights s [W]; a NaN value (no ray counted)
+    takes no part, and a field without any value is NaN"""
+    v = np.asarray(v, dtype=np.float64)
+    ok = np.isfinite(v)
+    w = np.where(ok, np.asarray(s, dtype=np.float64)[None, :], 0.0)
+    tot = w.sum(axis=1)
+    num = (w * np.where(ok, v, 0.0)).sum(axis=1)
+    return np.where(tot > 0.0, num / np.where(tot > 0.0, tot, 1.0), np.nan)
+
+
+class Transmission:
+    """what :func:`transmission` returns.
+
+    ``items``         [F, W] rox_tx_item records (engine.TX_ITEM_DTYPE); ``surfaces`` [F, W, n_seg]
+                      rox_tx_surface records (engine.TX_SURFACE_DTYPE)
+    ``T``             [F, W] the mean transmission of unpolarized light over the rays that arrived
+                      (NaN: none did)
+    ``throughput``    [F, W] sum of T over the rays launched: vignetting counted
+    ``poly_T``, ``poly_throughput``  [F] merged over the wavelengths with the spectral weights
+    ``pupil_fraction``  [F] the share of the unit pupil box each field's grid spans: with
+                      apply_vignetting a field's rays are launched over its own vignetted box
+                      [-(1 - vlx), 1 - vux] x [-(1 - vly), 1 - vuy], so a ray of a vignetted field
+                      stands for less of the entrance pupil -- (2 - vlx - vux)(2 - vly - vuy)/4
+    ``relative``      [F] poly_throughput * pupil_fraction over that of field ``ref_field``:
+                      RELATIVE TRANSMISSION INCLUDING VIGNETTING, by the vignetting factors and
+                      by the rays the apertures block alike.  (Where a field's factors differ
+                      between the two sides of an axis, its two halves are sampled at different
+                      densities; the box's area then weights their mean.)  It is not radiometric
+                      relative illumination: no projected pupil area, no cos^4 and no distortion
+                      term is applied.
+    ``surface_T``     [F, W, n_seg] the mean (Ts + Tp)/2 of each slot (1 at the object, the image
+                      and every interface counted as ideal)
+    ``surface_loss``  the slots ranked by their loss 1 - mean (Ts + Tp)/2 over every item's
+                      rays, largest first: a list of (slot, interface, loss)
+    ``slot_ifc``      [n_seg] the interface index of each slot
+    ``diattenuation_max``, ``diattenuation_mean``  [F, W]
+    ``T_map``, ``D_map``  [F, W, num_rays, num_rays] views of the rows, NaN where a ray failed
+                      (x the first axis), or None
+    ``E1``, ``E2``    [F, W, 3, num_rays, num_rays] the exit field vectors of the x-like and the
+                      y-like input state in the image frame, or None
+    ``results``       the device packets, with ``keep_packets``"""
+
+    def __init__(self, items, surfaces, slot_ifc, spectral_wts, ref_field=0, rows=None, num_rays=None, results=None,
+                 pupil_fraction=None):
+        self.items, self.surfaces = items, surfaces
+        self.slot_ifc = np.asarray(slot_ifc)
+        self.spectral_wts = np.asarray(spectral_wts, dtype=np.float64)
+        self.ref_field = int(ref_field)
+        self.results = results
+        F, W = items.shape
+        if not 0 <= self.ref_field < F:
+            raise ValueError(f'Transmission: ref_field {ref_field} outside [0, {F})')
+        n = items['n_ok'].astype(np.float64)
+        some = n > 0
+        den = np.where(some, n, 1.0)
+        self.T = np.where(some, items['t_sum'] / den, np.nan)
+        self.throughput = items['t_sum'] / items['n_rays']
+        self.diattenuation_mean = np.where(some, items['d_sum'] / den, np.nan)
+        self.diattenuation_max = items['d_max'].copy()
+        self.poly_T = _weighted_mean(self.T, self.spectral_wts)
+        self.poly_throughput = _weighted_mean(self.throughput, self.spectral_wts)
+        self.pupil_fraction = np.ones(F) if pupil_fraction is None else np.asarray(pupil_fraction, dtype=np.float64)
+        if self.pupil_fraction.shape != (F,):
+            raise ValueError(f'Transmission: one pupil_fraction per field, got {self.pupil_fraction.shape}')
+        weighted = self.poly_throughput * self.pupil_fraction
+        self.relative = weighted / weighted[self.ref_field]
+        ns = surfaces['n'].astype(np.float64)
+        self.surface_T = np.where(ns > 0, surfaces['t_sum'] / np.where(ns > 0, ns, 1.0), np.nan)
+        tot_n = ns.sum(axis=(0, 1))
+        mean = np.where(tot_n > 0, surfaces['t_sum'].sum(axis=(0, 1)) / np.where(tot_n > 0, tot_n, 1.0), 1.0)
+        loss = 1.0 - mean
+        order = sorted(range(loss.shape[0]), key=lambda k: (-loss[k], k))
+        self.surface_loss = [(k, int(self.slot_ifc[k]), float(loss[k])) for k in order]
+        self.T_map = self.D_map = self.E1 = self.E2 = None
+        if rows is not None:
+            num = int(num_rays)
+            grid = rows.reshape(F, W, rows.shape[1], num, num)
+            self.T_map, self.D_map = grid[:, :, 0], grid[:, :, 3]
+            if rows.shape[1] == 10:
+                self.E1, self.E2 = grid[:, :, 4:7], grid[:, :, 7:10]
+
+
+def _coating_tables(table, coatings):
+    """``coatings`` of :func:`transmission` -> (coat_kind [n_ifcs], coat_value [n_ifcs, 2]) or
+    (None, None)"""
+    if coatings is None:
+        return None, None
+    N = table.n_ifcs
+    kind = np.zeros(N, np.int32)
+    value = np.ones((N, 2), np.float64)
+
+    def fixed(v):
+        try:
+            v = None if isinstance(v, str) else np.asarray(v, dtype=np.float64).reshape(-1)
+        except (TypeError, ValueError):
+            v = None
+        if v is None or v.shape[0] not in (1, 2) or not (np.isfinite(v).all() and (v >= 0).all() and (v <= 1).all()):
+            raise ValueError(f'transmission: coatings: {coatings!r} is not \'bare\', \'ideal\', a power '
+                             f'transmission in [0, 1] or a pair (Ts, Tp) of them')
+        return (v[0], v[-1])
+
+    if isinstance(coatings, str):
+        if coatings != 'ideal':
+            raise ValueError(f'transmission: coatings: {coatings!r} is not None, \'ideal\', a value or a dict')
+        kind[:] = abi.COAT_IDEAL
+    elif isinstance(coatings, dict):
+        for i, c in coatings.items():
+            if not (isinstance(i, (int, np.integer)) and 0 < i < N - 1):
+                raise ValueError(f'transmission: coatings: key {i!r} is not an interface index in [1, {N - 2}]')
+            if isinstance(c, str) and c in ('bare', 'ideal'):
+                kind[i] = abi.COAT_IDEAL if c == 'ideal' else abi.COAT_BARE
+            else:
+                kind[i], value[i] = abi.COAT_FIXED, fixed(c)
+    else:
+        v = fixed(coatings)
+        nt = np.asarray(table.n_table)
+        for i in range(1, N - 1):
+            air = (nt[:, i - 1] == 1.0).all(), (nt[:, i] == 1.0).all()
+            if table.rows[i].mode == abi.TRANSMIT and air[0] != air[1]:     # glass on exactly one side
+                kind[i], value[i] = abi.COAT_FIXED, v
+    return kind, value
+
+
+def transmission(opt_model, flds=None, wvls=None, num_rays=64, coatings=None, check_apertures=True, pupil_maps=True,
+                 fields=False, keep_packets=False, packets=None, ref_field=0):
+    """How much of the light arrives, on the device: one FULL launch (rox_trace_pupil_grids) over
+    every (field, wavelength), set up exactly as :func:`beam_footprints` does, whose packets stay
+    in HBM, then one rox_surface_transmission call over them -- the Fresnel equations at every
+    interface with two orthogonal field vectors carried along each ray (include/roxtrace.h states
+    the arithmetic).  ``packets``: the result of ``beam_footprints(..., keep_packets=True)`` (or
+    its ``results``) over the same fields, wavelengths and ``num_rays`` -- no ray is traced again,
+    one trace serves both analyses.  ``coatings``: None (bare surfaces), 'ideal' (every interface
+    lossless), a power transmission or a pair (Ts, Tp) for every glass-air surface, or a dict
+    {interface index: 'bare' | 'ideal' | value | (Ts, Tp)}.  ``pupil_maps`` keeps the per-ray rows
+    (T_map, D_map), ``fields`` adds the exit field vectors.  Spectral weights as the through-focus
+    maps take them (osp['wvls'], or 1 per wavelength when ``wvls`` is given).
+
+    ``relative`` of the result is relative transmission including vignetting -- poly_throughput
+    times the share of the unit pupil box the field's vignetting factors leave its grid, over that
+    of field ``ref_field``.  It is NOT radiometric relative illumination: no projected
+    pupil area, cos^4 or distortion term is applied; that is out of scope here.  Neither are
+    absorbing or multilayer coatings, the complex indices of metal mirrors and diffraction
+    efficiencies: mirrors, thin lenses and phase elements are counted as ideal.
+    Returns :class:`Transmission`."""
+    num_rays = int(num_rays)
+    if num_rays < 1 or num_rays * num_rays > abi.MAX_FOOTPRINT_RAYS:
+        raise ValueError(f'transmission: num_rays {num_rays} outside [1, 16384]')
+    flds, wvls, _fw, spectral_wts, _ref = _map_spec(opt_model, flds, wvls, None, None,
+                                                    wvls[0] if wvls is not None and len(wvls) else None,
+                                                    'transmission')
+    F, W = len(flds), len(wvls)
+    if not 0 <= int(ref_field) < F:
+        raise ValueError(f'transmission: ref_field {ref_field} outside [0, {F})')
+    fs, wis, opts_list, box = [], [], [], []
+    eng = None
+    for fld in flds:
+        for wvl in wvls:
+            kw = dict(check_apertures=bool(check_apertures), apply_vignetting=True)
+            eng, f, wi, opts = _launch_setup(opt_model, fld, wvl, kw, abi.OUT_FULL)
+            fs.append(f)
+            wis.append(wi)
+            opts_list.append(opts)
+        box.append((2.0 - f.vlx - f.vux) * (2.0 - f.vly - f.vuy) / 4.0)
+    flags = int(opts_list[0].flags)
+    if any(int(o.flags) != flags for o in opts_list):
+        raise ValueError('transmission: the fields do not share their trace flags')
+    kind, value = _coating_tables(eng.table, coatings)
+    if packets is not None:
+        flags = int(getattr(packets, 'trace_flags', flags))
+        results = list(getattr(packets, 'results', packets) or [])
+        if len(results) != F * W or any(int(r.R) != num_rays * num_rays for r in results):
+            raise ValueError(f'transmission: packets are not {F * W} items of {num_rays}^2 rays (were they kept '
+                             f'with keep_packets=True?)')
+    else:
+        grid = make_grid((-1., -1.), (1., 1.), num_rays)
+        results = eng.trace_pupil_grids(fs, wis, grid, opts_list, want_pupil=False)
+    rows, surf, item = eng.surface_transmission(results, flags, wis, coat_kind=kind, coat_value=value,
+                                                want_rows=bool(pupil_maps or fields), fields=bool(fields))
+    n_seg = surf.shape[1]
+    return Transmission(item.reshape(F, W), surf.reshape(F, W, n_seg), eng.slot_interfaces(flags), spectral_wts,
+                        ref_field, rows, num_rays, results if keep_packets else None, box)
+
+
 # ---- MTF through focus ----------------------------------------------------------
 # the PSF stack through_focus_mtf holds at once: larger maps run rox_focus_psf / rox_focus_mtf
 # over consecutive groups of items (the results do not depend on the grouping)

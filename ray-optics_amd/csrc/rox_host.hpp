@@ -1,6 +1,6 @@
 // rox_host.hpp -- host-side helpers shared by the translation units that define C entry points
 // (roxtrace.hip and the units its header lists, spotstats.hip and the analyses psf.hip, mtf.hip,
-// ee.hip, gmtf.hip, zernike.hip, footprint.hip): the error path and the argument checks, the environment
+// ee.hip, gmtf.hip, zernike.hip, footprint.hip, fresnel.hip): the error path and the argument checks, the environment
 // switches, grow-only scratch blocks, scratch kept per (device, stream), the pinned staging of
 // host inputs and the carving of one workspace block.
 #pragma once

@@ -160,6 +160,22 @@ def footprint_view(records):
     return a.view(FOOTPRINT_DTYPE).reshape(a.shape[:-1])
 
 
+# rox_tx_surface / rox_tx_item: what surface_transmission returns
+TX_SURFACE_DTYPE = np.dtype([('n', np.int64)] + [(name, np.float64) for name in
+                                                ('ts_sum', 'tp_sum', 't_sum', 'ts_min', 'tp_min', 'ci_sum', 'ci_min')])
+TX_ITEM_DTYPE = np.dtype([('n_ok', np.int64), ('n_rays', np.int64)] +
+                         [(name, np.float64) for name in ('t_sum', 't_min', 't_max', 't1_sum', 't2_sum', 'd_sum', 'd_max')])
+assert TX_SURFACE_DTYPE.itemsize == C.sizeof(abi.TxSurface)
+assert TX_ITEM_DTYPE.itemsize == C.sizeof(abi.TxItem)
+
+
+def tx_view(records, dtype):
+    """the uint8 tensor surface_transmission(on_device=True) returns for ``surf`` or ``item`` -> a
+    TX_SURFACE_DTYPE / TX_ITEM_DTYPE array on the host"""
+    a = np.ascontiguousarray(records.cpu().numpy() if hasattr(records, 'cpu') else records)
+    return a.view(dtype).reshape(a.shape[:-1])
+
+
 # rox_zernike_stats: what focus_zernike returns
 ZERNIKE_STATS_DTYPE = np.dtype([('n', np.int64), ('n_outside', np.int64), ('rms', np.float64),
                                 ('rms_residual', np.float64), ('pv_residual', np.float64),
@@ -1223,6 +1239,60 @@ class TraceEngine:
                                                    p_rec, hw.ctypes.data if hw is not None else None, n_bins,
                                                    p_maps, self._stream()), 'rox_surface_footprints')
         return rec, maps
+
+    @_in_flight
+    def surface_transmission(self, results, trace_flags, wvl_idxs, coat_kind=None, coat_value=None, want_rows=True,
+                             fields=False, on_device=False):
+        """rox_surface_transmission over the FULL packets of finished launches (``results``,
+        ``trace_flags`` as surface_footprints; ``wvl_idxs``: the wavelength index each item was
+        traced at): Fresnel transmission and polarization ray tracing of every OK ray.
+        ``coat_kind`` ([n_ifcs] of abi.COAT_*) and ``coat_value`` ([n_ifcs, 2] = (Ts, Tp), read
+        where the kind is COAT_FIXED) go together; without them every interface is bare.
+        Returns ``(rows, surf, item)``: float64 [n_items, n_rows, R] with rows T, T1, T2, D (and
+        with ``fields`` the two exit field vectors, n_rows = 10), NaN where a ray failed (None
+        without ``want_rows``); a TX_SURFACE_DTYPE array [n_items, n_seg]; a TX_ITEM_DTYPE array
+        [n_items] -- NumPy, or with ``on_device`` torch tensors (the records as uint8 [..., 64]
+        and [n_items, 72]; ``tx_view`` reads them on the host)."""
+        t = self.torch
+        if isinstance(results, DeviceResult):
+            results = [results]
+        results = list(results)
+        n_items = len(results)
+        if not 1 <= n_items <= abi.MAX_FOCUS_ITEMS:
+            raise EngineError(f'surface_transmission: 1 to {abi.MAX_FOCUS_ITEMS} items, got {n_items}')
+        n_seg = self.num_segments(int(trace_flags))
+        R = int(results[0].R)
+        for i, r in enumerate(results):
+            if r.out_mode != abi.OUT_FULL or int(r.seg.shape[0]) != n_seg or int(r.R) != R:
+                raise EngineError(f'surface_transmission: item {i} is not a FULL packet of {n_seg} segments and '
+                                  f'{R} rays')
+        wi = np.ascontiguousarray(np.asarray(wvl_idxs, dtype=np.int32).reshape(-1))
+        if wi.shape[0] != n_items:
+            raise EngineError(f'surface_transmission: {wi.shape[0]} wvl_idxs for {n_items} items')
+        N = self.table.n_ifcs
+        if (coat_kind is None) != (coat_value is None):
+            raise EngineError('surface_transmission: coat_kind and coat_value go together')
+        ck = cv = None
+        if coat_kind is not None:
+            ck = np.ascontiguousarray(np.asarray(coat_kind, dtype=np.int32).reshape(-1))
+            cv = np.ascontiguousarray(np.asarray(coat_value, dtype=np.float64))
+            if ck.shape[0] != N or cv.shape != (N, 2):
+                raise EngineError(f'surface_transmission: coat_kind [{ck.shape[0]}] and coat_value '
+                                  f'{list(cv.shape)} are not [{N}] and [{N}, 2], one entry per interface')
+        n_rows = 10 if fields else 4
+        outs = (abi.Out * n_items)(*[r.out_struct() for r in results])
+        rows, p_rows = self._out(on_device, (n_items, n_rows, R), np.float64, t.float64) if want_rows \
+            else (None, None)
+        surf, p_surf = self._out(on_device, (n_items, n_seg), TX_SURFACE_DTYPE, t.uint8,
+                                 (n_items, n_seg, C.sizeof(abi.TxSurface)))
+        item, p_item = self._out(on_device, (n_items,), TX_ITEM_DTYPE, t.uint8, (n_items, C.sizeof(abi.TxItem)))
+        with t.cuda.device(self.device):
+            _check(self.lib.rox_surface_transmission(self._handle, int(trace_flags), abi.TX_FIELDS if fields else 0,
+                                                     n_items, outs, R, wi.ctypes.data, N if ck is not None else 0,
+                                                     ck.ctypes.data if ck is not None else None,
+                                                     cv.ctypes.data if cv is not None else None, p_rows, R, p_surf,
+                                                     p_item, self._stream()), 'rox_surface_transmission')
+        return rows, surf, item
 
     @_in_flight
     def focus_psf_ee(self, psf, pitch, centers, radii, want_centroid=True):

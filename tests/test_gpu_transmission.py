@@ -1,0 +1,332 @@
+"""rox_surface_transmission on the device against the NumPy restatement (tests/fresnel_ref.py)
+run on the same packets copied to the host: rows, minima, maxima and counts bit for bit, sums
+within n * 2^-53 relative of math.fsum of the restatement's per-ray values (the terms are
+non-negative, so that bound holds for any order of summation).  Grids are 15 x 15 rays on
+``workloads`` tables and on the committed tilted-singlet table: 225 rays is no multiple of 64 or of
+the tile, the last wave is ragged.
+
+15 points over [-1, 1] do not put a ray at the pupil centre exactly (-1 + 7 * (2 / 14) is not 0
+in float64; that ray leaves the object with direction (-5.6e-27, -5.6e-27, 1) and D = 3e-33).
+The axial test, which asserts D == 0.0 and T1 == T2 exactly, therefore spans [-0.875, 0.875]: the
+step 0.125 is exact and the centre ray is the axial ray.
+
+A packet that is not FULL, or has another ray count, is refused by TraceEngine (the C entry
+cannot see a buffer's out_mode); what the C entry itself refuses is checked with sentinels in the
+outputs."""
+import ctypes as C
+import math
+
+import numpy as np
+import pytest
+
+import fresnel_ref as FR
+from helpers import bit_equal, field_from_arr, fixture
+from rayoptics_amd import abi, workloads
+from fresnel_ref import AB_BOUND, CLOSED, EPS
+
+pytestmark = pytest.mark.gpu
+
+SPOT = abi.INTERSECT_OBJ | abi.CHECK_APERTURES | abi.APPLY_VIGNETTING
+NUM = 15
+CENTRE = (NUM // 2) * NUM + NUM // 2
+
+
+@pytest.fixture(scope='module')
+def torch():
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip('no GPU')
+    return torch
+
+
+def case(name):
+    """-> (table, trace flags, fields [n_items], wavelength indices [n_items])"""
+    if name.startswith('tilted'):                       # decentred and tilted: rt is not the identity
+        fx = fixture('tilted_singlet')
+        c = fx['grid_f1']
+        flags = int(c['flags']) | (abi.FILTER_PHANTOMS if name == 'tilted_filtered' else 0)
+        return fx.table, flags, [field_from_arr(c['field'])] * 2, [0, 1]
+    wl = workloads.load(name)
+    picks = {'dblgauss_c2': ([0, 0, 2, 2], [0, 2, 0, 2]), 'rc_telescope_c4': ([0, 4], [0, 0]),
+             'cell_phone': ([0, 1, 2], [1, 1, 1])}[name]     # (no ray of field 2 passes the apertures)
+    return wl.table, SPOT, [wl.fields[f] for f in picks[0]], picks[1]
+
+
+def trace(eng, flags, flds, wis, num=NUM, span=1.0):
+    from rayoptics_amd.engine import make_grid, make_opts
+    opts = [make_opts(flags=flags, out_mode=abi.OUT_FULL) for _ in flds]
+    return eng.trace_pupil_grids(flds, wis, make_grid((-span, -span), (span, span), num), opts, want_pupil=False)
+
+
+def host_of(results):
+    out = []
+    for r in results:
+        h = r.to_host(want=('seg', 'status'))
+        out.append((np.array(h.seg), np.array(h.status)))
+    return out
+
+
+def same(a, b):
+    return a == b or (math.isnan(a) and math.isnan(b))
+
+
+def check_item(table, flags, seg, status, wi, rows, surf, item, what, coat=(None, None)):
+    """one item's rows [n_rows, R], rox_tx_surface records [n_seg] and rox_tx_item record against (A)"""
+    a = FR.transmission_a(table, flags, seg, status, wi, coat[0], coat[1], fields=rows.shape[0] == 10)
+    bit_equal(rows, a['rows'], f'{what}: rows')
+    ref_s, ref_i = FR.records(a)
+    n = ref_i['n_ok']
+    assert int(item['n_ok']) == n and int(item['n_rays']) == status.shape[0], what
+    assert np.array_equal(surf['n'], ref_s['n']), what
+    for name in ('ts_min', 'tp_min', 'ci_min'):
+        bit_equal(surf[name], ref_s[name], f'{what}: {name}')
+    for name in ('t_min', 't_max', 'd_max'):
+        assert same(float(item[name]), ref_i[name]), (what, name, float(item[name]), ref_i[name])
+    for name in ('ts_sum', 'tp_sum', 't_sum', 'ci_sum'):
+        err = np.abs(surf[name] - ref_s[name])
+        print(f'{what}: {name} n {n} largest error {err.max():.3g} (bound {n * EPS * ref_s[name].max():.3g})')
+        assert (err <= n * EPS * ref_s[name]).all(), (what, name)
+    for name in ('t_sum', 't1_sum', 't2_sum', 'd_sum'):
+        err = abs(float(item[name]) - ref_i[name])
+        print(f'{what}: {name} n {n} error {err:.3g} (bound {n * EPS * ref_i[name]:.3g})')
+        assert err <= n * EPS * ref_i[name], (what, name)
+    return a
+
+
+@pytest.mark.parametrize('name', ['dblgauss_c2', 'rc_telescope_c4', 'cell_phone', 'tilted', 'tilted_filtered'])
+def test_exact_against_the_restatement(torch, name):
+    from rayoptics_amd.engine import TraceEngine
+    table, flags, flds, wis = case(name)
+    eng = TraceEngine(table)
+    results = trace(eng, flags, flds, wis)
+    host = host_of(results)
+    rows, surf, item = eng.surface_transmission(results, flags, wis, fields=True)
+    n_seg = eng.num_segments(flags)
+    assert rows.shape == (len(flds), 10, NUM * NUM) and surf.shape == (len(flds), n_seg)
+    n_ok = 0
+    for i, (seg, st) in enumerate(host):
+        a = check_item(table, flags, seg, st, wis[i], rows[i], surf[i], item[i], f'{name} item {i}')
+        n_ok += int(a['ok'].sum())
+    assert n_ok >= 100
+    if name == 'dblgauss_c2':                           # apertures checked: some rays fail
+        assert int(item['n_ok'].min()) < NUM * NUM and np.isnan(rows).any() and not np.isnan(rows).all()
+    if name == 'rc_telescope_c4':
+        assert [r.mode for r in table.rows].count(abi.REFLECT) == 2
+        assert (surf['t_sum'] == surf['n']).all()       # ideal mirrors cost nothing
+    if name == 'tilted_filtered':
+        assert n_seg == table.n_ifcs - 1 and any(r.mode == abi.PHANTOM for r in table.rows)
+    eng.close()
+
+
+def test_axial_field_of_the_double_gauss(torch):
+    from rayoptics_amd.engine import TraceEngine
+    wl = workloads.load('dblgauss_c2')
+    assert tuple(wl.fields[0].aim) == (0.0, 0.0)
+    eng = TraceEngine(wl.table)
+    results = trace(eng, SPOT, [wl.fields[0]], [1], span=0.875)
+    seg, st = host_of(results)[0]
+    assert st[CENTRE] == abi.OK and seg[0, 3:6, CENTRE].tolist() == [0.0, 0.0, 1.0]
+    rows, surf, item = eng.surface_transmission(results, SPOT, [1])
+    check_item(wl.table, SPOT, seg, st, 1, rows[0], surf[0], item[0], 'axial')
+    T, T1, T2, D = rows[0, :, CENTRE]
+    assert D == 0.0 and T1 == T2
+    nt = wl.table.n_table[1]
+    want, n_glass = 1.0, 0
+    for s in range(1, wl.table.n_ifcs - 1):
+        if nt[s - 1] != nt[s]:
+            want *= 4.0 * nt[s - 1] * nt[s] / (nt[s - 1] + nt[s]) ** 2
+            n_glass += 1
+    print(f'axial ray: T {T!r} closed form {want!r} error {abs(T - want):.3g} bound {CLOSED * n_glass:.3g}')
+    assert n_glass == 10 and abs(T - want) <= CLOSED * n_glass
+    assert float(item[0]['t_max']) >= T and float(item[0]['d_max']) > 1e-3      # the rim polarizes
+    eng.close()
+
+
+def test_an_off_axis_skew_ray(torch):
+    """s and p are redefined at every surface: the transmission of a skew ray is not the product
+    of the mean power coefficients; the independent formulation (B) agrees within the bound
+    measured on the host (tests/test_transmission_host.py)"""
+    from rayoptics_amd.engine import TraceEngine
+    wl = workloads.load('dblgauss_c2')
+    eng = TraceEngine(wl.table)
+    results = trace(eng, SPOT, [wl.fields[2]], [1])
+    seg, st = host_of(results)[0]
+    rows, _s, _i = eng.surface_transmission(results, SPOT, [1])
+    a = FR.transmission_a(wl.table, SPOT, seg, st, 1)
+    b = FR.transmission_b(wl.table, SPOT, seg, st, 1)
+    ok = a['ok']
+    naive = np.full(ok.shape, np.nan)
+    naive[ok] = np.prod((a['Ts'] + a['Tp']) / 2.0, axis=0)
+    r = int(np.flatnonzero(ok & (np.abs(seg[1, 0]) > 1.0) & (np.abs(seg[1, 1]) > 1.0))[0])
+    print(f'skew ray {r}: T {rows[0, 0, r]!r} naive {naive[r]!r} (B) {b[0, r]!r}')
+    assert abs(rows[0, 0, r] - naive[r]) > 100 * EPS
+    assert np.abs(rows[0][:, ok] - b[:, ok]).max() <= AB_BOUND
+    eng.close()
+
+
+def test_coatings(torch):
+    from rayoptics_amd.engine import TraceEngine
+    wl = workloads.load('dblgauss_c2')
+    table = wl.table
+    N = table.n_ifcs
+    eng = TraceEngine(table)
+    wis = [0, 2]
+    results = trace(eng, SPOT, [wl.fields[0], wl.fields[2]], wis)
+    host = host_of(results)
+    n_surf = N - 2
+    kind, value = np.full(N, abi.COAT_IDEAL, np.int32), np.ones((N, 2))
+    rows, surf, item = eng.surface_transmission(results, SPOT, wis, coat_kind=kind, coat_value=value)
+    for i, (seg, st) in enumerate(host):
+        check_item(table, SPOT, seg, st, wis[i], rows[i], surf[i], item[i], f'ideal item {i}', (kind, value))
+    ok = ~np.isnan(rows[:, 0])
+    assert np.nanmax(np.abs(rows[:, :3] - 1.0)) <= CLOSED * n_surf and np.nanmax(rows[:, 3]) <= CLOSED * n_surf
+    # one surface at (Ts, Tp) = (0.9, 0.8), the rest ideal
+    kind[4], value[4] = abi.COAT_FIXED, (0.9, 0.8)
+    rows, surf, item = eng.surface_transmission(results, SPOT, wis, coat_kind=kind, coat_value=value)
+    for i, (seg, st) in enumerate(host):
+        check_item(table, SPOT, seg, st, wis[i], rows[i], surf[i], item[i], f'fixed item {i}', (kind, value))
+    tol = CLOSED * n_surf
+    for j in (1, 2):
+        v = rows[:, j][ok]
+        assert v.min() >= 0.8 - tol and v.max() <= 0.9 + tol, (j, v.min(), v.max())
+    slot = 4
+    assert (surf['ts_min'][:, slot] == 0.9).all() and (surf['tp_min'][:, slot] == 0.8).all()
+    # the meridional rays of the off-axis field (x = 0: the middle row of the grid, x the outer axis):
+    # the x-like state is s there, the y-like state p
+    mer = np.arange(NUM) + (NUM // 2) * NUM
+    mer = mer[ok[1][mer]]
+    assert mer.size >= 5 and np.abs(host[1][0][:, 3, mer]).max() < 1e-12
+    assert np.abs(rows[1, 1, mer] - 0.9).max() <= tol and np.abs(rows[1, 2, mer] - 0.8).max() <= tol
+    eng.close()
+
+
+def test_repeats_destinations_and_grouping(torch):
+    from rayoptics_amd.engine import TX_ITEM_DTYPE, TX_SURFACE_DTYPE, TraceEngine, tx_view
+    table, flags, flds, wis = case('dblgauss_c2')
+    eng = TraceEngine(table)
+    results = trace(eng, flags, flds, wis)
+    rows, surf, item = eng.surface_transmission(results, flags, wis, fields=True)
+    again = eng.surface_transmission(results, flags, wis, fields=True)
+    assert all(x.tobytes() == y.tobytes() for x, y in zip((rows, surf, item), again)), 'a repeat differs'
+    drows, dsurf, ditem = eng.surface_transmission(results, flags, wis, fields=True, on_device=True)
+    assert drows.cpu().numpy().tobytes() == rows.tobytes(), 'device rows differ from host rows'
+    assert tx_view(dsurf, TX_SURFACE_DTYPE).tobytes() == surf.tobytes()
+    assert tx_view(ditem, TX_ITEM_DTYPE).tobytes() == item.tobytes()
+    for i, r in enumerate(results):                     # four in one call against four single calls
+        r1, s1, i1 = eng.surface_transmission(r, flags, wis[i:i + 1], fields=True)
+        assert r1.tobytes() == rows[i:i + 1].tobytes() and s1.tobytes() == surf[i:i + 1].tobytes(), f'item {i}'
+        assert i1.tobytes() == item[i:i + 1].tobytes(), f'item {i}'
+    none, s0, i0 = eng.surface_transmission(results, flags, wis, want_rows=False)
+    assert none is None and s0.tobytes() == surf.tobytes() and i0.tobytes() == item.tobytes()
+    r4, s4, i4 = eng.surface_transmission(results, flags, wis)
+    assert r4.tobytes() == rows[:, :4].tobytes() and s4.tobytes() == surf.tobytes() and i4.tobytes() == item.tobytes()
+    eng.close()
+
+
+def test_split_launches_equal_one_launch(torch):
+    """4 items x 600^2 rays with rows bound for host memory: the rows pass through the scratch a
+    range of rays at a time and the items run as two launches; the same bits as device
+    destinations (one launch), as each item's own call, and as (A) on one item"""
+    from rayoptics_amd.engine import TX_ITEM_DTYPE, TX_SURFACE_DTYPE, TraceEngine, tx_view
+    table, flags, flds, wis = case('dblgauss_c2')
+    eng = TraceEngine(table)
+    num = 600
+    results = trace(eng, flags, flds, wis, num=num)
+    rows, surf, item = eng.surface_transmission(results, flags, wis)
+    drows, dsurf, ditem = eng.surface_transmission(results, flags, wis, on_device=True)
+    assert drows.cpu().numpy().tobytes() == rows.tobytes()
+    assert tx_view(dsurf, TX_SURFACE_DTYPE).tobytes() == surf.tobytes()
+    assert tx_view(ditem, TX_ITEM_DTYPE).tobytes() == item.tobytes()
+    r1, s1, i1 = eng.surface_transmission(results[3], flags, wis[3:])
+    assert r1.tobytes() == rows[3:].tobytes() and s1.tobytes() == surf[3:].tobytes() and i1.tobytes() == item[3:].tobytes()
+    seg, st = host_of(results[3:])[0]
+    a = FR.transmission_a(table, flags, seg, st, wis[3])
+    bit_equal(rows[3], a['rows'], 'rows of 600^2 rays')
+    assert int(item[3]['n_ok']) == int(a['ok'].sum()) and int(item[3]['n_rays']) == num * num
+    assert float(item[3]['t_min']) == np.nanmin(a['rows'][0]) and float(item[3]['d_max']) == np.nanmax(a['rows'][3])
+    eng.close()
+
+
+def test_argument_errors_leave_the_outputs_untouched(torch):
+    from rayoptics_amd.engine import EngineError, TX_ITEM_DTYPE, TX_SURFACE_DTYPE, TraceEngine, load_library, make_grid, \
+        make_opts
+    lib = load_library()
+    table, flags, flds, wis = case('dblgauss_c2')
+    eng = TraceEngine(table)
+    results = trace(eng, flags, flds[:2], wis[:2])
+    grid = make_grid((-1., -1.), (1., 1.), NUM)
+    last = eng.trace_pupil_grid(flds[0], grid, 0, make_opts(flags=flags, out_mode=abi.OUT_LAST))
+    fewer = trace(eng, flags, flds[:1], wis[:1], num=NUM - 2)[0]
+    for bad in ([results[0], last], [results[0], fewer]):
+        with pytest.raises(EngineError, match='item 1 is not a FULL packet'):
+            eng.surface_transmission(bad, flags, wis[:2])
+    with pytest.raises(EngineError, match='wvl_idxs'):
+        eng.surface_transmission(results, flags, wis[:1])
+    with pytest.raises(EngineError, match='coat_kind'):
+        eng.surface_transmission(results, flags, wis[:2], coat_kind=np.zeros(table.n_ifcs, np.int32))
+    with pytest.raises(EngineError, match='coat_kind'):
+        eng.surface_transmission(results, flags, wis[:2], coat_kind=np.zeros(3, np.int32), coat_value=np.ones((3, 2)))
+
+    R, N, n_seg = NUM * NUM, table.n_ifcs, eng.num_segments(flags)
+    good = [r.out_struct() for r in results]
+    rows = np.zeros((2, 4, R))
+    surf = np.zeros((2, n_seg), TX_SURFACE_DTYPE)
+    item = np.zeros(2, TX_ITEM_DTYPE)
+    kind, value = np.zeros(N, np.int32), np.ones((N, 2))
+
+    def call(outs=None, n_rays=R, wvl=(0, 2), n_coat=N, kind_=kind, ld_rows=R, tx_flags=0):
+        arr = (abi.Out * 2)(*(outs or good))
+        rows[:] = 7.0
+        surf['n'] = -7
+        item['n_ok'] = -7
+        w = np.array(wvl, np.int32)
+        k = np.ascontiguousarray(kind_, dtype=np.int32)
+        rc = lib.rox_surface_transmission(eng._handle, flags, tx_flags, 2, arr, n_rays, w.ctypes.data, n_coat,
+                                          k.ctypes.data, value.ctypes.data, rows.ctypes.data, ld_rows,
+                                          surf.ctypes.data, item.ctypes.data, None)
+        return rc, lib.rox_last_error().decode()
+
+    def bad(field, v):
+        o = abi.Out.from_buffer_copy(bytes(good[1]))
+        setattr(o, field, v)
+        return [good[0], o]
+
+    k7 = kind.copy()
+    k7[3] = 7
+    cases = [(dict(outs=bad('ld', R - 1)), 'item 1: ld'), (dict(outs=bad('seg', None)), 'item 1'),
+             (dict(outs=bad('status', None)), 'item 1'), (dict(wvl=(0, len(table.wvls))), 'item 1: wvl_idx'),
+             (dict(wvl=(-1, 0)), 'item 0: wvl_idx'), (dict(n_coat=N - 1), 'n_coat'), (dict(kind_=k7), 'coat_kind[3]'),
+             (dict(ld_rows=R - 1), 'ld_rows'), (dict(tx_flags=8), 'tx_flags'), (dict(n_rays=0), 'n_rays')]
+    for kw, word in cases:
+        rc, msg = call(**kw)
+        assert rc == -1 and msg.startswith('rox_surface_transmission: ') and word in msg, (kw, rc, msg)
+        assert (rows == 7.0).all() and (surf['n'] == -7).all() and (item['n_ok'] == -7).all(), f'{kw}: outputs touched'
+    rc, msg = call()
+    assert rc == 0, msg
+    want = eng.surface_transmission(results, flags, [0, 2])
+    assert rows.tobytes() == want[0].tobytes() and surf.tobytes() == want[1].tobytes() and item.tobytes() == want[2].tobytes()
+    eng.close()
+
+
+def test_analysis_on_the_double_gauss(torch):
+    from rayoptics_amd import analyses
+    model = workloads.TableModel('dblgauss_c2')
+    wvls = list(model.workload.table.wvls)
+    kw = dict(flds=model.fields, wvls=wvls, num_rays=NUM)
+    tx = analyses.transmission(model, **kw)
+    F, W = len(model.fields), len(wvls)
+    assert tx.T.shape == (F, W) and tx.T_map.shape == (F, W, NUM, NUM) and tx.relative.shape == (F,)
+    assert tx.relative[0] == 1.0 and tx.relative[-1] < 1.0
+    assert (tx.throughput <= tx.T).all() and (tx.T > 0.5).all() and (tx.T < 0.7).all()
+    assert np.isnan(tx.T_map).any() and np.array_equal(np.isnan(tx.T_map), np.isnan(tx.D_map))
+    assert np.array_equal(np.sum(~np.isnan(tx.T_map), axis=(2, 3)), tx.items['n_ok'])
+    assert tx.surface_loss[0][2] > 0.04 and tx.surface_loss[-1][2] == 0.0
+    assert (tx.diattenuation_max >= tx.diattenuation_mean).all() and tx.diattenuation_max.max() < 0.5
+    # one trace serves both analyses
+    bf = analyses.beam_footprints(model, check_apertures=True, keep_packets=True, **kw)
+    shared = analyses.transmission(model, packets=bf, **kw)
+    assert shared.items.tobytes() == tx.items.tobytes() and shared.surfaces.tobytes() == tx.surfaces.tobytes()
+    assert shared.T_map.tobytes() == tx.T_map.tobytes() and shared.D_map.tobytes() == tx.D_map.tobytes()
+    assert np.array_equal(shared.relative, tx.relative)
+    coated = analyses.transmission(model, coatings=0.995, pupil_maps=False, **kw)
+    assert (coated.T > tx.T).all() and coated.T_map is None
