@@ -1069,6 +1069,35 @@ class BeamFootprints:
         return out
 
 
+def _packet_items(opt_model, flds, wvls, num_rays, check_apertures, what):
+    """every (field, wavelength) item of a packet analysis, field-major, each set up for a FULL
+    launch over the field's vignetted pupil; defaults as _map_spec, ref_wvl the first wavelength
+    given -> (engine, flds, wvls, spectral_wts, fields, wavelength indices, options, trace flags)"""
+    if num_rays < 1 or num_rays * num_rays > abi.MAX_FOOTPRINT_RAYS:
+        raise ValueError(f'{what}: num_rays {num_rays} outside [1, 16384]')
+    flds, wvls, _fw, spectral_wts, _ref = _map_spec(opt_model, flds, wvls, None, None,
+                                                    wvls[0] if wvls is not None and len(wvls) else None, what)
+    fs, wis, opts_list = [], [], []
+    eng = None
+    for fld in flds:
+        for wvl in wvls:
+            kw = dict(check_apertures=bool(check_apertures), apply_vignetting=True)
+            eng, f, wi, opts = _launch_setup(opt_model, fld, wvl, kw, abi.OUT_FULL)
+            fs.append(f)
+            wis.append(wi)
+            opts_list.append(opts)
+    flags = int(opts_list[0].flags)
+    if any(int(o.flags) != flags for o in opts_list):
+        raise ValueError(f'{what}: the fields do not share their trace flags')
+    return eng, flds, wvls, spectral_wts, fs, wis, opts_list, flags
+
+
+def _trace_packets(eng, fs, wis, opts_list, num_rays):
+    """the items' num_rays x num_rays grids over the unit pupil box in one FULL launch; the packets
+    stay in HBM"""
+    return eng.trace_pupil_grids(fs, wis, make_grid((-1., -1.), (1., 1.), num_rays), opts_list, want_pupil=False)
+
+
 def beam_footprints(opt_model, flds=None, wvls=None, num_rays=64, maps=0, check_apertures=False, partial=True,
                     ok_only=False, keep_packets=False):
     """The beam on every surface from a dense pupil grid, on the device: one FULL launch
@@ -1083,29 +1112,13 @@ def beam_footprints(opt_model, flds=None, wvls=None, num_rays=64, maps=0, check_
     record gets h = 1.  ``partial`` / ``ok_only`` select the records as the entry documents.
     Defaults as the through-focus maps: the fields of osp['fov'], the wavelengths of osp['wvls']
     (a workloads.TableModel has no osp: pass them).  Returns :class:`BeamFootprints`."""
-    from .engine import make_opts
     num_rays, maps = int(num_rays), int(maps)
-    if num_rays < 1 or num_rays * num_rays > abi.MAX_FOOTPRINT_RAYS:
-        raise ValueError(f'beam_footprints: num_rays {num_rays} outside [1, 16384]')
     if not 0 <= maps <= abi.MAX_FOOTPRINT_BINS:
         raise ValueError(f'beam_footprints: maps {maps} outside [0, {abi.MAX_FOOTPRINT_BINS}]')
-    flds, wvls, _fw, _sw, _ref = _map_spec(opt_model, flds, wvls, None, None,
-                                           wvls[0] if wvls is not None and len(wvls) else None, 'beam_footprints')
+    eng, flds, wvls, _sw, fs, wis, opts_list, flags = _packet_items(opt_model, flds, wvls, num_rays, check_apertures,
+                                                                    'beam_footprints')
     F, W = len(flds), len(wvls)
-    fs, wis, opts_list = [], [], []
-    eng = None
-    for fld in flds:
-        for wvl in wvls:
-            kw = dict(check_apertures=bool(check_apertures), apply_vignetting=True)
-            eng, f, wi, opts = _launch_setup(opt_model, fld, wvl, kw, abi.OUT_FULL)
-            fs.append(f)
-            wis.append(wi)
-            opts_list.append(opts)
-    flags = int(opts_list[0].flags)
-    if any(int(o.flags) != flags for o in opts_list):
-        raise ValueError('beam_footprints: the fields do not share their trace flags')
-    grid = make_grid((-1., -1.), (1., 1.), num_rays)
-    results = eng.trace_pupil_grids(fs, wis, grid, opts_list, want_pupil=False)
+    results = _trace_packets(eng, fs, wis, opts_list, num_rays)
     rec, _none = eng.surface_footprints(results, flags, partial=partial, ok_only=ok_only)
     n_seg = rec.shape[1]
     tbl = eng.table
@@ -1268,27 +1281,12 @@ def transmission(opt_model, flds=None, wvls=None, num_rays=64, coatings=None, ch
     efficiencies: mirrors, thin lenses and phase elements are counted as ideal.
     Returns :class:`Transmission`."""
     num_rays = int(num_rays)
-    if num_rays < 1 or num_rays * num_rays > abi.MAX_FOOTPRINT_RAYS:
-        raise ValueError(f'transmission: num_rays {num_rays} outside [1, 16384]')
-    flds, wvls, _fw, spectral_wts, _ref = _map_spec(opt_model, flds, wvls, None, None,
-                                                    wvls[0] if wvls is not None and len(wvls) else None,
-                                                    'transmission')
+    eng, flds, wvls, spectral_wts, fs, wis, opts_list, flags = _packet_items(opt_model, flds, wvls, num_rays,
+                                                                             check_apertures, 'transmission')
     F, W = len(flds), len(wvls)
     if not 0 <= int(ref_field) < F:
         raise ValueError(f'transmission: ref_field {ref_field} outside [0, {F})')
-    fs, wis, opts_list, box = [], [], [], []
-    eng = None
-    for fld in flds:
-        for wvl in wvls:
-            kw = dict(check_apertures=bool(check_apertures), apply_vignetting=True)
-            eng, f, wi, opts = _launch_setup(opt_model, fld, wvl, kw, abi.OUT_FULL)
-            fs.append(f)
-            wis.append(wi)
-            opts_list.append(opts)
-        box.append((2.0 - f.vlx - f.vux) * (2.0 - f.vly - f.vuy) / 4.0)
-    flags = int(opts_list[0].flags)
-    if any(int(o.flags) != flags for o in opts_list):
-        raise ValueError('transmission: the fields do not share their trace flags')
+    box = [(2.0 - f.vlx - f.vux) * (2.0 - f.vly - f.vuy) / 4.0 for f in fs[W - 1::W]]     # one per field
     kind, value = _coating_tables(eng.table, coatings)
     if packets is not None:
         flags = int(getattr(packets, 'trace_flags', flags))
@@ -1297,8 +1295,7 @@ def transmission(opt_model, flds=None, wvls=None, num_rays=64, coatings=None, ch
             raise ValueError(f'transmission: packets are not {F * W} items of {num_rays}^2 rays (were they kept '
                              f'with keep_packets=True?)')
     else:
-        grid = make_grid((-1., -1.), (1., 1.), num_rays)
-        results = eng.trace_pupil_grids(fs, wis, grid, opts_list, want_pupil=False)
+        results = _trace_packets(eng, fs, wis, opts_list, num_rays)
     rows, surf, item = eng.surface_transmission(results, flags, wis, coat_kind=kind, coat_value=value,
                                                 want_rows=bool(pupil_maps or fields), fields=bool(fields))
     n_seg = surf.shape[1]

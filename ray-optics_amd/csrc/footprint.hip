@@ -11,17 +11,18 @@
 // read only where the ray has a record there.  Each wave writes one partial record per slot; the
 // finishing kernel merges a slot's partial records in a fixed order (Chan / Golub / LeVeque for
 // the centroid and the second moment, both taken about a pivot ray of the item, footprint_pivot).
-// No floating-point atomics; the maps are integer atomics.
+// No floating-point atomics; the maps are integer atomics.  (Shared with fresnel.hip: rox_packets.hpp.)
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
 #include <cstdint>
-#include <cstring>
 
 #include "rox_device.hpp"
-#include "rox_host.hpp"
+#include "rox_packets.hpp"
 
 namespace {
+
+using rox::kRtDoubles;
 
 constexpr char kHipWhere[] = "rox_surface_footprints: ";
 
@@ -29,7 +30,6 @@ constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / 64;
 constexpr int kRays = 4;                        // rays per thread
 constexpr int kTile = kBlock * kRays;           // rays per workgroup
-constexpr int kRtDoubles = 10;                  // rt[9], rt_order
 // Device scratch of one launch (partial records, records and maps bound for host memory): a call
 // that needs more per launch runs as consecutive launches over fewer items.
 constexpr size_t kFpScratchBytes = size_t(8) << 20;
@@ -348,48 +348,41 @@ __global__ __launch_bounds__(kBlock) void footprint_kernel(const FpArgs a)
     }
 }
 
-// fp[item][k] from part[item][w][k], w = 0 .. n_waves - 1: thread t merges w = t, t + kBlock, ...
-// in that order, then the threads merge as a binary tree -- one fixed order
+// what the partial records of an (item, slot) merge into, and its count s as either holds it
+struct Sum {
+    Acc a;
+    int64_t c[5];                               // n_fail[1..4], n_inc
+};
+
+__device__ __forceinline__ int64_t count_of(const Sum &b, int s) { return b.c[s]; }
+__device__ __forceinline__ int64_t count_of(const Part &q, int s)
+{
+    return s < 4 ? (int64_t)((q.nf >> (16 * s)) & 0xffff) : (int64_t)q.n_inc;
+}
+
+// fp[item][k] from part[item][w][k], w = 0 .. n_waves - 1, in the order of rox::block_merge
 __global__ __launch_bounds__(kBlock) void footprint_finish(const Part *__restrict__ part, int n_waves, int n_seg,
                                                            const double *__restrict__ pivot,
                                                            rox_footprint *__restrict__ fp)
 {
-    __shared__ Acc sa[kBlock];
-    __shared__ int64_t si[kBlock][5];
-    const int k = blockIdx.x, t = threadIdx.x;
-    const Part *p = part + (size_t)blockIdx.y * n_waves * n_seg + k;
-    Acc acc = acc_empty();
-    int64_t c[5] = {0, 0, 0, 0, 0};             // n_fail[1..4], n_inc
-    for (int w = t; w < n_waves; w += kBlock) {
-        const Part q = p[(size_t)w * n_seg];
-        acc_merge(acc, q.a);
-        for (int s = 0; s < 4; ++s)
-            c[s] += (int64_t)((q.nf >> (16 * s)) & 0xffff);
-        c[4] += q.n_inc;
-    }
-    sa[t] = acc;
-    for (int s = 0; s < 5; ++s)
-        si[t][s] = c[s];
-    __syncthreads();
-    for (int h = kBlock / 2; h > 0; h >>= 1) {
-        if (t < h) {
-            Acc m = sa[t];
-            acc_merge(m, sa[t + h]);
-            sa[t] = m;
-            for (int s = 0; s < 5; ++s)
-                si[t][s] += si[t + h][s];
-        }
-        __syncthreads();
-    }
-    if (t == 0) {
-        const Acc m = sa[0];
+    __shared__ Sum lds[kBlock];
+    const int k = blockIdx.x;
+    const auto merge = [](Sum &m, const auto &b) {
+        acc_merge(m.a, b.a);
+        for (int s = 0; s < 5; ++s)
+            m.c[s] += count_of(b, s);
+    };
+    const Sum sum = rox::block_merge<kBlock>(part + (size_t)blockIdx.y * n_waves * n_seg + k, n_waves, n_seg,
+                                             Sum{acc_empty(), {0, 0, 0, 0, 0}}, merge, lds);
+    if (threadIdx.x == 0) {
+        const Acc m = sum.a;
         const double nan = __builtin_nan("");
         rox_footprint f;
         f.n = (int64_t)m.n;
         f.n_fail[0] = 0;
         for (int s = 0; s < 4; ++s)
-            f.n_fail[s + 1] = si[0][s];
-        f.n_inc = si[0][4];
+            f.n_fail[s + 1] = sum.c[s];
+        f.n_inc = sum.c[4];
         f.min[0] = m.minx; f.min[1] = m.miny;
         f.max[0] = m.maxx; f.max[1] = m.maxy;
         f.r2_max = m.r2;
@@ -414,27 +407,17 @@ extern "C" int rox_surface_footprints(rox_system *sys, uint32_t trace_flags, uin
 {
     static const char kE[] = "rox_surface_footprints";
     // every argument check comes before anything touches a device
-    if (!sys || !outs)
-        return rox::host_fail(ROX_E_ARG, "%s: null sys or outs", kE);
-    ROX_TRY(rox::check_range(kE, "n_items", n_items, 1, ROX_MAX_FOCUS_ITEMS));
+    ROX_TRY(rox::check_packet_call(kE, sys, outs, n_items));
     if (fp_flags & ~(ROX_FP_PARTIAL | ROX_FP_OK_ONLY))
         return rox::host_fail(ROX_E_ARG, "%s: unknown fp_flags bits 0x%x", kE,
                               fp_flags & ~(ROX_FP_PARTIAL | ROX_FP_OK_ONLY));
-    if (n_rays < 1 || n_rays > (int64_t(1) << 28))
-        return rox::host_fail(ROX_E_ARG, "%s: n_rays %lld outside [1, 2^28]", kE, (long long)n_rays);
+    ROX_TRY(rox::check_packet_rays(kE, n_rays));
     if (!fp && !maps)
         return rox::host_fail(ROX_E_ARG, "%s: null fp and maps", kE);
-    for (int32_t i = 0; i < n_items; ++i) {
-        if (!outs[i].seg || !outs[i].status || !outs[i].fail_surf)
-            return rox::host_fail(ROX_E_ARG, "%s: item %d: null seg, status or fail_surf", kE, i);
-        if (outs[i].ld < n_rays)
-            return rox::host_fail(ROX_E_ARG, "%s: item %d: ld %lld < n_rays %lld", kE, i, (long long)outs[i].ld,
-                                  (long long)n_rays);
-    }
-    int32_t n_ifcs = 0, n_seg = 0;
-    std::vector<int32_t> slots;
-    const rox_surface *rows = rox::system_rows(sys, &n_ifcs);
-    rox::system_slot_map(sys, (trace_flags & ROX_FILTER_PHANTOMS) != 0, slots, n_seg);
+    for (int32_t i = 0; i < n_items; ++i)
+        ROX_TRY(rox::check_packet_item(kE, i, outs[i], n_rays, true));
+    const rox::PacketSlots ps(sys, trace_flags);
+    const int32_t n_ifcs = ps.n_ifcs, n_seg = ps.n_seg;
     if (maps) {
         if (!half_width)
             return rox::host_fail(ROX_E_ARG, "%s: maps needs half_width", kE);
@@ -481,18 +464,12 @@ extern "C" int rox_surface_footprints(rox_system *sys, uint32_t trace_flags, uin
     char *h = ws->stage.h;
     for (int32_t i = 0; i < n_items; ++i)
         ((ItemIn *)h)[i] = ItemIn{outs[i].seg, outs[i].status, outs[i].fail_surf, outs[i].ld};
-    for (int32_t i = 0; i < n_ifcs; ++i) {
-        double *rt = (double *)(h + o_rt) + (size_t)i * kRtDoubles;
-        memcpy(rt, rows[i].rt, sizeof(double) * 9);
-        rt[9] = rows[i].rt_order == ROX_RT_C_ORDER ? 1.0 : 0.0;
-    }
+    ps.stage_rt((double *)(h + o_rt));
     for (int k = 0; k < n_seg; ++k)
         ((double *)(h + o_hw))[k] = maps ? half_width[k] : 0.0;
-    for (int32_t i = 0; i < n_ifcs; ++i) {
-        ((int32_t *)(h + o_nb))[i] = slots[n_ifcs + i];
-        if (slots[i] >= 0)
-            ((int32_t *)(h + o_si))[slots[i]] = i;
-    }
+    for (int32_t i = 0; i < n_ifcs; ++i)
+        ((int32_t *)(h + o_nb))[i] = ps.slots[n_ifcs + i];
+    ps.stage_slot_ifc((int32_t *)(h + o_si));
     HIP_TRY(hipMemcpyAsync(d_tab, h, b_tab, hipMemcpyHostToDevice, st));
     HIP_TRY(ws->stage.record(st));
 

@@ -11,20 +11,21 @@
 // its coating values, the rt of the interfaces in between -- is read through the constant address
 // space at wave-uniform addresses: scalar loads into SGPRs (the kernel's only vector loads are
 // the status byte and the twelve packet reads of a slot).  Each wave writes one partial record per slot and one for the item; the
-// finishing kernel merges them in a fixed order.  No floating-point atomics.
+// finishing kernel merges them in a fixed order.  No floating-point atomics.  (Shared with
+// footprint.hip: rox_packets.hpp.)
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <cstring>
 
 #include "rox_device.hpp"
-#include "rox_host.hpp"
+#include "rox_packets.hpp"
 #include "rox_system.hpp"
 
 namespace {
 
 using rox::ctbli;
 using rox::ctblp;
+using rox::kRtDoubles;
 
 constexpr char kHipWhere[] = "rox_surface_transmission: ";
 
@@ -32,7 +33,6 @@ constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / 64;
 constexpr int kRays = 2;                        // rays per thread: 107 VGPRs, no scratch, 4 waves per SIMD
 constexpr int kTile = kBlock * kRays;           // rays per workgroup
-constexpr int kRtDoubles = 10;                  // rt[9], rt_order
 // Device scratch of one launch (partial records, records, rows bound for host memory): a call that
 // needs more per launch runs as consecutive launches over fewer items and, for the rows, fewer
 // rays.  One item's partial records are not split: an item whose records exceed the cap (more than
@@ -320,30 +320,8 @@ __global__ __launch_bounds__(kBlock) void fresnel_kernel(const TxArgs a)
     }
 }
 
-// thread t merges the partial records w = t, t + kBlock, ... of its (item, slot) in that order, then
-// the threads merge as a binary tree -- one fixed order
-template <bool kItem>
-__device__ __forceinline__ Part finish_merge(const Part *__restrict__ p, int n_waves, int stride, Part *sa)
-{
-    const int t = threadIdx.x;
-    const double inf = __builtin_inf();
-    Part acc = kItem ? Part{{0.0, 0.0, 0.0, 0.0, inf, -inf, 0.0, -inf}} : part_empty();
-    for (int w = t; w < n_waves; w += kBlock)
-        part_merge<kItem>(acc, p[(size_t)w * stride]);
-    sa[t] = acc;
-    __syncthreads();
-    for (int h = kBlock / 2; h > 0; h >>= 1) {
-        if (t < h) {
-            Part m = sa[t];
-            part_merge<kItem>(m, sa[t + h]);
-            sa[t] = m;
-        }
-        __syncthreads();
-    }
-    return sa[0];
-}
-
-// block (k, item): slot k's record, or with k == n_seg the item's
+// block (k, item): slot k's record, or with k == n_seg the item's, its partial records merged in the
+// order of rox::block_merge
 __global__ __launch_bounds__(kBlock) void fresnel_finish(const Part *__restrict__ part, int n_waves, int n_seg,
                                                          int64_t n_rays, rox_tx_surface *__restrict__ surf,
                                                          rox_tx_item *__restrict__ item)
@@ -351,9 +329,10 @@ __global__ __launch_bounds__(kBlock) void fresnel_finish(const Part *__restrict_
     __shared__ Part sa[kBlock];
     const int k = blockIdx.x;
     const Part *p = part + (size_t)blockIdx.y * n_waves * (n_seg + 1) + k;
-    const double nan = __builtin_nan("");
+    const double nan = __builtin_nan(""), inf = __builtin_inf();
     if (k < n_seg) {
-        const Part m = finish_merge<false>(p, n_waves, n_seg + 1, sa);
+        const Part m = rox::block_merge<kBlock>(p, n_waves, n_seg + 1, part_empty(),
+                                                [](Part &a, const Part &b) { part_merge<false>(a, b); }, sa);
         if (threadIdx.x == 0) {
             const bool any = m.v[0] > 0.0;
             rox_tx_surface f;
@@ -364,7 +343,8 @@ __global__ __launch_bounds__(kBlock) void fresnel_finish(const Part *__restrict_
             surf[(size_t)blockIdx.y * n_seg + k] = f;
         }
     } else {
-        const Part m = finish_merge<true>(p, n_waves, n_seg + 1, sa);
+        const Part m = rox::block_merge<kBlock>(p, n_waves, n_seg + 1, Part{{0.0, 0.0, 0.0, 0.0, inf, -inf, 0.0, -inf}},
+                                                [](Part &a, const Part &b) { part_merge<true>(a, b); }, sa);
         if (threadIdx.x == 0) {
             const bool any = m.v[0] > 0.0;
             rox_tx_item f;
@@ -391,13 +371,10 @@ extern "C" int rox_surface_transmission(rox_system *sys, uint32_t trace_flags, u
     static const char kE[] = "rox_surface_transmission";
     // every argument check comes before anything touches a device; those that do not need the
     // system come before the system is read
-    if (!sys || !outs)
-        return rox::host_fail(ROX_E_ARG, "%s: null sys or outs", kE);
-    ROX_TRY(rox::check_range(kE, "n_items", n_items, 1, ROX_MAX_FOCUS_ITEMS));
+    ROX_TRY(rox::check_packet_call(kE, sys, outs, n_items));
     if (tx_flags & ~ROX_TX_FIELDS)
         return rox::host_fail(ROX_E_ARG, "%s: unknown tx_flags bits 0x%x", kE, tx_flags & ~ROX_TX_FIELDS);
-    if (n_rays < 1 || n_rays > (int64_t(1) << 28))
-        return rox::host_fail(ROX_E_ARG, "%s: n_rays %lld outside [1, 2^28]", kE, (long long)n_rays);
+    ROX_TRY(rox::check_packet_rays(kE, n_rays));
     if (!rows && !surf && !item)
         return rox::host_fail(ROX_E_ARG, "%s: null rows, surf and item", kE);
     if (rows && ld_rows < n_rays)
@@ -405,11 +382,7 @@ extern "C" int rox_surface_transmission(rox_system *sys, uint32_t trace_flags, u
     if (!wvl_idx)
         return rox::host_fail(ROX_E_ARG, "%s: null wvl_idx", kE);
     for (int32_t i = 0; i < n_items; ++i) {
-        if (!outs[i].seg || !outs[i].status)
-            return rox::host_fail(ROX_E_ARG, "%s: item %d: null seg or status", kE, i);
-        if (outs[i].ld < n_rays)
-            return rox::host_fail(ROX_E_ARG, "%s: item %d: ld %lld < n_rays %lld", kE, i, (long long)outs[i].ld,
-                                  (long long)n_rays);
+        ROX_TRY(rox::check_packet_item(kE, i, outs[i], n_rays, false));
         if (wvl_idx[i] < 0)
             return rox::host_fail(ROX_E_ARG, "%s: item %d: wvl_idx %d outside the index table", kE, i, wvl_idx[i]);
     }
@@ -428,16 +401,14 @@ extern "C" int rox_surface_transmission(rox_system *sys, uint32_t trace_flags, u
                                           coat_value[2 * s + c]);
         }
     }
-    int32_t n_ifcs = 0, n_seg = 0;
-    std::vector<int32_t> slots;
-    const rox_surface *srow = rox::system_rows(sys, &n_ifcs);
+    const rox::PacketSlots ps(sys, trace_flags);
+    const int32_t n_ifcs = ps.n_ifcs, n_seg = ps.n_seg;
     for (int32_t i = 0; i < n_items; ++i)
         if (wvl_idx[i] >= sys->n_wvls)
             return rox::host_fail(ROX_E_ARG, "%s: item %d: wvl_idx %d outside the index table of %d wavelengths",
                                   kE, i, wvl_idx[i], sys->n_wvls);
     if (coat_kind && n_coat != n_ifcs)
         return rox::host_fail(ROX_E_ARG, "%s: n_coat %d is not the number of interfaces %d", kE, n_coat, n_ifcs);
-    rox::system_slot_map(sys, (trace_flags & ROX_FILTER_PHANTOMS) != 0, slots, n_seg);
 
     hipStream_t st = (hipStream_t)stream;
     rox::PerStream<rox::Workspace>::Slot *slot;
@@ -484,25 +455,23 @@ extern "C" int rox_surface_transmission(rox_system *sys, uint32_t trace_flags, u
     char *h = ws->stage.h;
     for (int32_t i = 0; i < n_items; ++i)
         ((ItemIn *)h)[i] = ItemIn{outs[i].seg, outs[i].status, outs[i].ld, wvl_idx[i], 0};
+    ps.stage_rt((double *)(h + o_rt));
+    ps.stage_slot_ifc((int32_t *)(h + o_si));
     for (int32_t i = 0; i < n_ifcs; ++i) {
-        double *rt = (double *)(h + o_rt) + (size_t)i * kRtDoubles;
-        memcpy(rt, srow[i].rt, sizeof(double) * 9);
-        rt[9] = srow[i].rt_order == ROX_RT_C_ORDER ? 1.0 : 0.0;
+        const rox_surface &row = ps.rows[i];
         const int kind = coat_kind ? coat_kind[i] : ROX_COAT_BARE;
-        const bool mirror = srow[i].mode == ROX_REFLECT, glass = srow[i].mode == ROX_TRANSMIT;
+        const bool mirror = row.mode == ROX_REFLECT, glass = row.mode == ROX_TRANSMIT;
         int32_t model = kIdeal;
         if (mirror)
             model = kind == ROX_COAT_FIXED ? kFixedMirror : kMirror;
         else if (glass && kind == ROX_COAT_FIXED)
             model = kFixed;
-        else if (glass && kind == ROX_COAT_BARE && srow[i].profile != ROX_THINLENS && srow[i].ph.kind == ROX_PH_NONE)
+        else if (glass && kind == ROX_COAT_BARE && row.profile != ROX_THINLENS && row.ph.kind == ROX_PH_NONE)
             model = kBare;
         const bool fixed = model == kFixed || model == kFixedMirror;
         ((double *)(h + o_cv))[2 * i] = fixed ? coat_value[2 * i] : 1.0;
         ((double *)(h + o_cv))[2 * i + 1] = fixed ? coat_value[2 * i + 1] : 1.0;
         ((int32_t *)(h + o_md))[i] = model;
-        if (slots[i] >= 0)
-            ((int32_t *)(h + o_si))[slots[i]] = i;
     }
     HIP_TRY(hipMemcpyAsync(d_tab, h, b_tab, hipMemcpyHostToDevice, st));
     HIP_TRY(ws->stage.record(st));

@@ -1,0 +1,97 @@
+// rox_packets.hpp -- what the entries that walk the ROX_OUT_FULL packets of finished launches share
+// (footprint.hip, fresnel.hip): their argument checks, a system's slot tables as their kernels read
+// them, and the fixed-order merge of their finishing kernels.
+#pragma once
+
+#include <cstring>
+
+#include "rox_host.hpp"
+
+namespace rox {
+
+constexpr int kRtDoubles = 10;                  // an interface's staged row: rt[9], rt_order
+
+// ---- argument checks (as rox_host.hpp's); an entry calls them in its own order
+inline int check_packet_call(const char *e, const rox_system *sys, const rox_out *outs, int32_t n_items)
+{
+    if (!sys || !outs)
+        return host_fail(ROX_E_ARG, "%s: null sys or outs", e);
+    return check_range(e, "n_items", n_items, 1, ROX_MAX_FOCUS_ITEMS);
+}
+
+inline int check_packet_rays(const char *e, int64_t n_rays)
+{
+    if (n_rays < 1 || n_rays > (int64_t(1) << 28))
+        return host_fail(ROX_E_ARG, "%s: n_rays %lld outside [1, 2^28]", e, (long long)n_rays);
+    return 0;
+}
+
+// item i: the rows the entry reads are there and hold n_rays rays
+inline int check_packet_item(const char *e, int32_t i, const rox_out &out, int64_t n_rays, bool need_fail_surf)
+{
+    if (!out.seg || !out.status || (need_fail_surf && !out.fail_surf))
+        return host_fail(ROX_E_ARG, "%s: item %d: null %s", e, i,
+                         need_fail_surf ? "seg, status or fail_surf" : "seg or status");
+    if (out.ld < n_rays)
+        return host_fail(ROX_E_ARG, "%s: item %d: ld %lld < n_rays %lld", e, i, (long long)out.ld, (long long)n_rays);
+    return 0;
+}
+
+// ---- a system's interfaces and the FULL-packet slots of launches traced with trace_flags
+struct PacketSlots {
+    int32_t n_ifcs = 0, n_seg = 0;
+    const rox_surface *rows;                    // system_rows
+    std::vector<int32_t> slots;                 // system_slot_map
+
+    PacketSlots(const rox_system *sys, uint32_t trace_flags) : rows(system_rows(sys, &n_ifcs))
+    {
+        system_slot_map(sys, (trace_flags & ROX_FILTER_PHANTOMS) != 0, slots, n_seg);
+    }
+
+    // dst[n_ifcs][kRtDoubles]: rt, then 1.0 for ROX_RT_C_ORDER and 0.0 for ROX_RT_F_ORDER
+    void stage_rt(double *dst) const
+    {
+        for (int32_t i = 0; i < n_ifcs; ++i, dst += kRtDoubles) {
+            memcpy(dst, rows[i].rt, sizeof(double) * 9);
+            dst[9] = rows[i].rt_order == ROX_RT_C_ORDER ? 1.0 : 0.0;
+        }
+    }
+
+    // dst[n_seg]: the interface of slot k
+    void stage_slot_ifc(int32_t *dst) const
+    {
+        for (int32_t i = 0; i < n_ifcs; ++i)
+            if (slots[i] >= 0)
+                dst[slots[i]] = i;
+    }
+};
+
+// ---- the merge of a finishing kernel, by a workgroup of kBlock threads: the n records p[w * stride]
+// into one, in one fixed order whatever the launch -- thread t merges w = t, t + kBlock, ... in that
+// order into `init`, then the threads merge as a binary tree through lds[kBlock], the lower thread's
+// first.  merge(a, b) is a <- a merged with b, for b a record and for b a merged value.
+template <int kBlock, class In, class T, class Merge>
+__device__ __forceinline__ T block_merge(const In *__restrict__ p, int n, int stride, T init, Merge merge, T *lds)
+{
+    const int t = threadIdx.x;
+    for (int w = t; w < n; w += kBlock) {
+        // a copy, here and of lds[t + h]: a record's loads are issued together, not one where each
+        // value is first used (footprint_finish took 8 us longer per launch at 4096 waves without it)
+        const In q = p[(size_t)w * stride];
+        merge(init, q);
+    }
+    lds[t] = init;
+    __syncthreads();
+    for (int h = kBlock / 2; h > 0; h >>= 1) {
+        if (t < h) {
+            T m = lds[t];
+            const T o = lds[t + h];
+            merge(m, o);
+            lds[t] = m;
+        }
+        __syncthreads();
+    }
+    return lds[0];
+}
+
+}  // namespace rox

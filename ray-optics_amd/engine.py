@@ -138,6 +138,13 @@ FOCUS_STATS_DTYPE = np.dtype([(name, np.int64 if name == 'n' else np.float64)
 assert FOCUS_STATS_DTYPE.itemsize == C.sizeof(abi.FocusStats)
 
 
+def records_view(raw, dtype):
+    """the raw uint8 records [.., dtype.itemsize] an entry returns with ``on_device`` (a tensor, or
+    its NumPy copy) -> a ``dtype`` array [..] on the host"""
+    a = np.ascontiguousarray(raw.cpu().numpy() if hasattr(raw, 'cpu') else raw)
+    return a.view(dtype).reshape(a.shape[:-1])
+
+
 # rox_focus_psf_stats: what focus_psf returns
 FOCUS_PSF_STATS_DTYPE = np.dtype([(name, np.int64 if name == 'n' else np.float64)
                                   for name, _t in abi.FocusPsfStats._fields_])
@@ -156,8 +163,7 @@ assert FOOTPRINT_DTYPE.itemsize == C.sizeof(abi.Footprint)
 def footprint_view(records):
     """the uint8 tensor [n_items, n_seg, 144] surface_footprints(on_device=True) returns -> a
     FOOTPRINT_DTYPE array [n_items, n_seg] on the host"""
-    a = np.ascontiguousarray(records.cpu().numpy() if hasattr(records, 'cpu') else records)
-    return a.view(FOOTPRINT_DTYPE).reshape(a.shape[:-1])
+    return records_view(records, FOOTPRINT_DTYPE)
 
 
 # rox_tx_surface / rox_tx_item: what surface_transmission returns
@@ -172,8 +178,7 @@ assert TX_ITEM_DTYPE.itemsize == C.sizeof(abi.TxItem)
 def tx_view(records, dtype):
     """the uint8 tensor surface_transmission(on_device=True) returns for ``surf`` or ``item`` -> a
     TX_SURFACE_DTYPE / TX_ITEM_DTYPE array on the host"""
-    a = np.ascontiguousarray(records.cpu().numpy() if hasattr(records, 'cpu') else records)
-    return a.view(dtype).reshape(a.shape[:-1])
+    return records_view(records, dtype)
 
 
 # rox_zernike_stats: what focus_zernike returns
@@ -186,8 +191,7 @@ assert ZERNIKE_STATS_DTYPE.itemsize == C.sizeof(abi.ZernikeStats)
 def zernike_stats_view(raw):
     """the ZERNIKE_STATS_DTYPE array [..] of the raw uint8 records [.., 56] focus_zernike returns
     with ``on_device`` (copied to the host)"""
-    a = np.ascontiguousarray(raw.cpu().numpy() if hasattr(raw, 'cpu') else raw)
-    return a.view(ZERNIKE_STATS_DTYPE).reshape(a.shape[:-1])
+    return records_view(raw, ZERNIKE_STATS_DTYPE)
 
 
 class FocusRows:
@@ -1009,6 +1013,25 @@ class TraceEngine:
         a = np.empty(shape, dtype=dtype)
         return a, a.ctypes.data
 
+    def _records_out(self, on_device, shape, dtype):
+        """_out for the records of a C struct: a ``dtype`` array, or with ``on_device`` a uint8
+        tensor of the struct's bytes per record (``records_view`` reads it on the host)"""
+        return self._out(on_device, shape, dtype, self.torch.uint8, (*shape, dtype.itemsize))
+
+    def _packets(self, results, trace_flags, what):
+        """the FULL packets of finished launches (a single DeviceResult gains the item axis) ->
+        (results, n_items, n_seg, R, outs), outs the abi.Out array a packet entry reads"""
+        results = [results] if isinstance(results, DeviceResult) else list(results)
+        n_items = len(results)
+        if not 1 <= n_items <= abi.MAX_FOCUS_ITEMS:
+            raise EngineError(f'{what}: 1 to {abi.MAX_FOCUS_ITEMS} items, got {n_items}')
+        n_seg = self.num_segments(int(trace_flags))
+        R = int(results[0].R)
+        for i, r in enumerate(results):
+            if r.out_mode != abi.OUT_FULL or int(r.seg.shape[0]) != n_seg or int(r.R) != R:
+                raise EngineError(f'{what}: item {i} is not a FULL packet of {n_seg} segments and {R} rays')
+        return results, n_items, n_seg, R, (abi.Out * n_items)(*[r.out_struct() for r in results])
+
     @_in_flight
     def focus_psf(self, focus_rows, ndim, maxdim, wave_scale, want_psf=True):
         """rox_focus_psf over the rows of a through-focus launch (``focus_rows``: the FocusRows
@@ -1171,8 +1194,7 @@ class TraceEngine:
         ws = _f64(wave_scale, (n_items,))
         c = _f64(circle, (n_items, 3)) if circle is not None else None
         coef, p_coef = self._out(on_device, (n_items, K, J), np.float64, t.float64)
-        stats, p_stats = self._out(on_device, (n_items, K), ZERNIKE_STATS_DTYPE, t.uint8,
-                                   (n_items, K, C.sizeof(abi.ZernikeStats)))
+        stats, p_stats = self._records_out(on_device, (n_items, K), ZERNIKE_STATS_DTYPE)
         with t.cuda.device(self.device):
             _check(self.lib.rox_focus_zernike(n_items, K, rows.data_ptr(), ld, status.data_ptr(), g_arr,
                                               c.ctypes.data if c is not None else None, ws.ctypes.data, J,
@@ -1203,18 +1225,7 @@ class TraceEngine:
         of the raw records (``footprint_view`` reads it on the host) and an int32 tensor of the
         map's bit patterns."""
         t = self.torch
-        if isinstance(results, DeviceResult):
-            results = [results]
-        results = list(results)
-        n_items = len(results)
-        if not 1 <= n_items <= abi.MAX_FOCUS_ITEMS:
-            raise EngineError(f'surface_footprints: 1 to {abi.MAX_FOCUS_ITEMS} items, got {n_items}')
-        n_seg = self.num_segments(int(trace_flags))
-        R = int(results[0].R)
-        for i, r in enumerate(results):
-            if r.out_mode != abi.OUT_FULL or int(r.seg.shape[0]) != n_seg or int(r.R) != R:
-                raise EngineError(f'surface_footprints: item {i} is not a FULL packet of {n_seg} segments and '
-                                  f'{R} rays')
+        results, n_items, n_seg, R, outs = self._packets(results, trace_flags, 'surface_footprints')
         n_bins = int(n_bins)
         if not want_records and n_bins <= 0:
             raise EngineError('surface_footprints: records or maps (or both)')
@@ -1228,10 +1239,8 @@ class TraceEngine:
             if not (np.isfinite(hw).all() and (hw > 0).all()):
                 raise EngineError('surface_footprints: half_width must be finite and > 0')
         flags = (abi.FP_PARTIAL if partial else 0) | (abi.FP_OK_ONLY if ok_only else 0)
-        outs = (abi.Out * n_items)(*[r.out_struct() for r in results])
         none = (None, None)
-        rec, p_rec = self._out(on_device, (n_items, n_seg), FOOTPRINT_DTYPE, t.uint8,
-                               (n_items, n_seg, C.sizeof(abi.Footprint))) if want_records else none
+        rec, p_rec = self._records_out(on_device, (n_items, n_seg), FOOTPRINT_DTYPE) if want_records else none
         maps, p_maps = self._out(on_device, (n_items, n_seg, n_bins, n_bins), np.uint32, t.int32) \
             if n_bins > 0 else none
         with t.cuda.device(self.device):
@@ -1254,18 +1263,7 @@ class TraceEngine:
         [n_items] -- NumPy, or with ``on_device`` torch tensors (the records as uint8 [..., 64]
         and [n_items, 72]; ``tx_view`` reads them on the host)."""
         t = self.torch
-        if isinstance(results, DeviceResult):
-            results = [results]
-        results = list(results)
-        n_items = len(results)
-        if not 1 <= n_items <= abi.MAX_FOCUS_ITEMS:
-            raise EngineError(f'surface_transmission: 1 to {abi.MAX_FOCUS_ITEMS} items, got {n_items}')
-        n_seg = self.num_segments(int(trace_flags))
-        R = int(results[0].R)
-        for i, r in enumerate(results):
-            if r.out_mode != abi.OUT_FULL or int(r.seg.shape[0]) != n_seg or int(r.R) != R:
-                raise EngineError(f'surface_transmission: item {i} is not a FULL packet of {n_seg} segments and '
-                                  f'{R} rays')
+        results, n_items, n_seg, R, outs = self._packets(results, trace_flags, 'surface_transmission')
         wi = np.ascontiguousarray(np.asarray(wvl_idxs, dtype=np.int32).reshape(-1))
         if wi.shape[0] != n_items:
             raise EngineError(f'surface_transmission: {wi.shape[0]} wvl_idxs for {n_items} items')
@@ -1280,12 +1278,10 @@ class TraceEngine:
                 raise EngineError(f'surface_transmission: coat_kind [{ck.shape[0]}] and coat_value '
                                   f'{list(cv.shape)} are not [{N}] and [{N}, 2], one entry per interface')
         n_rows = 10 if fields else 4
-        outs = (abi.Out * n_items)(*[r.out_struct() for r in results])
         rows, p_rows = self._out(on_device, (n_items, n_rows, R), np.float64, t.float64) if want_rows \
             else (None, None)
-        surf, p_surf = self._out(on_device, (n_items, n_seg), TX_SURFACE_DTYPE, t.uint8,
-                                 (n_items, n_seg, C.sizeof(abi.TxSurface)))
-        item, p_item = self._out(on_device, (n_items,), TX_ITEM_DTYPE, t.uint8, (n_items, C.sizeof(abi.TxItem)))
+        surf, p_surf = self._records_out(on_device, (n_items, n_seg), TX_SURFACE_DTYPE)
+        item, p_item = self._records_out(on_device, (n_items,), TX_ITEM_DTYPE)
         with t.cuda.device(self.device):
             _check(self.lib.rox_surface_transmission(self._handle, int(trace_flags), abi.TX_FIELDS if fields else 0,
                                                      n_items, outs, R, wi.ctypes.data, N if ck is not None else 0,

@@ -5,14 +5,16 @@ extremes within 8 * 2^-53), a case with MISSED and TIR rays traced by the oracle
 FULL packets of the double Gauss and the .zmx zoom (9 items, 256^2 rays), phantom filtering, a
 1024^2 x 9 job split into several launches, bit-identical repeats, degenerate inputs, every
 argument error, and analyses.beam_footprints on the double Gauss."""
-import ctypes as C
+import functools
 import math
 
 import numpy as np
 import pytest
 
 import footprint_ref as FR
+import packets_fixture
 from helpers import field_from_arr, fixture
+from packets_fixture import torch, trace_packets, upload  # noqa: F401 (torch: the fixture)
 from rayoptics_amd import abi, workloads
 
 pytestmark = pytest.mark.gpu
@@ -24,24 +26,7 @@ GROUPS = [('dblgauss', 'rays_ap', 232, 152), ('dblgauss', 'grid_f0', 88, 56), ('
 FLAGS = [(False, False), (True, False), (False, True), (True, True)]
 
 
-@pytest.fixture(scope='module')
-def torch():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip('no GPU')
-    return torch
-
-
-def upload(eng, seg, status, fail_surf):
-    """host packets -> a DeviceResult-shaped FULL buffer (NaN where no record was written)"""
-    from rayoptics_amd.engine import DeviceResult
-    t = eng.torch
-    n_seg, _ten, R = seg.shape
-    res = DeviceResult(t, eng.device, n_seg, R, abi.OUT_FULL, False, True)
-    res.seg.copy_(t.from_numpy(np.ascontiguousarray(seg)))
-    res.status.copy_(t.from_numpy(np.ascontiguousarray(status, dtype=np.uint8)))
-    res.fail_surf.copy_(t.from_numpy(np.ascontiguousarray(fail_surf, dtype=np.int16)))
-    return res
+host_of = functools.partial(packets_fixture.host_of, want=('seg', 'status', 'fail_surf'))
 
 
 def log2_ceil(n):
@@ -143,20 +128,9 @@ def test_missed_and_tir_rays(torch):
 
 
 def traced_items(eng, wl, num, n_items, flags=SPOT):
-    from rayoptics_amd.engine import make_grid, make_opts
     F, W = len(wl.fields), len(wl.table.wvls)
     flds = [wl.fields[(i // W) % F] for i in range(n_items)]
-    wis = [i % W for i in range(n_items)]
-    opts = [make_opts(flags=flags, out_mode=abi.OUT_FULL) for _ in range(n_items)]
-    return eng.trace_pupil_grids(flds, wis, make_grid((-1., -1.), (1., 1.), num), opts, want_pupil=False)
-
-
-def host_of(results):
-    out = []
-    for r in results:
-        h = r.to_host(want=('seg', 'status', 'fail_surf'))
-        out.append((np.array(h.seg), np.array(h.status), np.array(h.fail_surf)))
-    return out
+    return trace_packets(eng, flags, flds, [i % W for i in range(n_items)], num)
 
 
 @pytest.mark.parametrize('name', ['dblgauss_c2', 'zmx_evenasph_c3'])

@@ -13,14 +13,16 @@ step 0.125 is exact and the centre ray is the axial ray.
 A packet that is not FULL, or has another ray count, is refused by TraceEngine (the C entry
 cannot see a buffer's out_mode); what the C entry itself refuses is checked with sentinels in the
 outputs."""
-import ctypes as C
+import functools
 import math
 
 import numpy as np
 import pytest
 
 import fresnel_ref as FR
+import packets_fixture
 from helpers import bit_equal, field_from_arr, fixture
+from packets_fixture import torch  # noqa: F401 (the fixture)
 from rayoptics_amd import abi, workloads
 from fresnel_ref import AB_BOUND, CLOSED, EPS
 
@@ -29,14 +31,6 @@ pytestmark = pytest.mark.gpu
 SPOT = abi.INTERSECT_OBJ | abi.CHECK_APERTURES | abi.APPLY_VIGNETTING
 NUM = 15
 CENTRE = (NUM // 2) * NUM + NUM // 2
-
-
-@pytest.fixture(scope='module')
-def torch():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip('no GPU')
-    return torch
 
 
 def case(name):
@@ -52,18 +46,8 @@ def case(name):
     return wl.table, SPOT, [wl.fields[f] for f in picks[0]], picks[1]
 
 
-def trace(eng, flags, flds, wis, num=NUM, span=1.0):
-    from rayoptics_amd.engine import make_grid, make_opts
-    opts = [make_opts(flags=flags, out_mode=abi.OUT_FULL) for _ in flds]
-    return eng.trace_pupil_grids(flds, wis, make_grid((-span, -span), (span, span), num), opts, want_pupil=False)
-
-
-def host_of(results):
-    out = []
-    for r in results:
-        h = r.to_host(want=('seg', 'status'))
-        out.append((np.array(h.seg), np.array(h.status)))
-    return out
+trace = functools.partial(packets_fixture.trace_packets, num=NUM)
+host_of = functools.partial(packets_fixture.host_of, want=('seg', 'status'))
 
 
 def same(a, b):

@@ -51,7 +51,7 @@ def main():
     args = ap.parse_args()
     import torch
     import rayoptics_amd  # noqa: F401
-    from rayoptics_amd import abi, analyses, workloads
+    from rayoptics_amd import analyses, workloads
     from rayoptics_amd.engine import make_grid
     import footprint_ref as FR
     results = []
@@ -60,15 +60,12 @@ def main():
         tbl = model.workload.table
         wvls = list(tbl.wvls)
         F, W = len(model.fields), len(wvls)
-        items = [(model.fields[(i // W) % F], wvls[i % W]) for i in range(N_ITEMS)]
+        assert F * W == N_ITEMS
         for n in args.rays:
             R = n * n
-            fs, wis, opts = [], [], []
-            for fld, wvl in items:
-                eng, f, wi, o = analyses._launch_setup(model, fld, wvl, dict(apply_vignetting=True), abi.OUT_FULL)
-                fs.append(f), wis.append(wi), opts.append(o)
-            flags = int(opts[0].flags)
-            res = eng.trace_pupil_grids(fs, wis, make_grid((-1., -1.), (1., 1.), n), opts, want_pupil=False)
+            eng, _f, _w, _sw, fs, wis, opts, flags = analyses._packet_items(model, model.fields, wvls, n, False,
+                                                                            'beam_footprints_bench')
+            res = analyses._trace_packets(eng, fs, wis, opts, n)
             rec, _m = eng.surface_footprints(res, flags)
             n_seg = rec.shape[1]
             hw = np.sqrt(np.maximum(rec['r2_max'].max(axis=0), 1e-12)) * analyses.FOOTPRINT_MAP_MARGIN

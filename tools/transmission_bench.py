@@ -53,7 +53,7 @@ def main():
     args = ap.parse_args()
     import torch
     import rayoptics_amd  # noqa: F401
-    from rayoptics_amd import abi, analyses, workloads
+    from rayoptics_amd import analyses, workloads
     from rayoptics_amd.engine import make_grid
     import fresnel_ref as FR
     results = []
@@ -62,16 +62,12 @@ def main():
         tbl = model.workload.table
         wvls = list(tbl.wvls)
         F, W = len(model.fields), len(wvls)
-        items = [(model.fields[(i // W) % F], wvls[i % W]) for i in range(N_ITEMS)]
+        assert F * W == N_ITEMS
         for n in args.rays:
             R = n * n
-            fs, wis, opts = [], [], []
-            for fld, wvl in items:
-                kw = dict(check_apertures=True, apply_vignetting=True)
-                eng, f, wi, o = analyses._launch_setup(model, fld, wvl, kw, abi.OUT_FULL)
-                fs.append(f), wis.append(wi), opts.append(o)
-            flags = int(opts[0].flags)
-            res = eng.trace_pupil_grids(fs, wis, make_grid((-1., -1.), (1., 1.), n), opts, want_pupil=False)
+            eng, _f, _w, _sw, fs, wis, opts, flags = analyses._packet_items(model, model.fields, wvls, n, True,
+                                                                            'transmission_bench')
+            res = analyses._trace_packets(eng, fs, wis, opts, n)
             _r, surf, item = eng.surface_transmission(res, flags, wis, want_rows=False)
             n_seg = surf.shape[1]
             n_ok = int(item['n_ok'].sum())
