@@ -924,10 +924,13 @@ int rox_surface_footprints(rox_system *sys, uint32_t trace_flags, uint32_t fp_fl
  * 2^28) plus, for rows bound for host memory, 8 MiB of rows.  Larger jobs run as consecutive
  * launches over fewer items (and, for rows bound for host memory, fewer rays) with the same
  * results.  Asynchronous on `stream` unless an output is host memory.
- * Not modelled: absorption, multilayer coatings, complex (metal) indices, diffraction
- * efficiency.                                                                               */
+ * Not modelled here: absorption, multilayer coatings, complex (metal) indices (these are
+ * rox_surface_thinfilm's, below), diffraction efficiency.                                     */
 #define ROX_TX_FIELDS 1u
 enum { ROX_COAT_BARE = 0, ROX_COAT_IDEAL = 1, ROX_COAT_FIXED = 2 };
+enum { ROX_COAT_STACK = 3 };       /* rox_surface_thinfilm only */
+#define ROX_MAX_COAT_LAYERS 64          /* layers of one interface's stack */
+#define ROX_MAX_COAT_LAYERS_TOTAL 4096  /* layers of one call */
 typedef struct rox_tx_surface {
     int64_t n;               /* rays counted (status ROX_OK)                                 */
     double ts_sum, tp_sum;   /* sums of Ts and of Tp at this slot (object and image: 1)      */
@@ -947,6 +950,76 @@ int rox_surface_transmission(rox_system *sys, uint32_t trace_flags, uint32_t tx_
                              const int32_t *wvl_idx, int32_t n_coat, const int32_t *coat_kind,
                              const double *coat_value, double *rows, int64_t ld_rows,
                              rox_tx_surface *surf, rox_tx_item *item, void *stream);
+
+/* rox_surface_transmission with thin-film stacks and metal mirrors: the same walk over the same
+ * packets with COMPLEX field vectors (a stack's ts and tp differ in phase), and at an interface
+ * whose coat_kind is ROX_COAT_STACK the characteristic matrix of its layers evaluated per ray.
+ * Everything rox_surface_transmission says about trace_flags, outs, n_rays, wvl_idx, n_coat,
+ * coat_kind, coat_value, rows, surf, item, the records, the scratch, the chunking, the
+ * destinations and the errors holds here, with these differences:
+ *   coat_kind  may also be ROX_COAT_STACK, on an interface between object and image that is
+ *          ROX_TRANSMIT (no thin lens, no phase element) or ROX_REFLECT; anywhere else
+ *          ROX_E_ARG names the interface.  Both media of a transmitting interface are real
+ *          (n_table).
+ *   wvl    HOST [n_items]: each item's vacuum wavelength in the unit of layer_thickness, finite
+ *          and > 0.
+ *   stack_first  HOST int32 [n_coat + 1]: CSR offsets into the layer arrays (stack_first[0] = 0);
+ *          only an interface of kind ROX_COAT_STACK has layers, at most ROX_MAX_COAT_LAYERS, and
+ *          a call at most ROX_MAX_COAT_LAYERS_TOTAL.  Layers are listed in the order the light
+ *          crosses them, from medium s-1 to medium s.  A stack may have 0 layers.
+ *   layer_thickness  HOST [n_layers], finite and >= 0.
+ *   layer_index  HOST [n_wvls][n_layers][2]: (re, im) of each layer's index per row of n_table,
+ *          re > 0, im >= 0: N = n + ik with exp(-iwt), k > 0 absorbs.
+ *   sub_index  HOST [n_wvls][n_coat][2]: the complex index of the metal or substrate behind a
+ *          ROX_REFLECT interface with a stack (re, im >= 0, not both 0); read only there, and
+ *          required if there is one.
+ *          wvl, layer_thickness and layer_index may be NULL when there is no layer, stack_first
+ *          when no interface has a stack.
+ *   tx_flags   ROX_TX_FIELDS: rows has 16 rows per item: rows 4-9 re(E1), re(E2), rows 10-15
+ *          im(E1), im(E2).
+ * Arithmetic (IEEE double, no FMA; sqrt, division, sincos and exp of the device's library, so a
+ * restatement agrees within a bound, not bit for bit).  Complex products are
+ * (a.r*b.r - a.i*b.i, a.r*b.i + a.i*b.r); 1/a = (a.r/m, -a.i/m), m = a.r*a.r + a.i*a.i.
+ *   Frames, slot 0 and the last slot as above; E1 and E2 start real.  Frames act on the real
+ *          and on the imaginary part.
+ *   Interfaces of the kinds ROX_COAT_BARE, _IDEAL and _FIXED: exactly the formulas above with the
+ *          real ts, tp applied to the real and to the imaginary part of E separately.  A call
+ *          without a stack gives rows 0-9 bit-identical to rox_surface_transmission's and rows
+ *          10-15 zero.
+ *   ROX_COAT_STACK at interface s: A = n1*ci, a2 = (n1*n1)*(1 - ci*ci), B' = n2*ct.  For a medium
+ *          of squared index N2 = N*N: g = sqrt(N2 - a2) on the branch Im g >= 0 (Re g >= 0 when
+ *          Im g = 0), from z = N2 - a2, m = sqrt(z.r*z.r + z.i*z.i): z.r >= 0: g.r =
+ *          sqrt((m + z.r)/2), g.i = z.i/(g.r + g.r) (0 when g.r = 0); else g.i = sqrt((m - z.r)/2),
+ *          g.r = z.i/(g.i + g.i).  Admittances: y = g (s), y = N2*(1/g) (p).  z == 0 exactly (the
+ *          ray runs along the layer: g = 0, 1/g is not finite) is not defined: that ray's rows
+ *          and its share of the sums are NaN although it counts as OK.
+ *          Exit side: transmitting ys = B', yp = (n2*n2)/B'; mirror: g from sub_index.
+ *          (B, C) = (1, y_exit) for s and for p; att = 0.  Layers from the last to the first, with
+ *          kd = (6.283185307179586*d)/wvl, x = kd*g.r, y = kd*g.i, e2 = exp(-(y + y)),
+ *          ch = (1 + e2)/2, sh = (1 - e2)/2, cs = (cos(x)*ch, -(sin(x)*sh)), sn = (sin(x)*ch,
+ *          cos(x)*sh) -- cos and sin of delta = x + iy over e^y, so nothing overflows -- and
+ *          att = att + y:   u = sn*(C*(1/y_j)), v = (y_j*sn)*B,
+ *          (B, C) <- (cs*B + (u.i, -u.r), cs*C + (v.i, -v.r)), 1/y_j = 1/g (s), g*(1/N2) (p).
+ *          y0 = A (s), (n1*n1)/A (p); den = y0*B + C.
+ *          Transmitting: f = exp(-att); ts = (f*(y0s + y0s))*(1/den_s),
+ *          tp = ((f*(y0p + y0p))*(ci/ct))*(1/den_p), qs = B'/A; ci == 0: ts = tp = qs = 0.
+ *          Without layers this is the bare formula.
+ *          Mirror: ts = (y0s*B - C)*(1/den_s), tp = -((y0p*B - C)*(1/den_p)), qs = 1 (ci == 0:
+ *          ts = tp = -1): a perfect conductor gives the ideal mirror's (-1, +1).
+ *          Ts = qs*|ts|^2, Tp = qs*|tp|^2 (reflectances on a mirror), |t|^2 = t.r*t.r + t.i*t.i.
+ *          For E in (E1, E2): a = ts*(s^ . E), b = tp*(p_in . E) (dot products of the real and of
+ *          the imaginary part), E <- a*s^ + b*p_out per part; q <- q*qs.
+ *   Rows:  g11 = E1r.E1r + E1i.E1i, g22 likewise, g12 = (E1r.E2r + E1i.E2i, E1r.E2i - E1i.E2r)
+ *          (Hermitian products), m, h as above, r = sqrt(h*h + (g12.r*g12.r + g12.i*g12.i)).
+ * The records' sums are merged over the same waves of 128 rays in the same order as
+ * rox_surface_transmission's: without a stack they are its records bit for bit.              */
+int rox_surface_thinfilm(rox_system *sys, uint32_t trace_flags, uint32_t tx_flags,
+                         int32_t n_items, const rox_out *outs, int64_t n_rays,
+                         const int32_t *wvl_idx, const double *wvl, int32_t n_coat,
+                         const int32_t *coat_kind, const double *coat_value,
+                         const int32_t *stack_first, const double *layer_thickness,
+                         const double *layer_index, const double *sub_index, double *rows,
+                         int64_t ld_rows, rox_tx_surface *surf, rox_tx_item *item, void *stream);
 
 /* chief-ray aiming ------------------------------------------------------- */
 /* One problem per (field, wavelength): trace.iterate_ray

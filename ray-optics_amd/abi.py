@@ -226,6 +226,8 @@ class TxItem(C.Structure):
 
 TX_FIELDS = 1               # include/roxtrace.h rox_surface_transmission
 COAT_BARE, COAT_IDEAL, COAT_FIXED = 0, 1, 2
+COAT_STACK = 3              # rox_surface_thinfilm only
+MAX_COAT_LAYERS, MAX_COAT_LAYERS_TOTAL = 64, 4096
 
 
 class Vig(C.Structure):
@@ -269,7 +271,8 @@ EXPORTS = ('rox_abi_version', 'rox_device_count', 'rox_set_device',
            'rox_pin_host_memory', 'rox_unpin_host_memory', 'rox_copy_async', 'rox_synchronize',
            'rox_spot_stats', 'rox_trace_through_focus', 'rox_trace_through_focus_grids',
            'rox_focus_psf', 'rox_focus_mtf', 'rox_focus_ee', 'rox_focus_gmtf', 'rox_focus_psf_ee',
-           'rox_focus_zernike', 'rox_surface_footprints', 'rox_surface_transmission')
+           'rox_focus_zernike', 'rox_surface_footprints', 'rox_surface_transmission',
+           'rox_surface_thinfilm')
 # ... and the measurement / self-test helpers of include/roxtrace_diag.h
 DIAG_EXPORTS = ('rox_time_pupil_grid', 'rox_selftest_fp64', 'rox_diag_pack_launches')
 
@@ -349,6 +352,9 @@ def declare(lib):
     lib.rox_surface_transmission.restype = C.c_int
     lib.rox_surface_transmission.argtypes = [vp, C.c_uint32, C.c_uint32, i32, P(Out), i64, vp, i32, vp, vp, vp, i64,
                                              vp, vp, vp]
+    lib.rox_surface_thinfilm.restype = C.c_int
+    lib.rox_surface_thinfilm.argtypes = [vp, C.c_uint32, C.c_uint32, i32, P(Out), i64, vp, vp, i32, vp, vp, vp, vp, vp,
+                                         vp, vp, i64, vp, vp, vp]
     lib.rox_time_pupil_grid.restype = C.c_int
     lib.rox_time_pupil_grid.argtypes = [vp, P(Field), P(Grid), i32, P(Opts),
                                         P(Out), vp, i32, P(dbl)]

@@ -24,6 +24,7 @@
 import numpy as np
 
 from . import abi, session
+from .coatings import Coating, stack_tables
 from .engine import make_grid
 from .raypkg import HostPackets
 from .trace import opts_from_kwargs, emit, _trace_pupil, _launch_setup
@@ -1175,7 +1176,8 @@ class Transmission:
     ``T_map``, ``D_map``  [F, W, num_rays, num_rays] views of the rows, NaN where a ray failed
                       (x the first axis), or None
     ``E1``, ``E2``    [F, W, 3, num_rays, num_rays] the exit field vectors of the x-like and the
-                      y-like input state in the image frame, or None
+                      y-like input state in the image frame (complex where a Coating was
+                      evaluated: a stack's ts and tp differ in phase), or None
     ``results``       the device packets, with ``keep_packets``"""
 
     def __init__(self, items, surfaces, slot_ifc, spectral_wts, ref_field=0, rows=None, num_rays=None, results=None,
@@ -1216,16 +1218,30 @@ class Transmission:
             self.T_map, self.D_map = grid[:, :, 0], grid[:, :, 3]
             if rows.shape[1] == 10:
                 self.E1, self.E2 = grid[:, :, 4:7], grid[:, :, 7:10]
+            elif rows.shape[1] == 16:           # thin films: complex amplitudes
+                self.E1 = grid[:, :, 4:7] + 1j * grid[:, :, 10:13]
+                self.E2 = grid[:, :, 7:10] + 1j * grid[:, :, 13:16]
 
 
 def _coating_tables(table, coatings):
-    """``coatings`` of :func:`transmission` -> (coat_kind [n_ifcs], coat_value [n_ifcs, 2]) or
-    (None, None)"""
+    """``coatings`` of :func:`transmission` -> (coat_kind [n_ifcs], coat_value [n_ifcs, 2],
+    {interface: Coating in the order the light crosses its layers}) or (None, None, {})"""
     if coatings is None:
-        return None, None
+        return None, None, {}
     N = table.n_ifcs
     kind = np.zeros(N, np.int32)
     value = np.ones((N, 2), np.float64)
+    stacks = {}
+    nt = np.asarray(table.n_table)
+
+    def air(i):
+        return bool((nt[:, i] == 1.0).all())
+
+    def stack(i, c):
+        """a Coating is written outside-first: as written where the light comes from the air (or
+        onto a mirror), flipped where the glass is the preceding medium"""
+        flip = 0 < i < N - 1 and table.rows[i].mode != abi.REFLECT and air(i) and not air(i - 1)
+        kind[i], stacks[i] = abi.COAT_STACK, c.reversed() if flip else c
 
     def fixed(v):
         try:
@@ -1247,16 +1263,19 @@ def _coating_tables(table, coatings):
                 raise ValueError(f'transmission: coatings: key {i!r} is not an interface index in [1, {N - 2}]')
             if isinstance(c, str) and c in ('bare', 'ideal'):
                 kind[i] = abi.COAT_IDEAL if c == 'ideal' else abi.COAT_BARE
+            elif isinstance(c, Coating):
+                stack(i, c)
             else:
                 kind[i], value[i] = abi.COAT_FIXED, fixed(c)
     else:
-        v = fixed(coatings)
-        nt = np.asarray(table.n_table)
+        v = None if isinstance(coatings, Coating) else fixed(coatings)
         for i in range(1, N - 1):
-            air = (nt[:, i - 1] == 1.0).all(), (nt[:, i] == 1.0).all()
-            if table.rows[i].mode == abi.TRANSMIT and air[0] != air[1]:     # glass on exactly one side
-                kind[i], value[i] = abi.COAT_FIXED, v
-    return kind, value
+            if table.rows[i].mode == abi.TRANSMIT and air(i - 1) != air(i):     # glass on exactly one side
+                if v is None:
+                    stack(i, coatings)
+                else:
+                    kind[i], value[i] = abi.COAT_FIXED, v
+    return kind, value, stacks
 
 
 def transmission(opt_model, flds=None, wvls=None, num_rays=64, coatings=None, check_apertures=True, pupil_maps=True,
@@ -1269,16 +1288,22 @@ def transmission(opt_model, flds=None, wvls=None, num_rays=64, coatings=None, ch
     its ``results``) over the same fields, wavelengths and ``num_rays`` -- no ray is traced again,
     one trace serves both analyses.  ``coatings``: None (bare surfaces), 'ideal' (every interface
     lossless), a power transmission or a pair (Ts, Tp) for every glass-air surface, or a dict
-    {interface index: 'bare' | 'ideal' | value | (Ts, Tp)}.  ``pupil_maps`` keeps the per-ray rows
-    (T_map, D_map), ``fields`` adds the exit field vectors.  Spectral weights as the through-focus
-    maps take them (osp['wvls'], or 1 per wavelength when ``wvls`` is given).
+    {interface index: 'bare' | 'ideal' | value | (Ts, Tp)}.  A :class:`coatings.Coating` -- a
+    thin-film stack, absorbing layers and a metal substrate included -- is accepted wherever a
+    value is: given bare it goes on every glass-air surface, flipped where the glass is the
+    preceding medium; as a dict value it is applied as written, outside-first on the air side
+    (on a mirror its ``substrate`` is the metal).  With a Coating present the one call is
+    rox_surface_thinfilm (the other interfaces' kinds alongside) and ``E1``, ``E2`` are complex.
+    ``pupil_maps`` keeps the per-ray rows (T_map, D_map), ``fields`` adds the exit field vectors.
+    Spectral weights as the through-focus maps take them (osp['wvls'], or 1 per wavelength when
+    ``wvls`` is given).
 
     ``relative`` of the result is relative transmission including vignetting -- poly_throughput
     times the share of the unit pupil box the field's vignetting factors leave its grid, over that
     of field ``ref_field``.  It is NOT radiometric relative illumination: no projected
     pupil area, cos^4 or distortion term is applied; that is out of scope here.  Neither are
-    absorbing or multilayer coatings, the complex indices of metal mirrors and diffraction
-    efficiencies: mirrors, thin lenses and phase elements are counted as ideal.
+    absorbing glasses (bulk absorption) and diffraction efficiencies: thin lenses and phase
+    elements are counted as ideal, and so is a mirror without a Coating.
     Returns :class:`Transmission`."""
     num_rays = int(num_rays)
     eng, flds, wvls, spectral_wts, fs, wis, opts_list, flags = _packet_items(opt_model, flds, wvls, num_rays,
@@ -1287,7 +1312,8 @@ def transmission(opt_model, flds=None, wvls=None, num_rays=64, coatings=None, ch
     if not 0 <= int(ref_field) < F:
         raise ValueError(f'transmission: ref_field {ref_field} outside [0, {F})')
     box = [(2.0 - f.vlx - f.vux) * (2.0 - f.vly - f.vuy) / 4.0 for f in fs[W - 1::W]]     # one per field
-    kind, value = _coating_tables(eng.table, coatings)
+    kind, value, stacks = _coating_tables(eng.table, coatings)
+    film = stack_tables(eng.table, stacks, 'transmission') if stacks else None
     if packets is not None:
         flags = int(getattr(packets, 'trace_flags', flags))
         results = list(getattr(packets, 'results', packets) or [])
@@ -1296,7 +1322,14 @@ def transmission(opt_model, flds=None, wvls=None, num_rays=64, coatings=None, ch
                              f'with keep_packets=True?)')
     else:
         results = _trace_packets(eng, fs, wis, opts_list, num_rays)
-    rows, surf, item = eng.surface_transmission(results, flags, wis, coat_kind=kind, coat_value=value,
+    if film is None:
+        rows, surf, item = eng.surface_transmission(results, flags, wis, coat_kind=kind, coat_value=value,
+                                                    want_rows=bool(pupil_maps or fields), fields=bool(fields))
+    else:
+        first, thick, index, sub = film
+        rows, surf, item = eng.surface_thinfilm(results, flags, wis, [float(eng.table.wvls[w]) for w in wis],
+                                                coat_kind=kind, coat_value=value, stack_first=first,
+                                                layer_thickness=thick, layer_index=index, sub_index=sub,
                                                 want_rows=bool(pupil_maps or fields), fields=bool(fields))
     n_seg = surf.shape[1]
     return Transmission(item.reshape(F, W), surf.reshape(F, W, n_seg), eng.slot_interfaces(flags), spectral_wts,

@@ -13,8 +13,15 @@
 // the status byte and the twelve packet reads of a slot).  Each wave writes one partial record per slot and one for the item; the
 // finishing kernel merges them in a fixed order.  No floating-point atomics.  (Shared with
 // footprint.hip: rox_packets.hpp.)
+//
+// rox_surface_thinfilm is the same walk with complex field vectors and, where an interface has a
+// stack of thin films or a metal behind it, the characteristic matrix of the stack evaluated per
+// ray (thinfilm_kernel: kFilmRays per thread, the layer loop wave-uniform in trip count, a stack's
+// layer tables for the item's wavelength scalar loads as well).  Both entries share the argument
+// checks, the staging, the launch loop and the finishing kernel (tx_entry).
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdint>
 
 #include "rox_device.hpp"
@@ -46,6 +53,8 @@ enum Model : int32_t {
     kMirror = 2,                                // ts = -1
     kFixed = 3,                                 // given power coefficients
     kFixedMirror = 4,
+    kStack = 5,                                 // thin films between two real media (thinfilm_kernel only)
+    kStackMirror = 6,                           // thin films, or none, over a metal
 };
 
 struct ItemIn {
@@ -80,6 +89,22 @@ struct TxArgs {
     int64_t ld_rows, row_ray0;
     Part *part;                                 // [items][n_waves][n_seg + 1] or nullptr
 };
+
+// what thinfilm_kernel reads besides: a layer's row of `layer` is (re N^2, im N^2, re 1/N^2, im 1/N^2)
+struct FilmArgs {
+    TxArgs t;                                   // n_rows is 4 or 16
+    const double *wvl;                          // [chunk's items] vacuum wavelength, the thicknesses' unit
+    const int32_t *stack_first;                 // [n_ifcs + 1] CSR offsets into the layers
+    const double *thick;                        // [n_layers]
+    const double *layer;                        // [n_wvls][n_layers][4]
+    const double *sub;                          // [n_wvls][n_ifcs][2] N^2 behind a kStackMirror
+    int32_t n_layers;
+};
+
+constexpr int kFilmRays = kRays;                // rays per thread of thinfilm_kernel, as fresnel_kernel: the same
+                                                // rays per wave, so the same partial sums in the same order
+constexpr int kFilmTile = kBlock * kFilmRays;
+static_assert(kFilmTile == kTile, "both kernels walk the same tiles: tx_entry sizes the launches with kTile");
 
 struct V3 {
     double x, y, z;
@@ -320,6 +345,321 @@ __global__ __launch_bounds__(kBlock) void fresnel_kernel(const TxArgs a)
     }
 }
 
+// ---- thin films: complex amplitudes (include/roxtrace.h rox_surface_thinfilm states the order)
+struct Cx {
+    double r, i;
+};
+
+__device__ __forceinline__ Cx cmul(const Cx &a, const Cx &b)
+{
+    return Cx{a.r * b.r - a.i * b.i, a.r * b.i + a.i * b.r};
+}
+__device__ __forceinline__ Cx cinv(const Cx &a)
+{
+    const double m = a.r * a.r + a.i * a.i;
+    return Cx{a.r / m, -a.i / m};
+}
+// sqrt(zr + i zi), zi >= 0, on the branch Im >= 0 (Re >= 0 when Im == 0)
+__device__ __forceinline__ Cx csqrt_up(double zr, double zi)
+{
+    const double m = sqrt(zr * zr + zi * zi);
+    if (zr >= 0.0) {
+        const double gr = sqrt((m + zr) / 2.0);
+        return Cx{gr, gr == 0.0 ? 0.0 : zi / (gr + gr)};
+    }
+    const double gi = sqrt((m - zr) / 2.0);
+    return Cx{zi / (gi + gi), gi};
+}
+// a layer of admittance y (iy = 1/y): (B, C) <- (cs*B - i*sn*C/y, -i*y*sn*B + cs*C)
+__device__ __forceinline__ void film_layer(Cx &B, Cx &C, const Cx &cs, const Cx &sn, const Cx &y, const Cx &iy)
+{
+    const Cx u = cmul(sn, cmul(C, iy)), v = cmul(cmul(y, sn), B);
+    const Cx cb = cmul(cs, B), cc = cmul(cs, C);
+    B = Cx{cb.r + u.i, cb.i - u.r};
+    C = Cx{cc.r + v.i, cc.i - v.r};
+}
+
+struct C3 {
+    V3 re, im;
+};
+
+// the state of a ray along the walk
+struct FilmRay {
+    int64_t r;
+    bool ok;
+    V3 b4;
+    C3 E1, E2;
+    double q;
+};
+
+// E <- (ts*(s . E))*s + (tp*(p_in . E))*p_out with complex ts, tp and E
+__device__ __forceinline__ C3 through_cx(const C3 &E, const V3 &s, const V3 &pi, const V3 &po, const Cx &ts,
+                                         const Cx &tp)
+{
+    const Cx a = cmul(ts, Cx{dot(s, E.re), dot(s, E.im)}), b = cmul(tp, Cx{dot(pi, E.re), dot(pi, E.im)});
+    return C3{V3{a.r * s.x + b.r * po.x, a.r * s.y + b.r * po.y, a.r * s.z + b.r * po.z},
+              V3{a.i * s.x + b.i * po.x, a.i * s.y + b.i * po.y, a.i * s.z + b.i * po.z}};
+}
+
+// fresnel_kernel's walk with complex E1, E2, over the same tile with the same rays per thread and
+// wave: the partial sums of the records are formed in the same order.  An interface of the models
+// kIdeal .. kFixedMirror applies fresnel_kernel's real formulas to the real and to the imaginary
+// part of the fields; kStack / kStackMirror evaluate the stack per ray.  The layer loop's trip
+// count, a layer's N^2 and thickness and the wavelength are wave-uniform (scalar loads); s and p
+// share g, delta, its cosine and its sine.  214 VGPRs, no scratch, 2 waves per SIMD.
+__global__ __launch_bounds__(kBlock) void thinfilm_kernel(const FilmArgs fa)
+{
+    const TxArgs &a = fa.t;
+    const ItemIn it = a.items[blockIdx.y];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int n_seg = a.n_seg;
+    const ctbli slot_ifc = (ctbli)a.slot_ifc, model_of = (ctbli)a.model, first = (ctbli)fa.stack_first;
+    const ctblp rt_of = (ctblp)a.rt, coat = (ctblp)a.coat, thick = (ctblp)fa.thick;
+    const ctblp ntab = (ctblp)a.n_table + (size_t)it.wvl * a.n_ifcs;
+    const ctblp layer = (ctblp)fa.layer + (size_t)it.wvl * fa.n_layers * 4;
+    const ctblp sub = (ctblp)fa.sub + (size_t)it.wvl * a.n_ifcs * 2;
+    const double wvl = fa.wvl ? ((ctblp)fa.wvl)[blockIdx.y] : 1.0;
+    const double nan = __builtin_nan("");
+
+    const V3 zero{0.0, 0.0, 0.0};
+    FilmRay ray[kFilmRays];
+#pragma unroll
+    for (int j = 0; j < kFilmRays; ++j) {
+        FilmRay &y = ray[j];
+        y.r = a.ray0 + (int64_t)blockIdx.x * kFilmTile + j * kBlock + threadIdx.x;
+        y.ok = y.r < a.n_rays && it.status[y.r] == ROX_OK;
+        y.b4 = zero;
+        y.E1 = y.E2 = C3{zero, zero};
+        y.q = 1.0;
+    }
+    const size_t wave_of_item = (size_t)(a.ray0 / kFilmTile + blockIdx.x) * kWaves + wave;
+    Part *out = a.part ? a.part + ((size_t)blockIdx.y * a.n_waves + wave_of_item) * (n_seg + 1) : nullptr;
+
+    for (int k = 0; k < n_seg; ++k) {
+        const double *rec = it.seg + (size_t)k * ROX_SEG_DOUBLES * it.ld;
+        V3 dj[kFilmRays], Nj[kFilmRays];
+#pragma unroll
+        for (int j = 0; j < kFilmRays; ++j) {
+            const int64_t r = ray[j].r;
+            dj[j] = Nj[j] = zero;
+            if (ray[j].ok) {
+                dj[j] = V3{rec[3 * it.ld + r], rec[4 * it.ld + r], rec[5 * it.ld + r]};
+                Nj[j] = V3{rec[7 * it.ld + r], rec[8 * it.ld + r], rec[9 * it.ld + r]};
+            }
+        }
+
+        const int s = slot_ifc[k];
+        if (k >= 1)
+            for (int i = slot_ifc[k - 1]; i < s; ++i) {
+                const ctblp rt = rt_of + (size_t)i * kRtDoubles;
+                const bool c_order = rt[9] != 0.0;
+#pragma unroll
+                for (int j = 0; j < kFilmRays; ++j) {
+                    FilmRay &y = ray[j];
+                    y.b4 = carry(rt, c_order, y.b4);
+                    y.E1 = C3{carry(rt, c_order, y.E1.re), carry(rt, c_order, y.E1.im)};
+                    y.E2 = C3{carry(rt, c_order, y.E2.re), carry(rt, c_order, y.E2.im)};
+                }
+            }
+
+        const bool inner = k > 0 && k < n_seg - 1;
+        int model = kIdeal, l0 = 0, l1 = 0;
+        double n1 = 1.0, n2 = 1.0, cTs = 1.0, cTp = 1.0, cts = 1.0, ctp = 1.0;
+        Cx sub2{1.0, 0.0};
+        if (inner) {
+            model = model_of[s];
+            n1 = ntab[s - 1];
+            n2 = ntab[s];
+            if (model == kBare && n1 == n2)
+                model = kIdeal;
+            if (model == kFixed || model == kFixedMirror) {
+                cTs = coat[2 * s];
+                cTp = coat[2 * s + 1];
+                cts = sqrt(cTs);
+                ctp = sqrt(cTp);
+            }
+            if (model == kMirror || model == kFixedMirror)
+                cts = -cts;
+            if (model == kStack || model == kStackMirror) {
+                l0 = first[s];
+                l1 = first[s + 1];
+            }
+            if (model == kStackMirror)
+                sub2 = Cx{sub[2 * s], sub[2 * s + 1]};
+        }
+        const bool stack = model == kStack || model == kStackMirror;
+
+        Part t = part_empty();
+#pragma unroll
+        for (int j = 0; j < kFilmRays; ++j) {
+            const V3 d = dj[j], N = Nj[j];
+            const bool ok = ray[j].ok;
+            V3 &b4 = ray[j].b4;
+            C3 &E1 = ray[j].E1, &E2 = ray[j].E2;
+            double &q = ray[j].q;
+            if (k == 0) {
+                V3 e = V3{d.z, 0.0, -d.x};
+                double ee = dot(e, e);
+                if (ee == 0.0) {
+                    e = V3{1.0, 0.0, 0.0};
+                    ee = dot(e, e);
+                }
+                E1 = C3{over(e, sqrt(ee)), zero};
+                E2 = C3{cross(d, E1.re), zero};
+                b4 = d;
+            }
+            const double ci = fabs(dot(b4, N));
+            double Ts = 1.0, Tp = 1.0;
+            if (inner) {
+                Cx ts{cts, 0.0}, tp{ctp, 0.0};
+                double qs = 1.0;
+                Ts = cTs;
+                Tp = cTp;
+                if (model == kBare) {
+                    const double ct = fabs(dot(d, N));
+                    const double A = n1 * ci, B = n2 * ct;
+                    ts.r = (A + A) / (A + B);
+                    tp.r = (A + A) / (n2 * ci + n1 * ct);
+                    qs = B / A;
+                    if (ci == 0.0)
+                        ts.r = tp.r = qs = 0.0;
+                    Ts = qs * (ts.r * ts.r);
+                    Tp = qs * (tp.r * tp.r);
+                } else if (stack) {
+                    const double ct = fabs(dot(d, N));
+                    const double A = n1 * ci, a2 = (n1 * n1) * (1.0 - ci * ci);
+                    const double Bx = n2 * ct;
+                    // (B, C) at the exit side: (1, y_exit) for s and for p
+                    Cx ys{Bx, 0.0}, yp{(n2 * n2) / Bx, 0.0};
+                    if (model == kStackMirror) {
+                        ys = csqrt_up(sub2.r - a2, sub2.i);
+                        yp = cmul(sub2, cinv(ys));
+                    }
+                    Cx Bs{1.0, 0.0}, Cs = ys, Bp{1.0, 0.0}, Cp = yp;
+                    double att = 0.0;
+                    for (int l = l1 - 1; l >= l0; --l) {
+                        const Cx N2{layer[4 * l], layer[4 * l + 1]}, iN2{layer[4 * l + 2], layer[4 * l + 3]};
+                        const double kd = (6.283185307179586 * thick[l]) / wvl;
+                        const Cx g = csqrt_up(N2.r - a2, N2.i), ig = cinv(g);
+                        const double x = kd * g.r, y = kd * g.i;
+                        double sx, cx;
+                        sincos(x, &sx, &cx);
+                        // cos and sin of x + iy over e^y: only e^(-2y) <= 1 is formed
+                        const double e2 = exp(-(y + y));
+                        const double ch = (1.0 + e2) / 2.0, sh = (1.0 - e2) / 2.0;
+                        const Cx cs{cx * ch, -(sx * sh)}, sn{sx * ch, cx * sh};
+                        att = att + y;
+                        film_layer(Bs, Cs, cs, sn, g, ig);
+                        film_layer(Bp, Cp, cs, sn, cmul(N2, ig), cmul(g, iN2));
+                    }
+                    const double y0s = A, y0p = (n1 * n1) / A;
+                    const Cx ds{y0s * Bs.r + Cs.r, y0s * Bs.i + Cs.i}, dp{y0p * Bp.r + Cp.r, y0p * Bp.i + Cp.i};
+                    const Cx is = cinv(ds), ip = cinv(dp);
+                    if (model == kStack) {
+                        const double f = exp(-att);
+                        const double fs = f * (y0s + y0s), fp = (f * (y0p + y0p)) * (ci / ct);
+                        ts = Cx{fs * is.r, fs * is.i};
+                        tp = Cx{fp * ip.r, fp * ip.i};
+                        qs = Bx / A;
+                        if (ci == 0.0) {
+                            ts = tp = Cx{0.0, 0.0};
+                            qs = 0.0;
+                        }
+                    } else {
+                        ts = cmul(Cx{y0s * Bs.r - Cs.r, y0s * Bs.i - Cs.i}, is);
+                        const Cx rp = cmul(Cx{y0p * Bp.r - Cp.r, y0p * Bp.i - Cp.i}, ip);
+                        tp = Cx{-rp.r, -rp.i};
+                        if (ci == 0.0) {
+                            ts = Cx{-1.0, 0.0};
+                            tp = Cx{-1.0, 0.0};
+                        }
+                    }
+                    Ts = qs * (ts.r * ts.r + ts.i * ts.i);
+                    Tp = qs * (tp.r * tp.r + tp.i * tp.i);
+                }
+                V3 c = cross(b4, N);
+                double cc = dot(c, c);
+                if (cc == 0.0) {
+                    c = fabs(b4.x) <= fabs(b4.y) ? cross(b4, V3{1.0, 0.0, 0.0}) : cross(b4, V3{0.0, 1.0, 0.0});
+                    cc = dot(c, c);
+                }
+                const V3 sh = over(c, sqrt(cc));
+                const V3 pi = cross(b4, sh), po = cross(d, sh);
+                if (stack) {
+                    E1 = through_cx(E1, sh, pi, po, ts, tp);
+                    E2 = through_cx(E2, sh, pi, po, ts, tp);
+                } else {
+                    E1 = C3{through(E1.re, sh, pi, po, ts.r, tp.r), through(E1.im, sh, pi, po, ts.r, tp.r)};
+                    E2 = C3{through(E2.re, sh, pi, po, ts.r, tp.r), through(E2.im, sh, pi, po, ts.r, tp.r)};
+                }
+                q = q * qs;
+            }
+            if (ok) {
+                t.v[0] += 1.0;
+                t.v[1] += Ts;
+                t.v[2] += Tp;
+                t.v[3] += (Ts + Tp) / 2.0;
+                t.v[4] = fmin(t.v[4], Ts);
+                t.v[5] = fmin(t.v[5], Tp);
+                t.v[6] += ci;
+                t.v[7] = fmin(t.v[7], ci);
+            }
+            b4 = d;
+        }
+        if (out) {
+            t = wave_merge<false>(t);
+            if (lane == 0)
+                out[k] = t;
+        }
+    }
+
+    // the rows of each ray, and the item's partial record: Hermitian products
+    const double inf = __builtin_inf();
+    Part t{{0.0, 0.0, 0.0, 0.0, inf, -inf, 0.0, -inf}};
+#pragma unroll
+    for (int j = 0; j < kFilmRays; ++j) {
+        const C3 &E1 = ray[j].E1, &E2 = ray[j].E2;
+        const double q = ray[j].q;
+        const bool ok = ray[j].ok;
+        const int64_t r = ray[j].r;
+        const double g11 = dot(E1.re, E1.re) + dot(E1.im, E1.im), g22 = dot(E2.re, E2.re) + dot(E2.im, E2.im);
+        const double g12r = dot(E1.re, E2.re) + dot(E1.im, E2.im), g12i = dot(E1.re, E2.im) - dot(E1.im, E2.re);
+        const double m = (g11 + g22) / 2.0, h = (g11 - g22) / 2.0;
+        const double rr = sqrt(h * h + (g12r * g12r + g12i * g12i));
+        const double T = q * m, T1 = q * g11, T2 = q * g22;
+        const double D = m == 0.0 ? 0.0 : rr / m;
+        if (ok) {
+            t.v[0] += 1.0;
+            t.v[1] += T;
+            t.v[2] += T1;
+            t.v[3] += T2;
+            t.v[4] = fmin(t.v[4], T);
+            t.v[5] = fmax(t.v[5], T);
+            t.v[6] += D;
+            t.v[7] = fmax(t.v[7], D);
+        }
+        if (a.rows && r < a.n_rays) {
+            double *row = a.rows + (size_t)blockIdx.y * a.n_rows * a.ld_rows + (r - a.row_ray0);
+            row[0] = ok ? T : nan;
+            row[a.ld_rows] = ok ? T1 : nan;
+            row[2 * a.ld_rows] = ok ? T2 : nan;
+            row[3 * a.ld_rows] = ok ? D : nan;
+            if (a.n_rows == 16) {
+                const double f[12] = {E1.re.x, E1.re.y, E1.re.z, E2.re.x, E2.re.y, E2.re.z,
+                                      E1.im.x, E1.im.y, E1.im.z, E2.im.x, E2.im.y, E2.im.z};
+#pragma unroll
+                for (int c = 0; c < 12; ++c)
+                    row[(4 + c) * a.ld_rows] = ok ? f[c] : nan;
+            }
+        }
+    }
+    if (out) {
+        t = wave_merge<true>(t);
+        if (lane == 0)
+            out[n_seg] = t;
+    }
+}
+
 // block (k, item): slot k's record, or with k == n_seg the item's, its partial records merged in the
 // order of rox::block_merge
 __global__ __launch_bounds__(kBlock) void fresnel_finish(const Part *__restrict__ part, int n_waves, int n_seg,
@@ -360,15 +700,42 @@ __global__ __launch_bounds__(kBlock) void fresnel_finish(const Part *__restrict_
 
 rox::PerStream<rox::Workspace> g_tx_ws;
 
-}  // namespace
+// what rox_surface_thinfilm takes besides (HOST arrays)
+struct Film {
+    const double *wvl;                          // [n_items]
+    const int32_t *stack_first;                 // [n_coat + 1]
+    const double *thick;                        // [n_layers]
+    const double *index;                        // [n_wvls][n_layers][2]
+    const double *sub;                          // [n_wvls][n_coat][2]
+};
 
-extern "C" int rox_surface_transmission(rox_system *sys, uint32_t trace_flags, uint32_t tx_flags, int32_t n_items,
-                                        const rox_out *outs, int64_t n_rays, const int32_t *wvl_idx,
-                                        int32_t n_coat, const int32_t *coat_kind, const double *coat_value,
-                                        double *rows, int64_t ld_rows, rox_tx_surface *surf, rox_tx_item *item,
-                                        void *stream)
+inline bool index_ok(double re, double im, bool layer)
 {
-    static const char kE[] = "rox_surface_transmission";
+    return std::isfinite(re) && std::isfinite(im) && im >= 0.0 && (layer ? re > 0.0 : (re >= 0.0 && re + im > 0.0));
+}
+
+// the layer checks of wavelength row w
+int check_layer_index(const char *kE, const Film *film, int32_t n_layers, int32_t w)
+{
+    for (int32_t l = 0; l < n_layers; ++l) {
+        const double *v = film->index + 2 * ((size_t)w * n_layers + l);
+        if (!index_ok(v[0], v[1], true))
+            return rox::host_fail(ROX_E_ARG, "%s: layer_index[%d][%d] = (%g, %g): re must be > 0 and im >= 0", kE, w,
+                                  l, v[0], v[1]);
+    }
+    return 0;
+}
+
+// both entries: rox_surface_transmission (film == nullptr, fresnel_kernel) and rox_surface_thinfilm
+int tx_entry(const char *kE, const Film *film, rox_system *sys, uint32_t trace_flags, uint32_t tx_flags,
+             int32_t n_items, const rox_out *outs, int64_t n_rays, const int32_t *wvl_idx, int32_t n_coat,
+             const int32_t *coat_kind, const double *coat_value, double *rows, int64_t ld_rows, rox_tx_surface *surf,
+             rox_tx_item *item, void *stream)
+{
+    // HIP_TRY (rox_host.hpp) names `kHipWhere` for the prefix of its messages: this local, in place of
+    // the file's, gives it the prefix of the entry that called
+    const char *const kHipWhere = film ? "rox_surface_thinfilm: " : ::kHipWhere;
+    const int max_kind = film ? ROX_COAT_STACK : ROX_COAT_FIXED;
     // every argument check comes before anything touches a device; those that do not need the
     // system come before the system is read
     ROX_TRY(rox::check_packet_call(kE, sys, outs, n_items));
@@ -392,7 +759,7 @@ extern "C" int rox_surface_transmission(rox_system *sys, uint32_t trace_flags, u
         if (n_coat < 2)
             return rox::host_fail(ROX_E_ARG, "%s: n_coat %d is not the number of interfaces", kE, n_coat);
         for (int32_t s = 0; s < n_coat; ++s) {
-            if (coat_kind[s] < ROX_COAT_BARE || coat_kind[s] > ROX_COAT_FIXED)
+            if (coat_kind[s] < ROX_COAT_BARE || coat_kind[s] > max_kind)
                 return rox::host_fail(ROX_E_ARG, "%s: coat_kind[%d] = %d is not a ROX_COAT_* kind", kE, s,
                                       coat_kind[s]);
             for (int c = 0; c < 2 && coat_kind[s] == ROX_COAT_FIXED; ++c)
@@ -400,6 +767,41 @@ extern "C" int rox_surface_transmission(rox_system *sys, uint32_t trace_flags, u
                     return rox::host_fail(ROX_E_ARG, "%s: coat_value[%d][%d] = %g outside [0, 1]", kE, s, c,
                                           coat_value[2 * s + c]);
         }
+    }
+    // the stacks: what can be checked without the system (of layer_index the first wavelength's row)
+    int32_t n_layers = 0;
+    if (film) {
+        const int32_t *sf = film->stack_first;
+        if (sf && !coat_kind)
+            return rox::host_fail(ROX_E_ARG, "%s: stack_first without coat_kind", kE);
+        for (int32_t s = 0; coat_kind && s < n_coat; ++s) {
+            if (coat_kind[s] == ROX_COAT_STACK && !sf)
+                return rox::host_fail(ROX_E_ARG, "%s: coat_kind[%d] is ROX_COAT_STACK without stack_first", kE, s);
+            if (!sf)
+                continue;
+            const int64_t n = (int64_t)sf[s + 1] - sf[s];
+            if (sf[0] != 0 || n < 0 || n > ROX_MAX_COAT_LAYERS)
+                return rox::host_fail(ROX_E_ARG, "%s: stack_first[%d]: %lld layers outside [0, %d] (stack_first[0] %d)",
+                                      kE, s, (long long)n, ROX_MAX_COAT_LAYERS, sf[0]);
+            if (n > 0 && coat_kind[s] != ROX_COAT_STACK)
+                return rox::host_fail(ROX_E_ARG, "%s: stack_first[%d]: %lld layers where coat_kind[%d] = %d is not "
+                                      "ROX_COAT_STACK", kE, s, (long long)n, s, coat_kind[s]);
+            if (sf[s + 1] > ROX_MAX_COAT_LAYERS_TOTAL)
+                return rox::host_fail(ROX_E_ARG, "%s: stack_first[%d] = %d: more than %d layers in all", kE, s + 1,
+                                      sf[s + 1], ROX_MAX_COAT_LAYERS_TOTAL);
+        }
+        n_layers = sf ? sf[n_coat] : 0;
+        if (n_layers > 0 && (!film->thick || !film->index || !film->wvl))
+            return rox::host_fail(ROX_E_ARG, "%s: wvl, layer_thickness and layer_index go with the %d layers of "
+                                  "stack_first", kE, n_layers);
+        for (int32_t i = 0; film->wvl && i < n_items; ++i)
+            if (!(std::isfinite(film->wvl[i]) && film->wvl[i] > 0.0))
+                return rox::host_fail(ROX_E_ARG, "%s: item %d: wvl %g must be finite and > 0", kE, i, film->wvl[i]);
+        for (int32_t l = 0; l < n_layers; ++l)
+            if (!(std::isfinite(film->thick[l]) && film->thick[l] >= 0.0))
+                return rox::host_fail(ROX_E_ARG, "%s: layer_thickness[%d] = %g must be finite and >= 0", kE, l,
+                                      film->thick[l]);
+        ROX_TRY(check_layer_index(kE, film, n_layers, 0));
     }
     const rox::PacketSlots ps(sys, trace_flags);
     const int32_t n_ifcs = ps.n_ifcs, n_seg = ps.n_seg;
@@ -409,6 +811,30 @@ extern "C" int rox_surface_transmission(rox_system *sys, uint32_t trace_flags, u
                                   kE, i, wvl_idx[i], sys->n_wvls);
     if (coat_kind && n_coat != n_ifcs)
         return rox::host_fail(ROX_E_ARG, "%s: n_coat %d is not the number of interfaces %d", kE, n_coat, n_ifcs);
+    // the stacks: what needs the system
+    for (int32_t w = 1; film && w < sys->n_wvls; ++w)
+        ROX_TRY(check_layer_index(kE, film, n_layers, w));
+    for (int32_t s = 0; film && coat_kind && s < n_ifcs; ++s) {
+        if (coat_kind[s] != ROX_COAT_STACK)
+            continue;
+        const rox_surface &row = ps.rows[s];
+        const bool inner = s > 0 && s < n_ifcs - 1;
+        const bool glass = row.mode == ROX_TRANSMIT && row.profile != ROX_THINLENS && row.ph.kind == ROX_PH_NONE;
+        if (!inner || !(glass || row.mode == ROX_REFLECT))
+            return rox::host_fail(ROX_E_ARG, "%s: coat_kind[%d]: a stack belongs on a ROX_TRANSMIT interface that is "
+                                  "no thin lens or phase element, or on a ROX_REFLECT interface", kE, s);
+        if (row.mode != ROX_REFLECT)
+            continue;
+        if (!film->sub)
+            return rox::host_fail(ROX_E_ARG, "%s: coat_kind[%d]: a stack on a ROX_REFLECT interface needs sub_index",
+                                  kE, s);
+        for (int32_t w = 0; w < sys->n_wvls; ++w) {
+            const double *v = film->sub + 2 * ((size_t)w * n_ifcs + s);
+            if (!index_ok(v[0], v[1], false))
+                return rox::host_fail(ROX_E_ARG, "%s: sub_index[%d][%d] = (%g, %g): re and im must be >= 0 and not "
+                                      "both 0", kE, w, s, v[0], v[1]);
+        }
+    }
 
     hipStream_t st = (hipStream_t)stream;
     rox::PerStream<rox::Workspace>::Slot *slot;
@@ -419,7 +845,7 @@ extern "C" int rox_surface_transmission(rox_system *sys, uint32_t trace_flags, u
     const bool want_rec = surf || item;
     const bool rows_host = rows && !rox::is_device(rows);
     const bool host_dst = rows_host || (surf && !rox::is_device(surf)) || (item && !rox::is_device(item));
-    const int n_rows = (tx_flags & ROX_TX_FIELDS) ? 10 : 4;
+    const int n_rows = (tx_flags & ROX_TX_FIELDS) ? (film ? 16 : 10) : 4;
     const int64_t n_tiles = (n_rays + kTile - 1) / kTile;
     const int n_waves = (int)n_tiles * kWaves;
     // rows bound for host memory pass through the scratch, a range of rays at a time
@@ -434,10 +860,17 @@ extern "C" int rox_surface_transmission(rox_system *sys, uint32_t trace_flags, u
     const size_t b_item = want_rec ? 256 : 0;
     const int64_t chunk = rox::chunk_for(n_items, b_rows + b_part + b_surf + b_item + 256, kTxScratchBytes);
 
-    // the tables, staged as one block: [items][rt][coat][model][slot_ifc]
+    // the tables, staged as one block: [items][rt][coat][model][slot_ifc] and, for the stacks,
+    // [stack_first][pad to 8][wvl][thickness][layer N^2, 1/N^2][sub N^2]
     const size_t o_rt = sizeof(ItemIn) * (size_t)n_items, o_cv = o_rt + sizeof(double) * kRtDoubles * n_ifcs;
     const size_t o_md = o_cv + sizeof(double) * 2 * n_ifcs, o_si = o_md + sizeof(int32_t) * n_ifcs;
-    const size_t b_tab = o_si + sizeof(int32_t) * n_seg;
+    const size_t n_wl = film ? (size_t)sys->n_wvls : 0;
+    const bool stacks = film && film->stack_first, sub = stacks && film->sub;
+    const size_t o_sf = o_si + sizeof(int32_t) * n_seg;
+    const size_t o_wv = (o_sf + (stacks ? sizeof(int32_t) * (n_ifcs + 1) : 0) + 7) & ~size_t(7);
+    const size_t o_th = o_wv + (film && film->wvl ? sizeof(double) * n_items : 0);
+    const size_t o_ly = o_th + sizeof(double) * n_layers, o_sb = o_ly + sizeof(double) * 4 * n_wl * n_layers;
+    const size_t b_tab = film ? o_sb + (sub ? sizeof(double) * 2 * n_wl * n_ifcs : 0) : o_sf;
     char *d_tab;
     double *d_rows;
     Part *d_part;
@@ -468,14 +901,49 @@ extern "C" int rox_surface_transmission(rox_system *sys, uint32_t trace_flags, u
             model = kFixed;
         else if (glass && kind == ROX_COAT_BARE && row.profile != ROX_THINLENS && row.ph.kind == ROX_PH_NONE)
             model = kBare;
+        if (kind == ROX_COAT_STACK)             // rox_surface_thinfilm only, where it was checked above
+            model = mirror ? kStackMirror : kStack;
         const bool fixed = model == kFixed || model == kFixedMirror;
         ((double *)(h + o_cv))[2 * i] = fixed ? coat_value[2 * i] : 1.0;
         ((double *)(h + o_cv))[2 * i + 1] = fixed ? coat_value[2 * i + 1] : 1.0;
         ((int32_t *)(h + o_md))[i] = model;
     }
+    if (stacks)
+        memcpy(h + o_sf, film->stack_first, sizeof(int32_t) * (n_ifcs + 1));
+    if (film && film->wvl)
+        memcpy(h + o_wv, film->wvl, sizeof(double) * n_items);
+    if (n_layers > 0)
+        memcpy(h + o_th, film->thick, sizeof(double) * n_layers);
+    // N^2 = (re*re - im*im, (re + re)*im) and its reciprocal conj(N^2) / |N^2|^2
+    const auto square = [](const double *v, double *n2) {
+        n2[0] = v[0] * v[0] - v[1] * v[1];
+        n2[1] = (v[0] + v[0]) * v[1];
+    };
+    for (size_t j = 0; j < n_wl * n_layers; ++j) {
+        double *n2 = (double *)(h + o_ly) + 4 * j;
+        square(film->index + 2 * j, n2);
+        const double m = n2[0] * n2[0] + n2[1] * n2[1];
+        n2[2] = n2[0] / m;
+        n2[3] = -n2[1] / m;
+    }
+    for (size_t j = 0; sub && j < n_wl * n_ifcs; ++j) {
+        double *n2 = (double *)(h + o_sb) + 2 * j;
+        n2[0] = 1.0;                            // read only behind a stack on a mirror
+        n2[1] = 0.0;
+        if (coat_kind[j % n_ifcs] == ROX_COAT_STACK && ps.rows[j % n_ifcs].mode == ROX_REFLECT)
+            square(film->sub + 2 * j, n2);
+    }
     HIP_TRY(hipMemcpyAsync(d_tab, h, b_tab, hipMemcpyHostToDevice, st));
     HIP_TRY(ws->stage.record(st));
 
+    FilmArgs fa{};
+    if (film) {
+        fa.stack_first = stacks ? (const int32_t *)(d_tab + o_sf) : nullptr;
+        fa.thick = (const double *)(d_tab + o_th);
+        fa.layer = (const double *)(d_tab + o_ly);
+        fa.sub = sub ? (const double *)(d_tab + o_sb) : nullptr;
+        fa.n_layers = n_layers;
+    }
     TxArgs a{};
     a.rt = (const double *)(d_tab + o_rt);
     a.coat = (const double *)(d_tab + o_cv);
@@ -495,7 +963,13 @@ extern "C" int rox_surface_transmission(rox_system *sys, uint32_t trace_flags, u
             a.rows = rows ? (rows_host ? d_rows : rows + (size_t)i0 * n_rows * ld_rows) : nullptr;
             a.ld_rows = rows_host ? range_rays : ld_rows;
             a.row_ray0 = rows_host ? first : 0;
-            hipLaunchKernelGGL(fresnel_kernel, dim3((unsigned)nt, (unsigned)c), dim3(kBlock), 0, st, a);
+            if (film) {
+                fa.t = a;
+                fa.wvl = film->wvl ? (const double *)(d_tab + o_wv) + i0 : nullptr;
+                hipLaunchKernelGGL(thinfilm_kernel, dim3((unsigned)nt, (unsigned)c), dim3(kBlock), 0, st, fa);
+            } else {
+                hipLaunchKernelGGL(fresnel_kernel, dim3((unsigned)nt, (unsigned)c), dim3(kBlock), 0, st, a);
+            }
             HIP_TRY(hipGetLastError());
             // this range's rows, copied before the next launch reuses the scratch
             if (rows_host)
@@ -517,4 +991,28 @@ extern "C" int rox_surface_transmission(rox_system *sys, uint32_t trace_flags, u
     if (host_dst)
         HIP_TRY(hipStreamSynchronize(st));
     return 0;
+}
+
+}  // namespace
+
+extern "C" int rox_surface_transmission(rox_system *sys, uint32_t trace_flags, uint32_t tx_flags, int32_t n_items,
+                                        const rox_out *outs, int64_t n_rays, const int32_t *wvl_idx,
+                                        int32_t n_coat, const int32_t *coat_kind, const double *coat_value,
+                                        double *rows, int64_t ld_rows, rox_tx_surface *surf, rox_tx_item *item,
+                                        void *stream)
+{
+    return tx_entry("rox_surface_transmission", nullptr, sys, trace_flags, tx_flags, n_items, outs, n_rays, wvl_idx,
+                    n_coat, coat_kind, coat_value, rows, ld_rows, surf, item, stream);
+}
+
+extern "C" int rox_surface_thinfilm(rox_system *sys, uint32_t trace_flags, uint32_t tx_flags, int32_t n_items,
+                                    const rox_out *outs, int64_t n_rays, const int32_t *wvl_idx, const double *wvl,
+                                    int32_t n_coat, const int32_t *coat_kind, const double *coat_value,
+                                    const int32_t *stack_first, const double *layer_thickness,
+                                    const double *layer_index, const double *sub_index, double *rows,
+                                    int64_t ld_rows, rox_tx_surface *surf, rox_tx_item *item, void *stream)
+{
+    const Film film{wvl, stack_first, layer_thickness, layer_index, sub_index};
+    return tx_entry("rox_surface_thinfilm", &film, sys, trace_flags, tx_flags, n_items, outs, n_rays, wvl_idx, n_coat,
+                    coat_kind, coat_value, rows, ld_rows, surf, item, stream);
 }

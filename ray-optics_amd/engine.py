@@ -1291,6 +1291,73 @@ class TraceEngine:
         return rows, surf, item
 
     @_in_flight
+    def surface_thinfilm(self, results, trace_flags, wvl_idxs, wvls_nm=None, coat_kind=None, coat_value=None,
+                         stack_first=None, layer_thickness=None, layer_index=None, sub_index=None, want_rows=True,
+                         fields=False, on_device=False):
+        """rox_surface_thinfilm: surface_transmission with complex field vectors and, where
+        ``coat_kind`` is abi.COAT_STACK, a thin-film stack evaluated per ray.  ``wvls_nm``: each
+        item's vacuum wavelength; ``stack_first`` ([n_ifcs + 1] CSR offsets), ``layer_thickness``
+        ([L], the unit of ``wvls_nm``), ``layer_index`` ([n_wvls, L, 2] = (re, im) per row of the
+        index table) and ``sub_index`` ([n_wvls, n_ifcs, 2], the metal behind a mirror's stack) as
+        coatings.stack_tables builds them.  Returns ``(rows, surf, item)`` as surface_transmission
+        does; with ``fields`` n_rows = 16: re(E1), re(E2), im(E1), im(E2)."""
+        t = self.torch
+        what = 'surface_thinfilm'
+        results, n_items, n_seg, R, outs = self._packets(results, trace_flags, what)
+        wi = np.ascontiguousarray(np.asarray(wvl_idxs, dtype=np.int32).reshape(-1))
+        if wi.shape[0] != n_items:
+            raise EngineError(f'{what}: {wi.shape[0]} wvl_idxs for {n_items} items')
+        N, W = self.table.n_ifcs, len(self.table.wvls)
+        if (coat_kind is None) != (coat_value is None):
+            raise EngineError(f'{what}: coat_kind and coat_value go together')
+        ck = cv = wv = sf = lt = li = sb = None
+        if coat_kind is not None:
+            ck = np.ascontiguousarray(np.asarray(coat_kind, dtype=np.int32).reshape(-1))
+            cv = np.ascontiguousarray(np.asarray(coat_value, dtype=np.float64))
+            if ck.shape[0] != N or cv.shape != (N, 2):
+                raise EngineError(f'{what}: coat_kind [{ck.shape[0]}] and coat_value '
+                                  f'{list(cv.shape)} are not [{N}] and [{N}, 2], one entry per interface')
+        if wvls_nm is not None:
+            wv = np.ascontiguousarray(np.asarray(wvls_nm, dtype=np.float64).reshape(-1))
+            if wv.shape[0] != n_items:
+                raise EngineError(f'{what}: {wv.shape[0]} wvls_nm for {n_items} items')
+        if stack_first is not None:
+            sf = np.ascontiguousarray(np.asarray(stack_first, dtype=np.int32).reshape(-1))
+            if ck is None or sf.shape[0] != N + 1:
+                raise EngineError(f'{what}: stack_first [{sf.shape[0]}] is not [{N + 1}] beside coat_kind')
+            L = int(sf[-1])
+            lt = np.ascontiguousarray(np.asarray(layer_thickness if layer_thickness is not None else [],
+                                                 dtype=np.float64).reshape(-1))
+            li = np.ascontiguousarray(np.asarray(layer_index if layer_index is not None else np.zeros((W, 0, 2)),
+                                                 dtype=np.float64))
+            if lt.shape[0] != L or li.shape != (W, L, 2):
+                raise EngineError(f'{what}: layer_thickness [{lt.shape[0]}] and layer_index {list(li.shape)} are not '
+                                  f'[{L}] and [{W}, {L}, 2], the layers of stack_first and the wavelengths of the '
+                                  f'table')
+            if L > 0 and wv is None:
+                raise EngineError(f'{what}: layers need wvls_nm')
+        elif layer_thickness is not None or layer_index is not None:
+            raise EngineError(f'{what}: layer_thickness and layer_index go with stack_first')
+        if sub_index is not None:
+            sb = np.ascontiguousarray(np.asarray(sub_index, dtype=np.float64))
+            if sb.shape != (W, N, 2):
+                raise EngineError(f'{what}: sub_index {list(sb.shape)} is not [{W}, {N}, 2]')
+        n_rows = 16 if fields else 4
+        rows, p_rows = self._out(on_device, (n_items, n_rows, R), np.float64, t.float64) if want_rows \
+            else (None, None)
+        surf, p_surf = self._records_out(on_device, (n_items, n_seg), TX_SURFACE_DTYPE)
+        item, p_item = self._records_out(on_device, (n_items,), TX_ITEM_DTYPE)
+        ptr = lambda v: v.ctypes.data if v is not None and v.size else None     # noqa: E731
+        with t.cuda.device(self.device):
+            _check(self.lib.rox_surface_thinfilm(self._handle, int(trace_flags), abi.TX_FIELDS if fields else 0,
+                                                 n_items, outs, R, wi.ctypes.data, ptr(wv),
+                                                 N if ck is not None else 0, ptr(ck), ptr(cv),
+                                                 sf.ctypes.data if sf is not None else None, ptr(lt), ptr(li),
+                                                 ptr(sb), p_rows, R, p_surf, p_item, self._stream()),
+                   'rox_surface_thinfilm')
+        return rows, surf, item
+
+    @_in_flight
     def focus_psf_ee(self, psf, pitch, centers, radii, want_centroid=True):
         """rox_focus_psf_ee over the PSFs focus_psf returns (``psf``: float64 [n_items, K, M, M] in
         HBM): the fraction of each PSF's sum over the pixels whose centre lies within ``radii``
