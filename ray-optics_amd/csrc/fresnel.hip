@@ -16,13 +16,17 @@
 //
 // rox_surface_thinfilm is the same walk with complex field vectors and, where an interface has a
 // stack of thin films or a metal behind it, the characteristic matrix of the stack evaluated per
-// ray (thinfilm_kernel: kFilmRays per thread, the layer loop wave-uniform in trip count, a stack's
-// layer tables for the item's wavelength scalar loads as well).  Both entries share the argument
-// checks, the staging, the launch loop and the finishing kernel (tx_entry).
+// ray (the layer loop wave-uniform in trip count, a stack's layer tables for the item's wavelength
+// scalar loads as well).  The walk is written once, fresnel_kernel<F, Args>, and instantiated for
+// real (V3, TxArgs) and for complex (C3, FilmArgs) field vectors; what the two do differently is in
+// the overloads beside carry and through, and the stack exists only in the complex instantiation.
+// Both entries share the argument checks, the staging, the launch loop and the finishing kernel
+// (tx_entry).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdint>
+#include <type_traits>
 
 #include "rox_device.hpp"
 #include "rox_packets.hpp"
@@ -38,7 +42,8 @@ constexpr char kHipWhere[] = "rox_surface_transmission: ";
 
 constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / 64;
-constexpr int kRays = 2;                        // rays per thread: 107 VGPRs, no scratch, 4 waves per SIMD
+constexpr int kRays = 2;                        // rays per thread: 107 VGPRs and 4 waves per SIMD (real), 214 and 2
+                                                // (complex), no scratch
 constexpr int kTile = kBlock * kRays;           // rays per workgroup
 // Device scratch of one launch (partial records, records, rows bound for host memory): a call that
 // needs more per launch runs as consecutive launches over fewer items and, for the rows, fewer
@@ -53,7 +58,7 @@ enum Model : int32_t {
     kMirror = 2,                                // ts = -1
     kFixed = 3,                                 // given power coefficients
     kFixedMirror = 4,
-    kStack = 5,                                 // thin films between two real media (thinfilm_kernel only)
+    kStack = 5,                                 // thin films between two real media (the complex walk only)
     kStackMirror = 6,                           // thin films, or none, over a metal
 };
 
@@ -90,9 +95,11 @@ struct TxArgs {
     Part *part;                                 // [items][n_waves][n_seg + 1] or nullptr
 };
 
-// what thinfilm_kernel reads besides: a layer's row of `layer` is (re N^2, im N^2, re 1/N^2, im 1/N^2)
-struct FilmArgs {
-    TxArgs t;                                   // n_rows is 4 or 16
+// what the complex walk reads besides: a layer's row of `layer` is (re N^2, im N^2, re 1/N^2, im 1/N^2).
+// Derived, so that the walk binds the TxArgs of either launch as `const TxArgs &` to the kernel
+// argument itself: reached through a function that returns a reference, the packet and status
+// reads of both instantiations turn from global into flat loads.
+struct FilmArgs : TxArgs {                      // n_rows is 4 or 16
     const double *wvl;                          // [chunk's items] vacuum wavelength, the thicknesses' unit
     const int32_t *stack_first;                 // [n_ifcs + 1] CSR offsets into the layers
     const double *thick;                        // [n_layers]
@@ -100,11 +107,6 @@ struct FilmArgs {
     const double *sub;                          // [n_wvls][n_ifcs][2] N^2 behind a kStackMirror
     int32_t n_layers;
 };
-
-constexpr int kFilmRays = kRays;                // rays per thread of thinfilm_kernel, as fresnel_kernel: the same
-                                                // rays per wave, so the same partial sums in the same order
-constexpr int kFilmTile = kBlock * kFilmRays;
-static_assert(kFilmTile == kTile, "both kernels walk the same tiles: tx_entry sizes the launches with kTile");
 
 struct V3 {
     double x, y, z;
@@ -167,184 +169,6 @@ __device__ __forceinline__ Part wave_merge(Part t)
     return t;
 }
 
-__global__ __launch_bounds__(kBlock) void fresnel_kernel(const TxArgs a)
-{
-    const ItemIn it = a.items[blockIdx.y];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int n_seg = a.n_seg;
-    // the tables through the constant address space (rox_device.hpp): a wave-uniform address there is
-    // a scalar load into SGPRs, and the stores of the partial records do not order it
-    const ctbli slot_ifc = (ctbli)a.slot_ifc, model_of = (ctbli)a.model;
-    const ctblp rt_of = (ctblp)a.rt, coat = (ctblp)a.coat;
-    const ctblp ntab = (ctblp)a.n_table + (size_t)it.wvl * a.n_ifcs;
-    const double nan = __builtin_nan("");
-
-    int64_t r[kRays];
-    bool ok[kRays];
-    V3 b4[kRays], E1[kRays], E2[kRays];
-    double q[kRays];
-#pragma unroll
-    for (int j = 0; j < kRays; ++j) {
-        r[j] = a.ray0 + (int64_t)blockIdx.x * kTile + j * kBlock + threadIdx.x;
-        ok[j] = r[j] < a.n_rays && it.status[r[j]] == ROX_OK;
-        b4[j] = E1[j] = E2[j] = V3{0.0, 0.0, 0.0};
-        q[j] = 1.0;
-    }
-    const size_t wave_of_item = (size_t)(a.ray0 / kTile + blockIdx.x) * kWaves + wave;
-    Part *out = a.part ? a.part + ((size_t)blockIdx.y * a.n_waves + wave_of_item) * (n_seg + 1) : nullptr;
-
-    for (int k = 0; k < n_seg; ++k) {
-        const double *rec = it.seg + (size_t)k * ROX_SEG_DOUBLES * it.ld;
-        V3 d[kRays], N[kRays];
-#pragma unroll
-        for (int j = 0; j < kRays; ++j) {
-            d[j] = N[j] = V3{0.0, 0.0, 0.0};
-            if (ok[j]) {
-                d[j] = V3{rec[3 * it.ld + r[j]], rec[4 * it.ld + r[j]], rec[5 * it.ld + r[j]]};
-                N[j] = V3{rec[7 * it.ld + r[j]], rec[8 * it.ld + r[j]], rec[9 * it.ld + r[j]]};
-            }
-        }
-
-        // the state into this slot's frame: through every interface in between
-        const int s = slot_ifc[k];
-        if (k >= 1)
-            for (int i = slot_ifc[k - 1]; i < s; ++i) {
-                const ctblp rt = rt_of + (size_t)i * kRtDoubles;
-                const bool c_order = rt[9] != 0.0;
-#pragma unroll
-                for (int j = 0; j < kRays; ++j) {
-                    b4[j] = carry(rt, c_order, b4[j]);
-                    E1[j] = carry(rt, c_order, E1[j]);
-                    E2[j] = carry(rt, c_order, E2[j]);
-                }
-            }
-
-        // the slot's model: the same for every ray of the workgroup
-        const bool inner = k > 0 && k < n_seg - 1;
-        int model = kIdeal;
-        double n1 = 1.0, n2 = 1.0, cTs = 1.0, cTp = 1.0, cts = 1.0, ctp = 1.0;
-        if (inner) {
-            model = model_of[s];
-            n1 = ntab[s - 1];
-            n2 = ntab[s];
-            if (model == kBare && n1 == n2)
-                model = kIdeal;
-            if (model == kFixed || model == kFixedMirror) {
-                cTs = coat[2 * s];
-                cTp = coat[2 * s + 1];
-                cts = sqrt(cTs);
-                ctp = sqrt(cTp);
-            }
-            if (model == kMirror || model == kFixedMirror)
-                cts = -cts;
-        }
-
-        Part t = part_empty();
-#pragma unroll
-        for (int j = 0; j < kRays; ++j) {
-            if (k == 0) {
-                V3 e = V3{d[j].z, 0.0, -d[j].x};
-                double ee = dot(e, e);
-                if (ee == 0.0) {
-                    e = V3{1.0, 0.0, 0.0};
-                    ee = dot(e, e);
-                }
-                E1[j] = over(e, sqrt(ee));
-                E2[j] = cross(d[j], E1[j]);
-                b4[j] = d[j];
-            }
-            const double ci = fabs(dot(b4[j], N[j]));
-            double Ts = 1.0, Tp = 1.0;
-            if (inner) {
-                double ts = cts, tp = ctp, qs = 1.0;
-                Ts = cTs;
-                Tp = cTp;
-                if (model == kBare) {
-                    const double ct = fabs(dot(d[j], N[j]));
-                    const double A = n1 * ci, B = n2 * ct;
-                    ts = (A + A) / (A + B);
-                    tp = (A + A) / (n2 * ci + n1 * ct);
-                    qs = B / A;
-                    if (ci == 0.0)
-                        ts = tp = qs = 0.0;
-                    Ts = qs * (ts * ts);
-                    Tp = qs * (tp * tp);
-                }
-                V3 c = cross(b4[j], N[j]);
-                double cc = dot(c, c);
-                if (cc == 0.0) {
-                    c = fabs(b4[j].x) <= fabs(b4[j].y) ? cross(b4[j], V3{1.0, 0.0, 0.0})
-                                                       : cross(b4[j], V3{0.0, 1.0, 0.0});
-                    cc = dot(c, c);
-                }
-                const V3 sh = over(c, sqrt(cc));
-                const V3 pi = cross(b4[j], sh), po = cross(d[j], sh);
-                E1[j] = through(E1[j], sh, pi, po, ts, tp);
-                E2[j] = through(E2[j], sh, pi, po, ts, tp);
-                q[j] = q[j] * qs;
-            }
-            if (ok[j]) {
-                t.v[0] += 1.0;
-                t.v[1] += Ts;
-                t.v[2] += Tp;
-                t.v[3] += (Ts + Tp) / 2.0;
-                t.v[4] = fmin(t.v[4], Ts);
-                t.v[5] = fmin(t.v[5], Tp);
-                t.v[6] += ci;
-                t.v[7] = fmin(t.v[7], ci);
-            }
-            b4[j] = d[j];
-        }
-        if (out) {
-            t = wave_merge<false>(t);
-            if (lane == 0)
-                out[k] = t;
-        }
-    }
-
-    // the rows of each ray, and the item's partial record
-    const double inf = __builtin_inf();
-    Part t{{0.0, 0.0, 0.0, 0.0, inf, -inf, 0.0, -inf}};
-#pragma unroll
-    for (int j = 0; j < kRays; ++j) {
-        const double g11 = dot(E1[j], E1[j]), g12 = dot(E1[j], E2[j]), g22 = dot(E2[j], E2[j]);
-        const double m = (g11 + g22) / 2.0, h = (g11 - g22) / 2.0;
-        const double rr = sqrt(h * h + g12 * g12);
-        const double T = q[j] * m, T1 = q[j] * g11, T2 = q[j] * g22;
-        const double D = m == 0.0 ? 0.0 : rr / m;
-        if (ok[j]) {
-            t.v[0] += 1.0;
-            t.v[1] += T;
-            t.v[2] += T1;
-            t.v[3] += T2;
-            t.v[4] = fmin(t.v[4], T);
-            t.v[5] = fmax(t.v[5], T);
-            t.v[6] += D;
-            t.v[7] = fmax(t.v[7], D);
-        }
-        if (a.rows && r[j] < a.n_rays) {
-            double *row = a.rows + (size_t)blockIdx.y * a.n_rows * a.ld_rows + (r[j] - a.row_ray0);
-            row[0] = ok[j] ? T : nan;
-            row[a.ld_rows] = ok[j] ? T1 : nan;
-            row[2 * a.ld_rows] = ok[j] ? T2 : nan;
-            row[3 * a.ld_rows] = ok[j] ? D : nan;
-            if (a.n_rows == 10) {
-                row[4 * a.ld_rows] = ok[j] ? E1[j].x : nan;
-                row[5 * a.ld_rows] = ok[j] ? E1[j].y : nan;
-                row[6 * a.ld_rows] = ok[j] ? E1[j].z : nan;
-                row[7 * a.ld_rows] = ok[j] ? E2[j].x : nan;
-                row[8 * a.ld_rows] = ok[j] ? E2[j].y : nan;
-                row[9 * a.ld_rows] = ok[j] ? E2[j].z : nan;
-            }
-        }
-    }
-    if (out) {
-        t = wave_merge<true>(t);
-        if (lane == 0)
-            out[n_seg] = t;
-    }
-}
-
 // ---- thin films: complex amplitudes (include/roxtrace.h rox_surface_thinfilm states the order)
 struct Cx {
     double r, i;
@@ -383,14 +207,27 @@ struct C3 {
     V3 re, im;
 };
 
-// the state of a ray along the walk
-struct FilmRay {
-    int64_t r;
-    bool ok;
-    V3 b4;
-    C3 E1, E2;
-    double q;
-};
+// What a complex field vector does differently from a real one: the walk below is written once
+// over either, and these overloads (with carry and through above) are all that tells them apart.
+__device__ __forceinline__ C3 carry(ctblp rt, bool c_order, const C3 &v)
+{
+    return C3{carry(rt, c_order, v.re), carry(rt, c_order, v.im)};
+}
+
+// a field that starts as the real vector v
+__device__ __forceinline__ void start(V3 &E, const V3 &v) { E = v; }
+__device__ __forceinline__ void start(C3 &E, const V3 &v) { E = C3{v, V3{0.0, 0.0, 0.0}}; }
+
+// ts and tp are real for a real field and complex for a complex one, where only a stack gives them
+// an imaginary part: the real part of either
+__device__ __forceinline__ double &re(double &t) { return t; }
+__device__ __forceinline__ double &re(Cx &t) { return t.r; }
+
+// real ts, tp act on the real and on the imaginary part separately
+__device__ __forceinline__ C3 through(const C3 &E, const V3 &s, const V3 &pi, const V3 &po, double ts, double tp)
+{
+    return C3{through(E.re, s, pi, po, ts, tp), through(E.im, s, pi, po, ts, tp)};
+}
 
 // E <- (ts*(s . E))*s + (tp*(p_in . E))*p_out with complex ts, tp and E
 __device__ __forceinline__ C3 through_cx(const C3 &E, const V3 &s, const V3 &pi, const V3 &po, const Cx &ts,
@@ -401,45 +238,101 @@ __device__ __forceinline__ C3 through_cx(const C3 &E, const V3 &s, const V3 &pi,
               V3{a.i * s.x + b.i * po.x, a.i * s.y + b.i * po.y, a.i * s.z + b.i * po.z}};
 }
 
-// fresnel_kernel's walk with complex E1, E2, over the same tile with the same rays per thread and
-// wave: the partial sums of the records are formed in the same order.  An interface of the models
-// kIdeal .. kFixedMirror applies fresnel_kernel's real formulas to the real and to the imaginary
-// part of the fields; kStack / kStackMirror evaluate the stack per ray.  The layer loop's trip
-// count, a layer's N^2 and thickness and the wavelength are wave-uniform (scalar loads); s and p
-// share g, delta, its cosine and its sine.  214 VGPRs, no scratch, 2 waves per SIMD.
-__global__ __launch_bounds__(kBlock) void thinfilm_kernel(const FilmArgs fa)
+// the Gram products of the two fields: <E1, E1>, <E2, E2> and |<E1, E2>|^2 (Hermitian when complex)
+struct Gram {
+    double g11, g22, g12sq;
+};
+__device__ __forceinline__ Gram gram(const V3 &E1, const V3 &E2)
 {
-    const TxArgs &a = fa.t;
+    const double g11 = dot(E1, E1), g12 = dot(E1, E2), g22 = dot(E2, E2);
+    return Gram{g11, g22, g12 * g12};
+}
+__device__ __forceinline__ Gram gram(const C3 &E1, const C3 &E2)
+{
+    const double g11 = dot(E1.re, E1.re) + dot(E1.im, E1.im), g22 = dot(E2.re, E2.re) + dot(E2.im, E2.im);
+    const double g12r = dot(E1.re, E2.re) + dot(E1.im, E2.im), g12i = dot(E1.re, E2.im) - dot(E1.im, E2.re);
+    return Gram{g11, g22, g12r * g12r + g12i * g12i};
+}
+
+// the field rows of a ray, from row `first` of its column `row` on: E1, E2 (6 rows), or re(E1), re(E2),
+// im(E1), im(E2) (12)
+__device__ __forceinline__ void store_fields(double *row, int64_t ld, int first, bool ok, const V3 &E1, const V3 &E2)
+{
+    const double nan = __builtin_nan("");
+    const double f[6] = {E1.x, E1.y, E1.z, E2.x, E2.y, E2.z};
+#pragma unroll
+    for (int c = 0; c < 6; ++c)
+        row[(first + c) * ld] = ok ? f[c] : nan;
+}
+__device__ __forceinline__ void store_fields(double *row, int64_t ld, int first, bool ok, const C3 &E1, const C3 &E2)
+{
+    store_fields(row, ld, first, ok, E1.re, E2.re);
+    store_fields(row, ld, first + 6, ok, E1.im, E2.im);
+}
+
+// the state of a ray along the walk
+template <class F>
+struct Ray {
+    int64_t r;
+    bool ok;
+    V3 b4;                                      // the direction before the slot
+    F E1, E2;
+    double q;                                   // the flux factor
+};
+
+// The walk of both entries: F = V3, Args = TxArgs carries real field vectors (rox_surface_transmission),
+// F = C3, Args = FilmArgs complex ones (rox_surface_thinfilm).  Both walk the same tile with the same
+// rays per thread and wave, so the partial sums of the records are formed in the same order.  An
+// interface of the models kIdeal .. kFixedMirror applies the same real formulas to either field;
+// kStack / kStackMirror, in the complex walk only, evaluate the stack per ray: the layer loop's trip
+// count, a layer's N^2 and thickness and the wavelength are wave-uniform (scalar loads); s and p
+// share g, delta, its cosine and its sine.
+template <class F, class Args>
+__global__ __launch_bounds__(kBlock) void fresnel_kernel(const Args args)
+{
+    constexpr bool kFilm = std::is_same<F, C3>::value;
+    using Co = typename std::conditional<kFilm, Cx, double>::type;      // of (ts, tp)
+    const TxArgs &a = args;                     // bound to the argument itself: see FilmArgs
     const ItemIn it = a.items[blockIdx.y];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int n_seg = a.n_seg;
-    const ctbli slot_ifc = (ctbli)a.slot_ifc, model_of = (ctbli)a.model, first = (ctbli)fa.stack_first;
-    const ctblp rt_of = (ctblp)a.rt, coat = (ctblp)a.coat, thick = (ctblp)fa.thick;
+    // the tables through the constant address space (rox_device.hpp): a wave-uniform address there is
+    // a scalar load into SGPRs, and the stores of the partial records do not order it
+    const ctbli slot_ifc = (ctbli)a.slot_ifc, model_of = (ctbli)a.model;
+    const ctblp rt_of = (ctblp)a.rt, coat = (ctblp)a.coat;
     const ctblp ntab = (ctblp)a.n_table + (size_t)it.wvl * a.n_ifcs;
-    const ctblp layer = (ctblp)fa.layer + (size_t)it.wvl * fa.n_layers * 4;
-    const ctblp sub = (ctblp)fa.sub + (size_t)it.wvl * a.n_ifcs * 2;
-    const double wvl = fa.wvl ? ((ctblp)fa.wvl)[blockIdx.y] : 1.0;
+    [[maybe_unused]] ctbli first = nullptr;
+    [[maybe_unused]] ctblp thick = nullptr, layer = nullptr, sub = nullptr;
+    [[maybe_unused]] double wvl = 1.0;
+    if constexpr (kFilm) {
+        first = (ctbli)args.stack_first;
+        thick = (ctblp)args.thick;
+        layer = (ctblp)args.layer + (size_t)it.wvl * args.n_layers * 4;
+        sub = (ctblp)args.sub + (size_t)it.wvl * a.n_ifcs * 2;
+        wvl = args.wvl ? ((ctblp)args.wvl)[blockIdx.y] : 1.0;
+    }
     const double nan = __builtin_nan("");
 
     const V3 zero{0.0, 0.0, 0.0};
-    FilmRay ray[kFilmRays];
+    Ray<F> ray[kRays];
 #pragma unroll
-    for (int j = 0; j < kFilmRays; ++j) {
-        FilmRay &y = ray[j];
-        y.r = a.ray0 + (int64_t)blockIdx.x * kFilmTile + j * kBlock + threadIdx.x;
+    for (int j = 0; j < kRays; ++j) {
+        Ray<F> &y = ray[j];
+        y.r = a.ray0 + (int64_t)blockIdx.x * kTile + j * kBlock + threadIdx.x;
         y.ok = y.r < a.n_rays && it.status[y.r] == ROX_OK;
         y.b4 = zero;
-        y.E1 = y.E2 = C3{zero, zero};
+        start(y.E1, zero);
+        start(y.E2, zero);
         y.q = 1.0;
     }
-    const size_t wave_of_item = (size_t)(a.ray0 / kFilmTile + blockIdx.x) * kWaves + wave;
+    const size_t wave_of_item = (size_t)(a.ray0 / kTile + blockIdx.x) * kWaves + wave;
     Part *out = a.part ? a.part + ((size_t)blockIdx.y * a.n_waves + wave_of_item) * (n_seg + 1) : nullptr;
 
     for (int k = 0; k < n_seg; ++k) {
         const double *rec = it.seg + (size_t)k * ROX_SEG_DOUBLES * it.ld;
-        V3 dj[kFilmRays], Nj[kFilmRays];
+        V3 dj[kRays], Nj[kRays];
 #pragma unroll
-        for (int j = 0; j < kFilmRays; ++j) {
+        for (int j = 0; j < kRays; ++j) {
             const int64_t r = ray[j].r;
             dj[j] = Nj[j] = zero;
             if (ray[j].ok) {
@@ -448,24 +341,27 @@ __global__ __launch_bounds__(kBlock) void thinfilm_kernel(const FilmArgs fa)
             }
         }
 
+        // the state into this slot's frame: through every interface in between
         const int s = slot_ifc[k];
         if (k >= 1)
             for (int i = slot_ifc[k - 1]; i < s; ++i) {
                 const ctblp rt = rt_of + (size_t)i * kRtDoubles;
                 const bool c_order = rt[9] != 0.0;
 #pragma unroll
-                for (int j = 0; j < kFilmRays; ++j) {
-                    FilmRay &y = ray[j];
+                for (int j = 0; j < kRays; ++j) {
+                    Ray<F> &y = ray[j];
                     y.b4 = carry(rt, c_order, y.b4);
-                    y.E1 = C3{carry(rt, c_order, y.E1.re), carry(rt, c_order, y.E1.im)};
-                    y.E2 = C3{carry(rt, c_order, y.E2.re), carry(rt, c_order, y.E2.im)};
+                    y.E1 = carry(rt, c_order, y.E1);
+                    y.E2 = carry(rt, c_order, y.E2);
                 }
             }
 
+        // the slot's model: the same for every ray of the workgroup
         const bool inner = k > 0 && k < n_seg - 1;
-        int model = kIdeal, l0 = 0, l1 = 0;
+        int model = kIdeal;
         double n1 = 1.0, n2 = 1.0, cTs = 1.0, cTp = 1.0, cts = 1.0, ctp = 1.0;
-        Cx sub2{1.0, 0.0};
+        [[maybe_unused]] int l0 = 0, l1 = 0;
+        [[maybe_unused]] Cx sub2{1.0, 0.0};
         if (inner) {
             model = model_of[s];
             n1 = ntab[s - 1];
@@ -480,23 +376,23 @@ __global__ __launch_bounds__(kBlock) void thinfilm_kernel(const FilmArgs fa)
             }
             if (model == kMirror || model == kFixedMirror)
                 cts = -cts;
-            if (model == kStack || model == kStackMirror) {
-                l0 = first[s];
-                l1 = first[s + 1];
+            if constexpr (kFilm) {
+                if (model == kStack || model == kStackMirror) {
+                    l0 = first[s];
+                    l1 = first[s + 1];
+                }
+                if (model == kStackMirror)
+                    sub2 = Cx{sub[2 * s], sub[2 * s + 1]};
             }
-            if (model == kStackMirror)
-                sub2 = Cx{sub[2 * s], sub[2 * s + 1]};
         }
-        const bool stack = model == kStack || model == kStackMirror;
+        const bool stack = kFilm && (model == kStack || model == kStackMirror);
 
         Part t = part_empty();
 #pragma unroll
-        for (int j = 0; j < kFilmRays; ++j) {
+        for (int j = 0; j < kRays; ++j) {
             const V3 d = dj[j], N = Nj[j];
-            const bool ok = ray[j].ok;
             V3 &b4 = ray[j].b4;
-            C3 &E1 = ray[j].E1, &E2 = ray[j].E2;
-            double &q = ray[j].q;
+            F &E1 = ray[j].E1, &E2 = ray[j].E2;
             if (k == 0) {
                 V3 e = V3{d.z, 0.0, -d.x};
                 double ee = dot(e, e);
@@ -504,78 +400,81 @@ __global__ __launch_bounds__(kBlock) void thinfilm_kernel(const FilmArgs fa)
                     e = V3{1.0, 0.0, 0.0};
                     ee = dot(e, e);
                 }
-                E1 = C3{over(e, sqrt(ee)), zero};
-                E2 = C3{cross(d, E1.re), zero};
+                const V3 e1 = over(e, sqrt(ee));
+                start(E1, e1);
+                start(E2, cross(d, e1));
                 b4 = d;
             }
             const double ci = fabs(dot(b4, N));
             double Ts = 1.0, Tp = 1.0;
             if (inner) {
-                Cx ts{cts, 0.0}, tp{ctp, 0.0};
+                Co ts{cts}, tp{ctp};
                 double qs = 1.0;
                 Ts = cTs;
                 Tp = cTp;
                 if (model == kBare) {
                     const double ct = fabs(dot(d, N));
                     const double A = n1 * ci, B = n2 * ct;
-                    ts.r = (A + A) / (A + B);
-                    tp.r = (A + A) / (n2 * ci + n1 * ct);
+                    re(ts) = (A + A) / (A + B);
+                    re(tp) = (A + A) / (n2 * ci + n1 * ct);
                     qs = B / A;
                     if (ci == 0.0)
-                        ts.r = tp.r = qs = 0.0;
-                    Ts = qs * (ts.r * ts.r);
-                    Tp = qs * (tp.r * tp.r);
-                } else if (stack) {
-                    const double ct = fabs(dot(d, N));
-                    const double A = n1 * ci, a2 = (n1 * n1) * (1.0 - ci * ci);
-                    const double Bx = n2 * ct;
-                    // (B, C) at the exit side: (1, y_exit) for s and for p
-                    Cx ys{Bx, 0.0}, yp{(n2 * n2) / Bx, 0.0};
-                    if (model == kStackMirror) {
-                        ys = csqrt_up(sub2.r - a2, sub2.i);
-                        yp = cmul(sub2, cinv(ys));
-                    }
-                    Cx Bs{1.0, 0.0}, Cs = ys, Bp{1.0, 0.0}, Cp = yp;
-                    double att = 0.0;
-                    for (int l = l1 - 1; l >= l0; --l) {
-                        const Cx N2{layer[4 * l], layer[4 * l + 1]}, iN2{layer[4 * l + 2], layer[4 * l + 3]};
-                        const double kd = (6.283185307179586 * thick[l]) / wvl;
-                        const Cx g = csqrt_up(N2.r - a2, N2.i), ig = cinv(g);
-                        const double x = kd * g.r, y = kd * g.i;
-                        double sx, cx;
-                        sincos(x, &sx, &cx);
-                        // cos and sin of x + iy over e^y: only e^(-2y) <= 1 is formed
-                        const double e2 = exp(-(y + y));
-                        const double ch = (1.0 + e2) / 2.0, sh = (1.0 - e2) / 2.0;
-                        const Cx cs{cx * ch, -(sx * sh)}, sn{sx * ch, cx * sh};
-                        att = att + y;
-                        film_layer(Bs, Cs, cs, sn, g, ig);
-                        film_layer(Bp, Cp, cs, sn, cmul(N2, ig), cmul(g, iN2));
-                    }
-                    const double y0s = A, y0p = (n1 * n1) / A;
-                    const Cx ds{y0s * Bs.r + Cs.r, y0s * Bs.i + Cs.i}, dp{y0p * Bp.r + Cp.r, y0p * Bp.i + Cp.i};
-                    const Cx is = cinv(ds), ip = cinv(dp);
-                    if (model == kStack) {
-                        const double f = exp(-att);
-                        const double fs = f * (y0s + y0s), fp = (f * (y0p + y0p)) * (ci / ct);
-                        ts = Cx{fs * is.r, fs * is.i};
-                        tp = Cx{fp * ip.r, fp * ip.i};
-                        qs = Bx / A;
-                        if (ci == 0.0) {
-                            ts = tp = Cx{0.0, 0.0};
-                            qs = 0.0;
+                        re(ts) = re(tp) = qs = 0.0;
+                    Ts = qs * (re(ts) * re(ts));
+                    Tp = qs * (re(tp) * re(tp));
+                } else if constexpr (kFilm) {
+                    if (stack) {
+                        const double ct = fabs(dot(d, N));
+                        const double A = n1 * ci, a2 = (n1 * n1) * (1.0 - ci * ci);
+                        const double Bx = n2 * ct;
+                        // (B, C) at the exit side: (1, y_exit) for s and for p
+                        Cx ys{Bx, 0.0}, yp{(n2 * n2) / Bx, 0.0};
+                        if (model == kStackMirror) {
+                            ys = csqrt_up(sub2.r - a2, sub2.i);
+                            yp = cmul(sub2, cinv(ys));
                         }
-                    } else {
-                        ts = cmul(Cx{y0s * Bs.r - Cs.r, y0s * Bs.i - Cs.i}, is);
-                        const Cx rp = cmul(Cx{y0p * Bp.r - Cp.r, y0p * Bp.i - Cp.i}, ip);
-                        tp = Cx{-rp.r, -rp.i};
-                        if (ci == 0.0) {
-                            ts = Cx{-1.0, 0.0};
-                            tp = Cx{-1.0, 0.0};
+                        Cx Bs{1.0, 0.0}, Cs = ys, Bp{1.0, 0.0}, Cp = yp;
+                        double att = 0.0;
+                        for (int l = l1 - 1; l >= l0; --l) {
+                            const Cx N2{layer[4 * l], layer[4 * l + 1]}, iN2{layer[4 * l + 2], layer[4 * l + 3]};
+                            const double kd = (6.283185307179586 * thick[l]) / wvl;
+                            const Cx g = csqrt_up(N2.r - a2, N2.i), ig = cinv(g);
+                            const double x = kd * g.r, y = kd * g.i;
+                            double sx, cx;
+                            sincos(x, &sx, &cx);
+                            // cos and sin of x + iy over e^y: only e^(-2y) <= 1 is formed
+                            const double e2 = exp(-(y + y));
+                            const double ch = (1.0 + e2) / 2.0, sh = (1.0 - e2) / 2.0;
+                            const Cx cs{cx * ch, -(sx * sh)}, sn{sx * ch, cx * sh};
+                            att = att + y;
+                            film_layer(Bs, Cs, cs, sn, g, ig);
+                            film_layer(Bp, Cp, cs, sn, cmul(N2, ig), cmul(g, iN2));
                         }
+                        const double y0s = A, y0p = (n1 * n1) / A;
+                        const Cx ds{y0s * Bs.r + Cs.r, y0s * Bs.i + Cs.i}, dp{y0p * Bp.r + Cp.r, y0p * Bp.i + Cp.i};
+                        const Cx is = cinv(ds), ip = cinv(dp);
+                        if (model == kStack) {
+                            const double f = exp(-att);
+                            const double fs = f * (y0s + y0s), fp = (f * (y0p + y0p)) * (ci / ct);
+                            ts = Cx{fs * is.r, fs * is.i};
+                            tp = Cx{fp * ip.r, fp * ip.i};
+                            qs = Bx / A;
+                            if (ci == 0.0) {
+                                ts = tp = Cx{0.0, 0.0};
+                                qs = 0.0;
+                            }
+                        } else {
+                            ts = cmul(Cx{y0s * Bs.r - Cs.r, y0s * Bs.i - Cs.i}, is);
+                            const Cx rp = cmul(Cx{y0p * Bp.r - Cp.r, y0p * Bp.i - Cp.i}, ip);
+                            tp = Cx{-rp.r, -rp.i};
+                            if (ci == 0.0) {
+                                ts = Cx{-1.0, 0.0};
+                                tp = Cx{-1.0, 0.0};
+                            }
+                        }
+                        Ts = qs * (ts.r * ts.r + ts.i * ts.i);
+                        Tp = qs * (tp.r * tp.r + tp.i * tp.i);
                     }
-                    Ts = qs * (ts.r * ts.r + ts.i * ts.i);
-                    Tp = qs * (tp.r * tp.r + tp.i * tp.i);
                 }
                 V3 c = cross(b4, N);
                 double cc = dot(c, c);
@@ -586,15 +485,17 @@ __global__ __launch_bounds__(kBlock) void thinfilm_kernel(const FilmArgs fa)
                 const V3 sh = over(c, sqrt(cc));
                 const V3 pi = cross(b4, sh), po = cross(d, sh);
                 if (stack) {
-                    E1 = through_cx(E1, sh, pi, po, ts, tp);
-                    E2 = through_cx(E2, sh, pi, po, ts, tp);
+                    if constexpr (kFilm) {
+                        E1 = through_cx(E1, sh, pi, po, ts, tp);
+                        E2 = through_cx(E2, sh, pi, po, ts, tp);
+                    }
                 } else {
-                    E1 = C3{through(E1.re, sh, pi, po, ts.r, tp.r), through(E1.im, sh, pi, po, ts.r, tp.r)};
-                    E2 = C3{through(E2.re, sh, pi, po, ts.r, tp.r), through(E2.im, sh, pi, po, ts.r, tp.r)};
+                    E1 = through(E1, sh, pi, po, re(ts), re(tp));
+                    E2 = through(E2, sh, pi, po, re(ts), re(tp));
                 }
-                q = q * qs;
+                ray[j].q = ray[j].q * qs;
             }
-            if (ok) {
+            if (ray[j].ok) {
                 t.v[0] += 1.0;
                 t.v[1] += Ts;
                 t.v[2] += Tp;
@@ -613,22 +514,18 @@ __global__ __launch_bounds__(kBlock) void thinfilm_kernel(const FilmArgs fa)
         }
     }
 
-    // the rows of each ray, and the item's partial record: Hermitian products
+    // the rows of each ray, and the item's partial record
     const double inf = __builtin_inf();
     Part t{{0.0, 0.0, 0.0, 0.0, inf, -inf, 0.0, -inf}};
 #pragma unroll
-    for (int j = 0; j < kFilmRays; ++j) {
-        const C3 &E1 = ray[j].E1, &E2 = ray[j].E2;
-        const double q = ray[j].q;
-        const bool ok = ray[j].ok;
-        const int64_t r = ray[j].r;
-        const double g11 = dot(E1.re, E1.re) + dot(E1.im, E1.im), g22 = dot(E2.re, E2.re) + dot(E2.im, E2.im);
-        const double g12r = dot(E1.re, E2.re) + dot(E1.im, E2.im), g12i = dot(E1.re, E2.im) - dot(E1.im, E2.re);
-        const double m = (g11 + g22) / 2.0, h = (g11 - g22) / 2.0;
-        const double rr = sqrt(h * h + (g12r * g12r + g12i * g12i));
-        const double T = q * m, T1 = q * g11, T2 = q * g22;
+    for (int j = 0; j < kRays; ++j) {
+        const Ray<F> &y = ray[j];
+        const Gram g = gram(y.E1, y.E2);
+        const double m = (g.g11 + g.g22) / 2.0, h = (g.g11 - g.g22) / 2.0;
+        const double rr = sqrt(h * h + g.g12sq);
+        const double T = y.q * m, T1 = y.q * g.g11, T2 = y.q * g.g22;
         const double D = m == 0.0 ? 0.0 : rr / m;
-        if (ok) {
+        if (y.ok) {
             t.v[0] += 1.0;
             t.v[1] += T;
             t.v[2] += T1;
@@ -638,19 +535,14 @@ __global__ __launch_bounds__(kBlock) void thinfilm_kernel(const FilmArgs fa)
             t.v[6] += D;
             t.v[7] = fmax(t.v[7], D);
         }
-        if (a.rows && r < a.n_rays) {
-            double *row = a.rows + (size_t)blockIdx.y * a.n_rows * a.ld_rows + (r - a.row_ray0);
-            row[0] = ok ? T : nan;
-            row[a.ld_rows] = ok ? T1 : nan;
-            row[2 * a.ld_rows] = ok ? T2 : nan;
-            row[3 * a.ld_rows] = ok ? D : nan;
-            if (a.n_rows == 16) {
-                const double f[12] = {E1.re.x, E1.re.y, E1.re.z, E2.re.x, E2.re.y, E2.re.z,
-                                      E1.im.x, E1.im.y, E1.im.z, E2.im.x, E2.im.y, E2.im.z};
-#pragma unroll
-                for (int c = 0; c < 12; ++c)
-                    row[(4 + c) * a.ld_rows] = ok ? f[c] : nan;
-            }
+        if (a.rows && y.r < a.n_rays) {
+            double *row = a.rows + (size_t)blockIdx.y * a.n_rows * a.ld_rows + (y.r - a.row_ray0);
+            row[0] = y.ok ? T : nan;
+            row[a.ld_rows] = y.ok ? T1 : nan;
+            row[2 * a.ld_rows] = y.ok ? T2 : nan;
+            row[3 * a.ld_rows] = y.ok ? D : nan;
+            if (a.n_rows == (kFilm ? 16 : 10))
+                store_fields(row, a.ld_rows, 4, y.ok, y.E1, y.E2);
         }
     }
     if (out) {
@@ -726,7 +618,7 @@ int check_layer_index(const char *kE, const Film *film, int32_t n_layers, int32_
     return 0;
 }
 
-// both entries: rox_surface_transmission (film == nullptr, fresnel_kernel) and rox_surface_thinfilm
+// both entries: rox_surface_transmission (film == nullptr, the real walk) and rox_surface_thinfilm
 int tx_entry(const char *kE, const Film *film, rox_system *sys, uint32_t trace_flags, uint32_t tx_flags,
              int32_t n_items, const rox_out *outs, int64_t n_rays, const int32_t *wvl_idx, int32_t n_coat,
              const int32_t *coat_kind, const double *coat_value, double *rows, int64_t ld_rows, rox_tx_surface *surf,
@@ -964,11 +856,13 @@ int tx_entry(const char *kE, const Film *film, rox_system *sys, uint32_t trace_f
             a.ld_rows = rows_host ? range_rays : ld_rows;
             a.row_ray0 = rows_host ? first : 0;
             if (film) {
-                fa.t = a;
+                static_cast<TxArgs &>(fa) = a;
                 fa.wvl = film->wvl ? (const double *)(d_tab + o_wv) + i0 : nullptr;
-                hipLaunchKernelGGL(thinfilm_kernel, dim3((unsigned)nt, (unsigned)c), dim3(kBlock), 0, st, fa);
+                hipLaunchKernelGGL((fresnel_kernel<C3, FilmArgs>), dim3((unsigned)nt, (unsigned)c), dim3(kBlock), 0,
+                                   st, fa);
             } else {
-                hipLaunchKernelGGL(fresnel_kernel, dim3((unsigned)nt, (unsigned)c), dim3(kBlock), 0, st, a);
+                hipLaunchKernelGGL((fresnel_kernel<V3, TxArgs>), dim3((unsigned)nt, (unsigned)c), dim3(kBlock), 0, st,
+                                   a);
             }
             HIP_TRY(hipGetLastError());
             // this range's rows, copied before the next launch reuses the scratch

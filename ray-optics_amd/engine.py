@@ -1249,6 +1249,40 @@ class TraceEngine:
                                                    p_maps, self._stream()), 'rox_surface_footprints')
         return rec, maps
 
+    def _transmission(self, what, entry, field_rows, results, trace_flags, wvl_idxs, coat_kind, coat_value,
+                      want_rows, fields, on_device, tables=None):
+        """the body of surface_transmission and surface_thinfilm: ``entry`` is the C entry
+        rox_<what>, ``field_rows`` its n_rows with ``fields``.  ``tables(n_items, N, ck)`` checks
+        what the entry takes besides and returns those arrays (None for a null pointer) as two
+        tuples: the arguments that follow wvl_idx, and those that follow coat_value."""
+        t = self.torch
+        results, n_items, n_seg, R, outs = self._packets(results, trace_flags, what)
+        wi = np.ascontiguousarray(np.asarray(wvl_idxs, dtype=np.int32).reshape(-1))
+        if wi.shape[0] != n_items:
+            raise EngineError(f'{what}: {wi.shape[0]} wvl_idxs for {n_items} items')
+        N = self.table.n_ifcs
+        if (coat_kind is None) != (coat_value is None):
+            raise EngineError(f'{what}: coat_kind and coat_value go together')
+        ck = cv = None
+        if coat_kind is not None:
+            ck = np.ascontiguousarray(np.asarray(coat_kind, dtype=np.int32).reshape(-1))
+            cv = np.ascontiguousarray(np.asarray(coat_value, dtype=np.float64))
+            if ck.shape[0] != N or cv.shape != (N, 2):
+                raise EngineError(f'{what}: coat_kind [{ck.shape[0]}] and coat_value '
+                                  f'{list(cv.shape)} are not [{N}] and [{N}, 2], one entry per interface')
+        after_wvl, after_coat = tables(n_items, N, ck) if tables else ((), ())
+        n_rows = field_rows if fields else 4
+        rows, p_rows = self._out(on_device, (n_items, n_rows, R), np.float64, t.float64) if want_rows \
+            else (None, None)
+        surf, p_surf = self._records_out(on_device, (n_items, n_seg), TX_SURFACE_DTYPE)
+        item, p_item = self._records_out(on_device, (n_items,), TX_ITEM_DTYPE)
+        ptr = lambda v: v.ctypes.data if v is not None and v.size else None     # noqa: E731
+        with t.cuda.device(self.device):
+            _check(entry(self._handle, int(trace_flags), abi.TX_FIELDS if fields else 0, n_items, outs, R,
+                         wi.ctypes.data, *map(ptr, after_wvl), N if ck is not None else 0, ptr(ck), ptr(cv),
+                         *map(ptr, after_coat), p_rows, R, p_surf, p_item, self._stream()), 'rox_' + what)
+        return rows, surf, item
+
     @_in_flight
     def surface_transmission(self, results, trace_flags, wvl_idxs, coat_kind=None, coat_value=None, want_rows=True,
                              fields=False, on_device=False):
@@ -1262,33 +1296,8 @@ class TraceEngine:
         without ``want_rows``); a TX_SURFACE_DTYPE array [n_items, n_seg]; a TX_ITEM_DTYPE array
         [n_items] -- NumPy, or with ``on_device`` torch tensors (the records as uint8 [..., 64]
         and [n_items, 72]; ``tx_view`` reads them on the host)."""
-        t = self.torch
-        results, n_items, n_seg, R, outs = self._packets(results, trace_flags, 'surface_transmission')
-        wi = np.ascontiguousarray(np.asarray(wvl_idxs, dtype=np.int32).reshape(-1))
-        if wi.shape[0] != n_items:
-            raise EngineError(f'surface_transmission: {wi.shape[0]} wvl_idxs for {n_items} items')
-        N = self.table.n_ifcs
-        if (coat_kind is None) != (coat_value is None):
-            raise EngineError('surface_transmission: coat_kind and coat_value go together')
-        ck = cv = None
-        if coat_kind is not None:
-            ck = np.ascontiguousarray(np.asarray(coat_kind, dtype=np.int32).reshape(-1))
-            cv = np.ascontiguousarray(np.asarray(coat_value, dtype=np.float64))
-            if ck.shape[0] != N or cv.shape != (N, 2):
-                raise EngineError(f'surface_transmission: coat_kind [{ck.shape[0]}] and coat_value '
-                                  f'{list(cv.shape)} are not [{N}] and [{N}, 2], one entry per interface')
-        n_rows = 10 if fields else 4
-        rows, p_rows = self._out(on_device, (n_items, n_rows, R), np.float64, t.float64) if want_rows \
-            else (None, None)
-        surf, p_surf = self._records_out(on_device, (n_items, n_seg), TX_SURFACE_DTYPE)
-        item, p_item = self._records_out(on_device, (n_items,), TX_ITEM_DTYPE)
-        with t.cuda.device(self.device):
-            _check(self.lib.rox_surface_transmission(self._handle, int(trace_flags), abi.TX_FIELDS if fields else 0,
-                                                     n_items, outs, R, wi.ctypes.data, N if ck is not None else 0,
-                                                     ck.ctypes.data if ck is not None else None,
-                                                     cv.ctypes.data if cv is not None else None, p_rows, R, p_surf,
-                                                     p_item, self._stream()), 'rox_surface_transmission')
-        return rows, surf, item
+        return self._transmission('surface_transmission', self.lib.rox_surface_transmission, 10, results,
+                                  trace_flags, wvl_idxs, coat_kind, coat_value, want_rows, fields, on_device)
 
     @_in_flight
     def surface_thinfilm(self, results, trace_flags, wvl_idxs, wvls_nm=None, coat_kind=None, coat_value=None,
@@ -1301,61 +1310,40 @@ class TraceEngine:
         index table) and ``sub_index`` ([n_wvls, n_ifcs, 2], the metal behind a mirror's stack) as
         coatings.stack_tables builds them.  Returns ``(rows, surf, item)`` as surface_transmission
         does; with ``fields`` n_rows = 16: re(E1), re(E2), im(E1), im(E2)."""
-        t = self.torch
         what = 'surface_thinfilm'
-        results, n_items, n_seg, R, outs = self._packets(results, trace_flags, what)
-        wi = np.ascontiguousarray(np.asarray(wvl_idxs, dtype=np.int32).reshape(-1))
-        if wi.shape[0] != n_items:
-            raise EngineError(f'{what}: {wi.shape[0]} wvl_idxs for {n_items} items')
-        N, W = self.table.n_ifcs, len(self.table.wvls)
-        if (coat_kind is None) != (coat_value is None):
-            raise EngineError(f'{what}: coat_kind and coat_value go together')
-        ck = cv = wv = sf = lt = li = sb = None
-        if coat_kind is not None:
-            ck = np.ascontiguousarray(np.asarray(coat_kind, dtype=np.int32).reshape(-1))
-            cv = np.ascontiguousarray(np.asarray(coat_value, dtype=np.float64))
-            if ck.shape[0] != N or cv.shape != (N, 2):
-                raise EngineError(f'{what}: coat_kind [{ck.shape[0]}] and coat_value '
-                                  f'{list(cv.shape)} are not [{N}] and [{N}, 2], one entry per interface')
-        if wvls_nm is not None:
-            wv = np.ascontiguousarray(np.asarray(wvls_nm, dtype=np.float64).reshape(-1))
-            if wv.shape[0] != n_items:
-                raise EngineError(f'{what}: {wv.shape[0]} wvls_nm for {n_items} items')
-        if stack_first is not None:
-            sf = np.ascontiguousarray(np.asarray(stack_first, dtype=np.int32).reshape(-1))
-            if ck is None or sf.shape[0] != N + 1:
-                raise EngineError(f'{what}: stack_first [{sf.shape[0]}] is not [{N + 1}] beside coat_kind')
-            L = int(sf[-1])
-            lt = np.ascontiguousarray(np.asarray(layer_thickness if layer_thickness is not None else [],
-                                                 dtype=np.float64).reshape(-1))
-            li = np.ascontiguousarray(np.asarray(layer_index if layer_index is not None else np.zeros((W, 0, 2)),
-                                                 dtype=np.float64))
-            if lt.shape[0] != L or li.shape != (W, L, 2):
-                raise EngineError(f'{what}: layer_thickness [{lt.shape[0]}] and layer_index {list(li.shape)} are not '
-                                  f'[{L}] and [{W}, {L}, 2], the layers of stack_first and the wavelengths of the '
-                                  f'table')
-            if L > 0 and wv is None:
-                raise EngineError(f'{what}: layers need wvls_nm')
-        elif layer_thickness is not None or layer_index is not None:
-            raise EngineError(f'{what}: layer_thickness and layer_index go with stack_first')
-        if sub_index is not None:
-            sb = np.ascontiguousarray(np.asarray(sub_index, dtype=np.float64))
-            if sb.shape != (W, N, 2):
-                raise EngineError(f'{what}: sub_index {list(sb.shape)} is not [{W}, {N}, 2]')
-        n_rows = 16 if fields else 4
-        rows, p_rows = self._out(on_device, (n_items, n_rows, R), np.float64, t.float64) if want_rows \
-            else (None, None)
-        surf, p_surf = self._records_out(on_device, (n_items, n_seg), TX_SURFACE_DTYPE)
-        item, p_item = self._records_out(on_device, (n_items,), TX_ITEM_DTYPE)
-        ptr = lambda v: v.ctypes.data if v is not None and v.size else None     # noqa: E731
-        with t.cuda.device(self.device):
-            _check(self.lib.rox_surface_thinfilm(self._handle, int(trace_flags), abi.TX_FIELDS if fields else 0,
-                                                 n_items, outs, R, wi.ctypes.data, ptr(wv),
-                                                 N if ck is not None else 0, ptr(ck), ptr(cv),
-                                                 sf.ctypes.data if sf is not None else None, ptr(lt), ptr(li),
-                                                 ptr(sb), p_rows, R, p_surf, p_item, self._stream()),
-                   'rox_surface_thinfilm')
-        return rows, surf, item
+
+        def tables(n_items, N, ck):
+            W = len(self.table.wvls)
+            wv = sf = lt = li = sb = None
+            if wvls_nm is not None:
+                wv = np.ascontiguousarray(np.asarray(wvls_nm, dtype=np.float64).reshape(-1))
+                if wv.shape[0] != n_items:
+                    raise EngineError(f'{what}: {wv.shape[0]} wvls_nm for {n_items} items')
+            if stack_first is not None:
+                sf = np.ascontiguousarray(np.asarray(stack_first, dtype=np.int32).reshape(-1))
+                if ck is None or sf.shape[0] != N + 1:
+                    raise EngineError(f'{what}: stack_first [{sf.shape[0]}] is not [{N + 1}] beside coat_kind')
+                L = int(sf[-1])
+                lt = np.ascontiguousarray(np.asarray(layer_thickness if layer_thickness is not None else [],
+                                                     dtype=np.float64).reshape(-1))
+                li = np.ascontiguousarray(np.asarray(layer_index if layer_index is not None
+                                                     else np.zeros((W, 0, 2)), dtype=np.float64))
+                if lt.shape[0] != L or li.shape != (W, L, 2):
+                    raise EngineError(f'{what}: layer_thickness [{lt.shape[0]}] and layer_index {list(li.shape)} '
+                                      f'are not [{L}] and [{W}, {L}, 2], the layers of stack_first and the '
+                                      f'wavelengths of the table')
+                if L > 0 and wv is None:
+                    raise EngineError(f'{what}: layers need wvls_nm')
+            elif layer_thickness is not None or layer_index is not None:
+                raise EngineError(f'{what}: layer_thickness and layer_index go with stack_first')
+            if sub_index is not None:
+                sb = np.ascontiguousarray(np.asarray(sub_index, dtype=np.float64))
+                if sb.shape != (W, N, 2):
+                    raise EngineError(f'{what}: sub_index {list(sb.shape)} is not [{W}, {N}, 2]')
+            return (wv,), (sf, lt, li, sb)
+
+        return self._transmission(what, self.lib.rox_surface_thinfilm, 16, results, trace_flags, wvl_idxs, coat_kind,
+                                  coat_value, want_rows, fields, on_device, tables)
 
     @_in_flight
     def focus_psf_ee(self, psf, pitch, centers, radii, want_centroid=True):

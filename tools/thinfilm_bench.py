@@ -27,7 +27,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
 
 N_ITEMS = 9
-# one layer of one ray in thinfilm_kernel (csrc/fresnel.hip), a division, a square root, sincos and
+# one layer of one ray in fresnel_kernel<C3, FilmArgs> (csrc/fresnel.hip), a division, a square root, sincos and
 # exp counted as one operation each: g = sqrt(N^2 - a2) 10, 1/g 5, the phase 2, sincos 2, exp and
 # the scaled cosh / sinh 6, cs and sn 5, the sum of Im delta 1, the p admittance and its reciprocal
 # 12, and two characteristic-matrix updates of six complex products and two complex sums each, 80
