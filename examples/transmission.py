@@ -5,7 +5,8 @@ rox_surface_transmission over the packets where they are (analyses.transmission)
 transmission of every field and wavelength for bare surfaces and with a 99.5 % coating on every
 glass-air surface, the surfaces that cost the most, the apodization of the pupil, the
 diattenuation, and each field's transmission relative to the axial one with vignetting counted
-(not radiometric relative illumination: no pupil-area, cos^4 or distortion term).  Stand-alone:
+(not radiometric relative illumination: no pupil-area, cos^4 or distortion term -- that is
+examples/relative_illumination.py).  Stand-alone:
 the table and the field constants come from ray-optics_amd/data/dblgauss_c2.json; behind
 ray-optics the call is the same with the live OpticalModel.
 

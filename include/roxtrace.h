@@ -1021,6 +1021,60 @@ int rox_surface_thinfilm(rox_system *sys, uint32_t trace_flags, uint32_t tx_flag
                          const double *layer_index, const double *sub_index, double *rows,
                          int64_t ld_rows, rox_tx_surface *surf, rox_tx_item *item, void *stream);
 
+/* The projected solid angle of the image-space bundle: the signed area the num x num pupil grid
+ * of a finished launch covers in the plane of the direction cosines (L, M) it arrives with --
+ * for a Lambertian object of uniform radiance the irradiance at the image point is proportional
+ * to the integral of T dL dM over that area (conservation of basic radiance; Rimmer, "Relative
+ * illumination calculations", Proc. SPIE 655, 1986), which contains cos^4, pupil aberration,
+ * distortion and vignetting.  One pass over rows that are already in HBM; no system is needed.
+ *   outs   HOST [n_items] of DEVICE pointers: the rox_out of each ROX_GRID_PRODUCT launch of
+ *          num x num rays, all rows traced: ray r = i*num + j, x_i outer, y_j inner.  seg, status
+ *          and ld are read.  L of ray r is seg[(dir_row + 0)*ld + r], M is seg[(dir_row + 1)*ld + r]:
+ *          dir_row = 3 for ROX_OUT_LAST, (n_seg - 1)*10 + 3 for ROX_OUT_FULL (the image slot's d.x
+ *          and d.y, in the image interface's frame).  A ray counts iff its status is ROX_OK; the
+ *          rows of any other ray are never read.
+ *   weight optional DEVICE: ray r of item i has weight weight[i*weight_stride + r], read for
+ *          counted rays only (rox_surface_transmission's rows with weight_stride =
+ *          n_rows*ld_rows: row 0, T).  NULL: every weight is 1.
+ *   item   optional, host or device [n_items] rox_sa_item.
+ *   cells  optional, host or device [n_items][num-1][num-1]: the signed, unweighted area of
+ *          every cell.
+ * Arithmetic, in operation order (IEEE double, no FMA: every step is one NumPy float64
+ * operation).  Cell (i, j) has the corners a = (i, j), b = (i+1, j), c = (i+1, j+1), d = (i, j+1)
+ * and k counted corners.
+ *   k = 4  area = ((Lc - La)*(Md - Mb) - (Ld - Lb)*(Mc - Ma)) * 0.5
+ *          weight = ((wa + wb) + (wc + wd)) * 0.25
+ *   k = 3  (p, q, r) = the counted corners in the cyclic order a, b, c, d, the missing one skipped:
+ *          area = ((Lq - Lp)*(Mr - Mp) - (Lr - Lp)*(Mq - Mp)) * 0.5
+ *          weight = ((wp + wq) + wr) / 3.0
+ *   k < 3  area = 0.
+ * Every ray and every cell is counted exactly once.  Minima and maxima are exact selections; the
+ * sums are per-wave partial sums merged in a fixed order by a finishing kernel (no
+ * floating-point atomics): identical calls, host and device destinations, and one call over n
+ * items against n calls over one item each give the same bits.
+ * item and cells may not both be NULL.  n_items in [1, ROX_MAX_FOCUS_ITEMS], num in
+ * [2, ROX_MAX_SA_NUM], ld >= num*num, dir_row >= 0, weight_stride >= num*num with weight.
+ * Argument errors return ROX_E_ARG naming the parameter and item before anything is enqueued and
+ * leave the outputs untouched.  Scratch per launch is 32 MiB or, where that is more, what one
+ * item needs (120 bytes of partial records per wave -- 4 MB at num = 16384 -- plus, for cells
+ * bound for host memory, the item's cells); larger jobs run as consecutive launches over fewer
+ * items with the same results.  Asynchronous on `stream` unless an output is host memory.   */
+#define ROX_MAX_SA_NUM 16384
+typedef struct rox_sa_item {
+    int64_t n_ok;            /* rays counted (status ROX_OK)                                  */
+    int64_t n_cells[5];      /* the (num-1)^2 cells by their number k of counted corners      */
+    double a_full, a_tri;    /* the signed sums of the k = 4 and of the k = 3 areas           */
+    double a_abs;            /* sum of |area| over both: > |a_full + a_tri| where the map folds */
+    double aw_full, aw_tri;  /* sums of area*weight; without weight a_full and a_tri bit for bit */
+    double l_sum, m_sum;     /* sums of L and of M over the counted rays                      */
+    double l_min, l_max, m_min, m_max;
+    double r2_max;           /* max of L*L + M*M (two products, one sum): an exact selection  */
+} rox_sa_item;               /* 144 bytes; l_min .. r2_max are NaN where nothing counted, the
+                                sums are then 0                                               */
+int rox_projected_solid_angle(int32_t n_items, int32_t num, const rox_out *outs, int32_t dir_row,
+                              const double *weight, int64_t weight_stride, rox_sa_item *item,
+                              double *cells, void *stream);
+
 /* chief-ray aiming ------------------------------------------------------- */
 /* One problem per (field, wavelength): trace.iterate_ray
  * (rayoptics/raytr/trace.py:313-415) as trace.aim_chief_ray calls it

@@ -230,6 +230,17 @@ COAT_STACK = 3              # rox_surface_thinfilm only
 MAX_COAT_LAYERS, MAX_COAT_LAYERS_TOTAL = 64, 4096
 
 
+class SaItem(C.Structure):
+    """rox_sa_item: the area one item's pupil grid covers in image-space direction cosines"""
+    _fields_ = [('n_ok', C.c_int64), ('n_cells', C.c_int64 * 5), ('a_full', C.c_double), ('a_tri', C.c_double),
+                ('a_abs', C.c_double), ('aw_full', C.c_double), ('aw_tri', C.c_double), ('l_sum', C.c_double),
+                ('m_sum', C.c_double), ('l_min', C.c_double), ('l_max', C.c_double), ('m_min', C.c_double),
+                ('m_max', C.c_double), ('r2_max', C.c_double)]
+
+
+MAX_SA_NUM = 16384          # include/roxtrace.h ROX_MAX_SA_NUM
+
+
 class Vig(C.Structure):
     _fields_ = [('fld', Field), ('start_dir', C.c_double * 2), ('unit_dir', C.c_double * 2),
                 ('xy', C.c_int32), ('wvl_idx', C.c_int32), ('stop_surf', C.c_int32),
@@ -260,6 +271,7 @@ assert C.sizeof(ZernikeStats) == 56
 assert C.sizeof(Footprint) == 144
 assert C.sizeof(TxSurface) == 64
 assert C.sizeof(TxItem) == 72
+assert C.sizeof(SaItem) == 144
 
 # every symbol include/roxtrace.h declares (checked by tests/test_abi.py) ...
 EXPORTS = ('rox_abi_version', 'rox_device_count', 'rox_set_device',
@@ -272,7 +284,7 @@ EXPORTS = ('rox_abi_version', 'rox_device_count', 'rox_set_device',
            'rox_spot_stats', 'rox_trace_through_focus', 'rox_trace_through_focus_grids',
            'rox_focus_psf', 'rox_focus_mtf', 'rox_focus_ee', 'rox_focus_gmtf', 'rox_focus_psf_ee',
            'rox_focus_zernike', 'rox_surface_footprints', 'rox_surface_transmission',
-           'rox_surface_thinfilm')
+           'rox_surface_thinfilm', 'rox_projected_solid_angle')
 # ... and the measurement / self-test helpers of include/roxtrace_diag.h
 DIAG_EXPORTS = ('rox_time_pupil_grid', 'rox_selftest_fp64', 'rox_diag_pack_launches')
 
@@ -355,6 +367,8 @@ def declare(lib):
     lib.rox_surface_thinfilm.restype = C.c_int
     lib.rox_surface_thinfilm.argtypes = [vp, C.c_uint32, C.c_uint32, i32, P(Out), i64, vp, vp, i32, vp, vp, vp, vp, vp,
                                          vp, vp, i64, vp, vp, vp]
+    lib.rox_projected_solid_angle.restype = C.c_int
+    lib.rox_projected_solid_angle.argtypes = [i32, i32, P(Out), i32, vp, i64, vp, vp, vp]
     lib.rox_time_pupil_grid.restype = C.c_int
     lib.rox_time_pupil_grid.argtypes = [vp, P(Field), P(Grid), i32, P(Opts),
                                         P(Out), vp, i32, P(dbl)]

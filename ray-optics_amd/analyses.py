@@ -20,6 +20,8 @@
                         polychromatic, from the PSFs in HBM (rox_focus_mtf)
   through_focus_gmtf (new) the geometric MTF and line spread through focus along any
                         direction, from the rays in HBM (rox_focus_gmtf)
+  relative_illumination (new) radiometric relative illumination from the image-space solid
+                        angle of each field's pupil grid (rox_projected_solid_angle)
 """
 import numpy as np
 
@@ -1070,10 +1072,11 @@ class BeamFootprints:
         return out
 
 
-def _packet_items(opt_model, flds, wvls, num_rays, check_apertures, what):
+def _packet_items(opt_model, flds, wvls, num_rays, check_apertures, what, out_mode=abi.OUT_FULL):
     """every (field, wavelength) item of a packet analysis, field-major, each set up for a FULL
-    launch over the field's vignetted pupil; defaults as _map_spec, ref_wvl the first wavelength
-    given -> (engine, flds, wvls, spectral_wts, fields, wavelength indices, options, trace flags)"""
+    (or ``out_mode``) launch over the field's vignetted pupil; defaults as _map_spec, ref_wvl the
+    first wavelength given -> (engine, flds, wvls, spectral_wts, fields, wavelength indices,
+    options, trace flags)"""
     if num_rays < 1 or num_rays * num_rays > abi.MAX_FOOTPRINT_RAYS:
         raise ValueError(f'{what}: num_rays {num_rays} outside [1, 16384]')
     flds, wvls, _fw, spectral_wts, _ref = _map_spec(opt_model, flds, wvls, None, None,
@@ -1083,7 +1086,7 @@ def _packet_items(opt_model, flds, wvls, num_rays, check_apertures, what):
     for fld in flds:
         for wvl in wvls:
             kw = dict(check_apertures=bool(check_apertures), apply_vignetting=True)
-            eng, f, wi, opts = _launch_setup(opt_model, fld, wvl, kw, abi.OUT_FULL)
+            eng, f, wi, opts = _launch_setup(opt_model, fld, wvl, kw, out_mode)
             fs.append(f)
             wis.append(wi)
             opts_list.append(opts)
@@ -1166,7 +1169,7 @@ class Transmission:
                       between the two sides of an axis, its two halves are sampled at different
                       densities; the box's area then weights their mean.)  It is not radiometric
                       relative illumination: no projected pupil area, no cos^4 and no distortion
-                      term is applied.
+                      term is applied -- that is :func:`relative_illumination`.
     ``surface_T``     [F, W, n_seg] the mean (Ts + Tp)/2 of each slot (1 at the object, the image
                       and every interface counted as ideal)
     ``surface_loss``  the slots ranked by their loss 1 - mean (Ts + Tp)/2 over every item's
@@ -1301,7 +1304,8 @@ def transmission(opt_model, flds=None, wvls=None, num_rays=64, coatings=None, ch
     ``relative`` of the result is relative transmission including vignetting -- poly_throughput
     times the share of the unit pupil box the field's vignetting factors leave its grid, over that
     of field ``ref_field``.  It is NOT radiometric relative illumination: no projected
-    pupil area, cos^4 or distortion term is applied; that is out of scope here.  Neither are
+    pupil area, cos^4 or distortion term is applied; :func:`relative_illumination` answers that,
+    from the image-space solid angle of the same grids.  Out of scope here are
     absorbing glasses (bulk absorption) and diffraction efficiencies: thin lenses and phase
     elements are counted as ideal, and so is a mirror without a Coating.
     Returns :class:`Transmission`."""
@@ -1334,6 +1338,155 @@ def transmission(opt_model, flds=None, wvls=None, num_rays=64, coatings=None, ch
     n_seg = surf.shape[1]
     return Transmission(item.reshape(F, W), surf.reshape(F, W, n_seg), eng.slot_interfaces(flags), spectral_wts,
                         ref_field, rows, num_rays, results if keep_packets else None, box)
+
+
+# ---- radiometric relative illumination from the image-space solid angle -------------
+class RelativeIllumination:
+    """what :func:`relative_illumination` returns.
+
+    ``items``         [F, W] rox_sa_item records (engine.SA_ITEM_DTYPE)
+    ``omega_raw``     [F, W] |A|, A = a_full + a_tri: the projected solid angle of the image-space
+                      bundle as the cells with three or four rays that arrived add up to
+    ``omega``         [F, W] |A + c|, the boundary-corrected projected solid angle: a cell with k of
+                      its corners inside the beam is on average k/4 inside it, and A counted such
+                      cells as 0, 0, 1/2 or 1, so c = cell * (n1/4 + n2/2 + n3/4) with cell =
+                      a_full / n4 the mean full cell and nk = n_cells[k]
+    ``boundary_share``  [F, W] c / (A + c): what the correction contributes -- the handle on
+                      convergence, which is first-order in 1 / num_rays
+    ``ri``            [F, W] omega / omega[ref_field], per wavelength
+    ``poly_omega``, ``poly_ri``  [F] omega merged over the wavelengths with the spectral weights,
+                      and its ratio to that of field ``ref_field``
+    ``omega_t``, ``ri_t``, ``poly_omega_t``, ``poly_ri_t``  the same of the integral of T dL dM
+                      (aw_full + aw_tri, the correction scaled by its ratio to A); None without
+                      ``coatings``
+    ``fno_eff``       [F, W] 1 / (2 sqrt(omega / pi)), the effective image-space F-number
+    ``chief_dir``     [F, W, 2] (l_sum, m_sum) / n_ok, the mean direction of arrival
+    ``na_max``        [F, W] sqrt(r2_max), the largest sine of arrival
+    ``folded``        [F, W] a_abs exceeds |A| by more than (n3 + n4) * 2^-52 * a_abs: the pupil
+                      map folds over and the signed area under-counts
+    ``cell_maps``     [F, W, num_rays - 1, num_rays - 1] the cells' signed areas (x the first
+                      axis), or None
+    ``flds``          the fields, those a ``sweep`` made included
+    An item without a ray is NaN throughout; so is a ratio to an ``omega`` of 0 (an afocal image
+    space)."""
+
+    def __init__(self, items, spectral_wts, ref_field=0, weighted=False, cell_maps=None, flds=None):
+        self.items = items
+        self.spectral_wts = np.asarray(spectral_wts, dtype=np.float64)
+        self.ref_field = int(ref_field)
+        self.cell_maps = cell_maps
+        self.flds = flds
+        F, _W = items.shape
+        if not 0 <= self.ref_field < F:
+            raise ValueError(f'RelativeIllumination: ref_field {ref_field} outside [0, {F})')
+        nc = items['n_cells'].astype(np.float64)
+        some = items['n_ok'] > 0
+        with np.errstate(divide='ignore', invalid='ignore'):
+            A = items['a_full'] + items['a_tri']
+            cell = np.where(nc[..., 4] > 0, items['a_full'] / np.where(nc[..., 4] > 0, nc[..., 4], 1.0), 0.0)
+            corr = cell * (nc[..., 1] * 0.25 + nc[..., 2] * 0.5 + nc[..., 3] * 0.25)
+            self.omega_raw = np.where(some, np.abs(A), np.nan)
+            self.omega = np.where(some, np.abs(A + corr), np.nan)
+            self.boundary_share = np.where(some, corr / (A + corr), np.nan)
+            self.ri, self.poly_omega, self.poly_ri = self._ratios(self.omega)
+            self.omega_t = self.ri_t = self.poly_omega_t = self.poly_ri_t = None
+            if weighted:
+                Aw = items['aw_full'] + items['aw_tri']
+                self.omega_t = np.where(some, np.abs(Aw + corr * (Aw / A)), np.nan)
+                self.ri_t, self.poly_omega_t, self.poly_ri_t = self._ratios(self.omega_t)
+            self.fno_eff = 1.0 / (2.0 * np.sqrt(self.omega / np.pi))
+            n = np.where(some, items['n_ok'], 1).astype(np.float64)
+            self.chief_dir = np.where(some[..., None], np.stack([items['l_sum'] / n, items['m_sum'] / n], axis=-1),
+                                      np.nan)
+            self.na_max = np.sqrt(items['r2_max'])
+            self.folded = items['a_abs'] - np.abs(A) > (nc[..., 3] + nc[..., 4]) * 2.0 ** -52 * items['a_abs']
+
+    def _ratios(self, omega):
+        """(omega / omega[ref_field] per wavelength, omega merged over the wavelengths, its ratio)"""
+        poly = _weighted_mean(omega, self.spectral_wts)
+        return omega / omega[self.ref_field][None, :], poly, poly / poly[self.ref_field]
+
+
+def _field_sweep(opt_model, n):
+    """``n`` fields evenly spaced from the axis to the model's outermost field along that field's
+    (x, y) direction: copies of it without vignetting factors, aimed in one batch"""
+    import copy
+    from .trace import aim_chief_rays
+    from .workloads import TableModel
+    n = int(n)
+    if n < 2:
+        raise ValueError(f'relative_illumination: sweep {n} < 2')
+    if isinstance(opt_model, TableModel):
+        raise ValueError('relative_illumination: sweep needs a live model: a TableModel carries prebuilt fields only')
+    fov = opt_model['osp']['fov']
+    _value, k = fov.max_field()
+    outer = fov.fields[k]
+    flds = []
+    for t in np.linspace(0.0, 1.0, n):
+        f = copy.copy(outer)
+        f.x, f.y = float(outer.x * t), float(outer.y * t)
+        f.vux = f.vuy = f.vlx = f.vly = 0.0
+        f.chief_ray = f.ref_sphere = None
+        flds.append(f)
+    for f, aim in zip(flds, aim_chief_rays(opt_model, flds)):
+        f.aim_info = aim
+    return flds
+
+
+def relative_illumination(opt_model, flds=None, wvls=None, num_rays=128, coatings=None, check_apertures=True,
+                          ref_field=0, sweep=None, cell_maps=False):
+    """Radiometric relative illumination, on the device: how bright each field's image point is
+    compared with field ``ref_field``'s.  For a Lambertian object of uniform radiance the
+    irradiance at an image point is proportional to the integral of T dL dM over the direction
+    cosines (L, M) with which the bundle arrives (conservation of basic radiance; Rimmer, "Relative
+    illumination calculations", 1986): cos^4, pupil aberration, distortion and vignetting are all
+    in that one area, which rox_projected_solid_angle takes from the ``num_rays`` x ``num_rays``
+    pupil grid of every (field, wavelength) where its rows are (include/roxtrace.h states the
+    arithmetic).  Items and defaults as :func:`transmission`: field-major, the unit pupil box with
+    apply_vignetting.  Without ``coatings`` one OUT_LAST launch and one call (T = 1: the geometric
+    answer).  With ``coatings`` -- anything :func:`transmission` accepts, a Coating included, or
+    'bare' for the Fresnel losses of uncoated surfaces -- the FULL launch, the transmission (or
+    thin-film) call with its rows left on the device, and the call with row 0 (T) as the weight.
+
+    ``sweep`` = n replaces ``flds`` by n fields evenly spaced from the axis to the outermost field
+    along its (x, y) direction, without vignetting factors (the clear apertures do the
+    vignetting) and aimed in one batch: the RI-against-field curve.  A live model only.
+
+    Limits.  The object is taken as Lambertian.  (L, M) are direction cosines in the image
+    interface's own frame: for a curved or tilted image this is the irradiance on that frame's
+    z-plane.  An afocal image space has omega = 0 and its ratios are NaN.  The estimate converges
+    first-order in 1 / num_rays (``boundary_share``).  Returns :class:`RelativeIllumination`."""
+    num_rays = int(num_rays)
+    if not 2 <= num_rays <= abi.MAX_SA_NUM:
+        raise ValueError(f'relative_illumination: num_rays {num_rays} outside [2, {abi.MAX_SA_NUM}]')
+    if sweep is not None:
+        flds = _field_sweep(opt_model, sweep)
+    weighted = coatings is not None
+    eng, flds, wvls, spectral_wts, fs, wis, opts_list, flags = _packet_items(
+        opt_model, flds, wvls, num_rays, check_apertures, 'relative_illumination',
+        abi.OUT_FULL if weighted else abi.OUT_LAST)
+    F, W = len(flds), len(wvls)
+    if not 0 <= int(ref_field) < F:
+        raise ValueError(f'relative_illumination: ref_field {ref_field} outside [0, {F})')
+    rows = None
+    if weighted:
+        bare = isinstance(coatings, str) and coatings == 'bare'
+        kind, value, stacks = _coating_tables(eng.table, None if bare else coatings)
+        film = stack_tables(eng.table, stacks, 'relative_illumination') if stacks else None
+    results = _trace_packets(eng, fs, wis, opts_list, num_rays)
+    if weighted and film is None:
+        rows, _surf, _item = eng.surface_transmission(results, flags, wis, coat_kind=kind, coat_value=value,
+                                                      on_device=True)
+    elif weighted:
+        first, thick, index, sub = film
+        rows, _surf, _item = eng.surface_thinfilm(results, flags, wis, [float(eng.table.wvls[w]) for w in wis],
+                                                  coat_kind=kind, coat_value=value, stack_first=first,
+                                                  layer_thickness=thick, layer_index=index, sub_index=sub,
+                                                  on_device=True)
+    items, cells = eng.projected_solid_angle(results, num_rays, weight=rows, weight_row=0, want_cells=bool(cell_maps))
+    if cells is not None:
+        cells = cells.reshape(F, W, num_rays - 1, num_rays - 1)
+    return RelativeIllumination(items.reshape(F, W), spectral_wts, ref_field, weighted, cells, flds)
 
 
 # ---- MTF through focus ----------------------------------------------------------

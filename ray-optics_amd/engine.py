@@ -181,6 +181,13 @@ def tx_view(records, dtype):
     return records_view(records, dtype)
 
 
+# rox_sa_item: what projected_solid_angle returns
+SA_ITEM_DTYPE = np.dtype([('n_ok', np.int64), ('n_cells', np.int64, (5,))] +
+                         [(name, np.float64) for name in ('a_full', 'a_tri', 'a_abs', 'aw_full', 'aw_tri', 'l_sum',
+                                                          'm_sum', 'l_min', 'l_max', 'm_min', 'm_max', 'r2_max')])
+assert SA_ITEM_DTYPE.itemsize == C.sizeof(abi.SaItem)
+
+
 # rox_zernike_stats: what focus_zernike returns
 ZERNIKE_STATS_DTYPE = np.dtype([('n', np.int64), ('n_outside', np.int64), ('rms', np.float64),
                                 ('rms_residual', np.float64), ('pv_residual', np.float64),
@@ -1344,6 +1351,54 @@ class TraceEngine:
 
         return self._transmission(what, self.lib.rox_surface_thinfilm, 16, results, trace_flags, wvl_idxs, coat_kind,
                                   coat_value, want_rows, fields, on_device, tables)
+
+    @_in_flight
+    def projected_solid_angle(self, results, num, weight=None, weight_row=0, want_cells=False, on_device=False):
+        """rox_projected_solid_angle over the finished ``num`` x ``num`` product grids of a
+        trace_pupil_grids call (``results``: its list of DeviceResult, OUT_LAST or OUT_FULL, or a
+        single one, still in HBM): the signed area each grid covers in the direction cosines
+        (L, M) its rays reach the image with, over the rays with status OK.  ``weight``: a
+        contiguous float64 device tensor [n_items, n_rows, R], row ``weight_row`` of which weighs
+        the rays -- what surface_transmission(..., on_device=True) returns as ``rows``, row 0 its
+        T.  Returns ``(items, cells)``: a SA_ITEM_DTYPE array [n_items] and, with ``want_cells``,
+        float64 [n_items, num - 1, num - 1] of the cells' signed areas (else None) -- NumPy, or
+        with ``on_device`` torch tensors (the records as uint8 [n_items, 144]; ``records_view``
+        reads them on the host)."""
+        t = self.torch
+        what = 'projected_solid_angle'
+        results = [results] if isinstance(results, DeviceResult) else list(results)
+        n_items, num = len(results), int(num)
+        if not 1 <= n_items <= abi.MAX_FOCUS_ITEMS:
+            raise EngineError(f'{what}: 1 to {abi.MAX_FOCUS_ITEMS} items, got {n_items}')
+        if not 2 <= num <= abi.MAX_SA_NUM:
+            raise EngineError(f'{what}: num {num} outside [2, {abi.MAX_SA_NUM}]')
+        mode = results[0].out_mode
+        if mode not in (abi.OUT_LAST, abi.OUT_FULL):
+            raise EngineError(f'{what}: reads OUT_LAST or OUT_FULL packets, not out_mode {mode}')
+        n_seg = int(results[0].seg.shape[0]) if mode == abi.OUT_FULL else 1
+        for i, r in enumerate(results):
+            if r.out_mode != mode or int(r.R) != num * num or \
+                    (mode == abi.OUT_FULL and int(r.seg.shape[0]) != n_seg):
+                raise EngineError(f'{what}: item {i} is not a packet of out_mode {mode}, {n_seg} segments and '
+                                  f'{num} x {num} rays')
+        dir_row = (n_seg - 1) * abi.SEG_DOUBLES + 3
+        p_w, stride = None, 0
+        if weight is not None:
+            if not hasattr(weight, 'data_ptr') or weight.dim() != 3 or weight.dtype != t.float64 or \
+                    not weight.is_contiguous() or not weight.is_cuda or int(weight.shape[0]) != n_items or \
+                    int(weight.shape[2]) < num * num or not 0 <= int(weight_row) < int(weight.shape[1]):
+                raise EngineError(f'{what}: weight is a contiguous float64 device tensor [{n_items}, n_rows, '
+                                  f'R >= {num * num}] and weight_row one of its rows')
+            stride = int(weight.shape[1]) * int(weight.shape[2])
+            p_w = weight.data_ptr() + 8 * int(weight_row) * int(weight.shape[2])
+        outs = (abi.Out * n_items)(*[r.out_struct() for r in results])
+        item, p_item = self._records_out(on_device, (n_items,), SA_ITEM_DTYPE)
+        cells, p_cells = self._out(on_device, (n_items, num - 1, num - 1), np.float64, t.float64) \
+            if want_cells else (None, None)
+        with t.cuda.device(self.device):
+            _check(self.lib.rox_projected_solid_angle(n_items, num, outs, dir_row, p_w, stride, p_item, p_cells,
+                                                      self._stream()), 'rox_projected_solid_angle')
+        return item, cells
 
     @_in_flight
     def focus_psf_ee(self, psf, pitch, centers, radii, want_centroid=True):
