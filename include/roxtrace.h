@@ -1075,6 +1075,79 @@ int rox_projected_solid_angle(int32_t n_items, int32_t num, const rox_out *outs,
                               const double *weight, int64_t weight_stride, rox_sa_item *item,
                               double *cells, void *stream);
 
+/* Segment foci: where between two interfaces a weighted bundle is smallest, from the
+ * ROX_OUT_FULL packets of finished launches.  A ray leaves the interface of slot k on a straight
+ * line; per (item, slot) the weighted first and second moments of those lines are reduced where
+ * the packets are (HBM), and the host solves a quadratic (below).  rox_surface_footprints gives
+ * beam sizes on the interfaces only and takes no weights; this entry serves the ghost analysis
+ * (a ghost path is an unfolded table, its rays weighted by rox_surface_thinfilm's row 0).
+ *   trace_flags, n_items, outs, n_rays   as rox_surface_footprints; of a slot's 10 rows p, d and
+ *          dst are read (fail_surf is not).
+ *   weight optional DEVICE: ray r of item i has weight weight[i*weight_stride + r]
+ *          (rox_surface_thinfilm's rows with weight_stride = n_rows*ld_rows: row 0, T).  NULL:
+ *          every weight is 1.  weight_stride >= n_rays.
+ *   window optional HOST pair (hx, hy), both > 0: w_in and n_in are over the rays with
+ *          |ax| <= hx and |ay| <= hy (at the image slot: a detector of 2hx x 2hy centred on the
+ *          axis).  NULL: every counted ray.
+ *   rec    host or device [n_items][n_seg] rox_seg_focus.
+ * Which rays count.  A ray is looked at only if its status is ROX_OK: no row and no weight of any
+ * other ray is read.  Of those, a ray whose weight is not finite or is negative (NaN included;
+ * rox_surface_thinfilm documents a NaN case) adds to n_bad of every slot and to nothing else.
+ * Arithmetic per remaining ray and slot, in operation order (IEEE double, no FMA: every step is
+ * one NumPy float64 operation), from the slot's p = (x, y, z), d = (L, M, N) and dst:
+ *          N == 0: the ray adds to n_flat and to nothing else.  Otherwise it is counted (n):
+ *          mx = L/N, my = M/N; ax = x - z*mx, ay = y - z*my (where the line meets the plane z = 0
+ *          of the slot's frame); z_out = z + dst*N; inside = no window or (|ax| <= hx and
+ *          |ay| <= hy).  a = (ax, ay), b = (mx, my), w = the weight (0 is allowed and counted).
+ * Reduction.  The partition: the rays of an item in tiles of 1024; thread t (0 .. 255) of tile T
+ * holds rays 1024*T + 256*j + t, j = 0 .. 3; wave v of the tile is its threads 64*v .. 64*v + 63.
+ *   A counted ray is a record of its own: W = w, the means its a and b, the moments 0, w_in = w
+ *          if inside else 0.  A thread merges its counted rays in the order of j into an empty
+ *          record (W = 0, w_in = 0, counts 0, ranges +inf / -inf).
+ *   The merge of P with Q, P's rays first (Chan, Golub and LeVeque's pairwise update, weighted):
+ *          Q.W == 0: P keeps its means and moments; P.W == 0: it takes Q's; otherwise
+ *          W = P.W + Q.W, f = Q.W/W, g = P.W*f, da = Q.a - P.a, db = Q.b - P.b,
+ *          mean <- P.mean + d*f, m_aa <- (P.m_aa + Q.m_aa) + (da.x*da.x + da.y*da.y)*g,
+ *          m_ab <- (P.m_ab + Q.m_ab) + (da.x*db.x + da.y*db.y)*g, m_bb likewise.
+ *          w_in <- P.w_in + Q.w_in; counts add; minima and maxima are exact selections.
+ *   A wave: for o = 32, 16, 8, 4, 2, 1 every lane l merges its value (P) with that of lane l ^ o
+ *          (Q); lane 0's value is the wave's partial record.
+ *   An (item, slot): the partial records of waves 0 .. n_waves - 1 (n_waves = 4*ceil(n_rays/1024))
+ *          are merged by a finishing kernel of 256 threads: thread t merges waves t, t + 256, ...
+ *          in that order into an empty record, then for h = 128, 64, .., 1 thread t < h merges
+ *          its value (P) with thread t + h's (Q); thread 0's value is the record.
+ * No floating-point atomics: identical calls, host and device destinations, and one call over n
+ * items against n calls over one item each give the same bits.
+ * What the host derives.  The bundle's weighted mean-square radius about its centroid at the
+ * plane z = zeta of the slot's frame is (m_aa + 2*zeta*m_ab + zeta^2*m_bb)/w_sum: smallest at
+ * zeta* = -m_ab/m_bb, where it is (m_aa - m_ab^2/m_bb)/w_sum.  The focus lies in the segment when
+ * zeta* lies between the z_in and the z_out range.  At the image slot zeta* is the distance of the
+ * focus from the image plane and the value at zeta = 0 the mean-square size of the patch.
+ * n_items in [1, ROX_MAX_FOCUS_ITEMS], n_rays in [1, 2^28], ld >= n_rays.  Argument errors return
+ * ROX_E_ARG naming the parameter and item before anything is enqueued and leave the outputs
+ * untouched.  Scratch per launch is 32 MiB or, where that is more, what one item needs (120 bytes
+ * of partial records per wave of 256 rays and slot: 17 MB at 2^20 rays and 35 slots); larger jobs
+ * run as consecutive launches over fewer items with the same results.  Asynchronous on `stream`
+ * unless rec is host memory.                                                                  */
+typedef struct rox_seg_focus {
+    int64_t n;               /* rays counted                                                  */
+    int64_t n_flat;          /* rays left out because N == 0                                  */
+    int64_t n_bad;           /* rays left out for their weight (the same at every slot)       */
+    int64_t n_in;            /* counted rays inside the window                                */
+    double w_sum;            /* sum of w over the counted rays                                */
+    double w_in;             /* ... over those inside the window                              */
+    double a_mean[2];        /* weighted means of a and of b                                  */
+    double b_mean[2];
+    double m_aa;             /* sum w |a - a_mean|^2                                          */
+    double m_ab;             /* sum w (a - a_mean).(b - b_mean)                               */
+    double m_bb;             /* sum w |b - b_mean|^2                                          */
+    double z_in_min, z_in_max;   /* range of z over the counted rays; empty: +inf / -inf      */
+    double z_out_min, z_out_max; /* range of z_out                                            */
+} rox_seg_focus;             /* 136 bytes; a_mean .. m_bb are NaN where n == 0 or w_sum == 0  */
+int rox_segment_foci(rox_system *sys, uint32_t trace_flags, int32_t n_items, const rox_out *outs,
+                     int64_t n_rays, const double *weight, int64_t weight_stride,
+                     const double *window, rox_seg_focus *rec, void *stream);
+
 /* chief-ray aiming ------------------------------------------------------- */
 /* One problem per (field, wavelength): trace.iterate_ray
  * (rayoptics/raytr/trace.py:313-415) as trace.aim_chief_ray calls it

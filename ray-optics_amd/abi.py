@@ -241,6 +241,15 @@ class SaItem(C.Structure):
 MAX_SA_NUM = 16384          # include/roxtrace.h ROX_MAX_SA_NUM
 
 
+class SegFocus(C.Structure):
+    """rox_seg_focus: the weighted moments of one item's rays as they leave one FULL-packet slot"""
+    _fields_ = [('n', C.c_int64), ('n_flat', C.c_int64), ('n_bad', C.c_int64), ('n_in', C.c_int64),
+                ('w_sum', C.c_double), ('w_in', C.c_double), ('a_mean', C.c_double * 2),
+                ('b_mean', C.c_double * 2), ('m_aa', C.c_double), ('m_ab', C.c_double), ('m_bb', C.c_double),
+                ('z_in_min', C.c_double), ('z_in_max', C.c_double), ('z_out_min', C.c_double),
+                ('z_out_max', C.c_double)]
+
+
 class Vig(C.Structure):
     _fields_ = [('fld', Field), ('start_dir', C.c_double * 2), ('unit_dir', C.c_double * 2),
                 ('xy', C.c_int32), ('wvl_idx', C.c_int32), ('stop_surf', C.c_int32),
@@ -272,6 +281,7 @@ assert C.sizeof(Footprint) == 144
 assert C.sizeof(TxSurface) == 64
 assert C.sizeof(TxItem) == 72
 assert C.sizeof(SaItem) == 144
+assert C.sizeof(SegFocus) == 136
 
 # every symbol include/roxtrace.h declares (checked by tests/test_abi.py) ...
 EXPORTS = ('rox_abi_version', 'rox_device_count', 'rox_set_device',
@@ -284,7 +294,7 @@ EXPORTS = ('rox_abi_version', 'rox_device_count', 'rox_set_device',
            'rox_spot_stats', 'rox_trace_through_focus', 'rox_trace_through_focus_grids',
            'rox_focus_psf', 'rox_focus_mtf', 'rox_focus_ee', 'rox_focus_gmtf', 'rox_focus_psf_ee',
            'rox_focus_zernike', 'rox_surface_footprints', 'rox_surface_transmission',
-           'rox_surface_thinfilm', 'rox_projected_solid_angle')
+           'rox_surface_thinfilm', 'rox_projected_solid_angle', 'rox_segment_foci')
 # ... and the measurement / self-test helpers of include/roxtrace_diag.h
 DIAG_EXPORTS = ('rox_time_pupil_grid', 'rox_selftest_fp64', 'rox_diag_pack_launches')
 
@@ -369,6 +379,8 @@ def declare(lib):
                                          vp, vp, i64, vp, vp, vp]
     lib.rox_projected_solid_angle.restype = C.c_int
     lib.rox_projected_solid_angle.argtypes = [i32, i32, P(Out), i32, vp, i64, vp, vp, vp]
+    lib.rox_segment_foci.restype = C.c_int
+    lib.rox_segment_foci.argtypes = [vp, C.c_uint32, i32, P(Out), i64, vp, i64, vp, vp, vp]
     lib.rox_time_pupil_grid.restype = C.c_int
     lib.rox_time_pupil_grid.argtypes = [vp, P(Field), P(Grid), i32, P(Opts),
                                         P(Out), vp, i32, P(dbl)]

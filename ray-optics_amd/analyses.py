@@ -1489,6 +1489,167 @@ def relative_illumination(opt_model, flds=None, wvls=None, num_rays=128, coating
     return RelativeIllumination(items.reshape(F, W), spectral_wts, ref_field, weighted, cells, flds)
 
 
+# ---- two-reflection ghosts ---------------------------------------------------------
+class Ghosts:
+    """what :func:`ghost_analysis` returns.  P pairs, F fields, W wavelengths; a pair is (j, i):
+    reflected at interface j, then at the earlier interface i.
+
+    ``pairs``         the P pairs analysed; ``skipped`` the pairs left out, as ((j, i), reason)
+    ``records``       P arrays [F, W, n_seg_p] of rox_seg_focus records (engine.SEG_FOCUS_DTYPE),
+                      the rays weighted by the ghost path's transmission; ``slots`` P dicts with
+                      the ``source`` interface, the ``pass_`` (reflections so far) and the nominal
+                      ``gap`` (medium) of the segment after each slot
+    ``rays``          [P, F, W] rays that arrive at the image
+    ``flux``          [P, F, W] the sum of their weights; ``signal`` [F, W] that of the nominal path
+    ``ratio``         [P, F, W] flux / signal
+    ``in_detector``   [P, F, W] the share of the flux that lands inside ``detector`` (1 without one)
+    ``centroid``      [P, F, W, 2] the weighted centroid of the ghost patch on the image plane
+    ``rms_patch``     [P, F, W] its weighted RMS radius
+    ``focus_distance``  [P, F, W] where the ghost focuses, from the image plane along z (NaN: a
+                      collimated bundle)
+    ``poly_flux``, ``poly_ratio``, ``poly_rms_patch``  [P, F] merged over the wavelengths with the
+                      spectral weights of :class:`Transmission` (poly_ratio = poly_flux over the
+                      signal merged the same way)
+    ``internal_foci`` the ghost light's foci between two interfaces, after the first reflection: a
+                      list of dicts (pair, field, wvl, source, pass_, gap, zeta, rms_min)
+    ``results``       the device packets of every pair, with ``keep_packets``; ``trace_flags`` the
+                      rox_opts.flags they were traced with
+    Items without a ray, or whose weights sum to 0, are NaN in the derived figures."""
+
+    def __init__(self, pairs, skipped, records, slots, signal, spectral_wts, results=None):
+        from .engine import seg_focus_derive
+        self.pairs = [tuple(p) for p in pairs]
+        self.skipped = list(skipped)
+        self.records, self.slots = list(records), list(slots)
+        self.signal = np.asarray(signal, dtype=np.float64)
+        self.spectral_wts = np.asarray(spectral_wts, dtype=np.float64)
+        self.results, self.trace_flags = results, None
+        F, W = self.signal.shape
+        P = len(self.pairs)
+        img = np.zeros((P, F, W), dtype=self.records[0].dtype) if P else np.zeros((0, F, W))
+        for p, rec in enumerate(self.records):
+            img[p] = rec[:, :, -1]
+        self.internal_foci = []
+        if P == 0:
+            z = np.zeros((0, F, W))
+            self.rays = z.astype(np.int64)
+            self.flux = self.ratio = self.in_detector = self.rms_patch = self.focus_distance = z
+            self.centroid = np.zeros((0, F, W, 2))
+            self.poly_flux = self.poly_ratio = self.poly_rms_patch = np.zeros((0, F))
+            return
+        with np.errstate(divide='ignore', invalid='ignore'):
+            zeta, _ms_min, ms_0, _inside = seg_focus_derive(img)
+            self.rays = img['n'].copy()
+            self.flux = img['w_sum'].copy()
+            self.ratio = self.flux / self.signal[None]
+            some = self.flux > 0.0
+            self.in_detector = np.where(some, img['w_in'] / np.where(some, self.flux, 1.0), np.nan)
+            self.centroid = img['a_mean'].copy()
+            self.rms_patch = np.sqrt(ms_0)
+            self.focus_distance = zeta
+            self.poly_flux = np.stack([_weighted_mean(f, self.spectral_wts) for f in self.flux])
+            poly_signal = _weighted_mean(self.signal, self.spectral_wts)
+            self.poly_ratio = self.poly_flux / poly_signal[None]
+            self.poly_rms_patch = np.stack([_weighted_mean(r, self.spectral_wts) for r in self.rms_patch])
+        for p, (rec, sl) in enumerate(zip(self.records, self.slots)):
+            zeta, ms_min, _ms_0, inside = seg_focus_derive(rec[:, :, :-1])
+            for f, w, k in zip(*np.nonzero(inside & (np.asarray(sl['pass_'])[None, None, :-1] >= 1))):
+                self.internal_foci.append(dict(pair=self.pairs[p], field=int(f), wvl=int(w),
+                                               source=int(sl['source'][k]), pass_=int(sl['pass_'][k]),
+                                               gap=int(sl['gap'][k]), zeta=float(zeta[f, w, k]),
+                                               rms_min=float(np.sqrt(ms_min[f, w, k]))))
+
+    def _figure(self):
+        """[P, F] poly_ratio / (pi * poly_rms_patch^2), -inf where a field has no flux or no patch"""
+        with np.errstate(divide='ignore', invalid='ignore'):
+            fig = self.poly_ratio / (np.pi * self.poly_rms_patch ** 2)
+        return np.where(np.isnan(fig), -np.inf, fig)
+
+    def ranking(self):
+        """the pairs by their largest poly_ratio / (pi * poly_rms_patch^2) over the fields -- flux
+        over patch area, the brightest ghost first: a list of (pair index, figure); a pair without
+        flux ranks last"""
+        fig = self._figure()
+        best = fig.max(axis=1) if fig.size else np.zeros(0)
+        order = sorted(range(len(self.pairs)), key=lambda p: (-best[p], p))
+        return [(p, float(best[p])) for p in order]
+
+    def table(self, n=10):
+        """the ``n`` worst ghosts as text, one line per pair (its worst field)"""
+        lines = [' pair (j, i)   flux/signal   RMS patch   focus from image   in detector   flux/signal/area']
+        figure = self._figure()
+        for p, fig in self.ranking()[:n]:
+            f = int(np.argmax(figure[p]))
+            j, i = self.pairs[p]
+            lines.append(f' ({j:3d}, {i:3d})   {self.poly_ratio[p, f]:11.3e}   {self.poly_rms_patch[p, f]:9.4g}   '
+                         f'{_weighted_mean(self.focus_distance[p], self.spectral_wts)[f]:16.4g}   '
+                         f'{_weighted_mean(self.in_detector[p], self.spectral_wts)[f]:11.3f}   {fig:16.3e}')
+        for (j, i), why in self.skipped:
+            lines.append(f' ({j:3d}, {i:3d})   skipped: {why}')
+        return '\n'.join(lines)
+
+
+def ghost_analysis(opt_model, flds=None, wvls=None, num_rays=64, coatings=None, surfaces=None, pairs=None,
+                   check_apertures=True, detector=None, keep_packets=False):
+    """Two-reflection ghosts, on the device: for every pair of refracting surfaces (j, i) the light
+    reflected at j and again at the earlier i, followed to the image.  Items and defaults as
+    :func:`transmission`.  Per pair: the unfolded table (ghost.unfold) on its own engine, one FULL
+    launch over every (field, wavelength) with the nominal fields -- the object side up to j is
+    untouched, so aim and vignetting box serve --, one rox_surface_thinfilm call whose rows stay
+    in HBM (ghost.coating_tables: the reflecting rows are the Fresnel reflection of the bare or
+    coated surface, total internal reflection included) and one rox_segment_foci call weighted
+    by its row 0.  One nominal :func:`transmission` call gives the signal flux per item.
+    ``coatings`` as :func:`transmission` takes them; ``surfaces`` restricts the reflecting
+    interfaces; ``pairs`` names the (j, i) to analyse (each must be one ghost.ghost_pairs finds
+    or skips); ``detector``: (hx, hy), the half-widths of a detector centred on the image axis.
+    Not followed: the sensor as a reflector, more than two reflections, pairs with a mirror, a
+    phase element or a thin lens between them (reported in ``skipped``).  Returns :class:`Ghosts`."""
+    from . import ghost
+    num_rays = int(num_rays)
+    what = 'ghost_analysis'
+    eng, flds, wvls, spectral_wts, fs, wis, opts_list, flags = _packet_items(opt_model, flds, wvls, num_rays,
+                                                                             check_apertures, what)
+    F, W = len(flds), len(wvls)
+    table = eng.table
+    found, skipped = ghost.ghost_pairs(table, surfaces)
+    if pairs is not None:
+        want = [(int(j), int(i)) for j, i in pairs]
+        known = set(found) | {p for p, _why in skipped}
+        for p in want:
+            if p not in known:
+                raise ValueError(f'{what}: pairs: {p} is not a pair of reflecting refracting surfaces (j, i), i < j')
+        found = [p for p in found if p in want]
+        skipped = [(p, why) for p, why in skipped if p in want]
+    window = None
+    if detector is not None:
+        window = np.asarray(detector, dtype=np.float64).reshape(-1)
+        if window.shape[0] != 2 or not (window > 0).all():
+            raise ValueError(f'{what}: detector {detector!r} is not a pair (hx, hy) > 0')
+    nominal = transmission(opt_model, flds, wvls, num_rays, coatings, check_apertures, pupil_maps=False)
+    wvls_nm = [float(table.wvls[w]) for w in wis]
+    records, slots, kept = [], [], []
+    for j, i in found:
+        unf = ghost.unfold(table, j, i)
+        geng = session.engine_for_table(unf.table)
+        gopts = []
+        for o in opts_list:
+            g = abi.Opts.from_buffer_copy(bytes(o))
+            g.last_surf = unf.table.n_ifcs - 2
+            gopts.append(g)
+        results = _trace_packets(geng, fs, wis, gopts, num_rays)
+        rows, _surf, _item = geng.surface_thinfilm(results, flags, wis, wvls_nm, on_device=True,
+                                                   **ghost.coating_tables(table, unf, coatings))
+        rec = geng.segment_foci(results, flags, weight=rows, weight_row=0, window=window)
+        sl = geng.slot_interfaces(flags)
+        records.append(rec.reshape(F, W, len(sl)))
+        slots.append(dict(source=unf.source[sl], pass_=unf.segment_pass[sl], gap=unf.segment_gap[sl]))
+        if keep_packets:
+            kept.append(results)
+    out = Ghosts(found, skipped, records, slots, nominal.items['t_sum'], spectral_wts, kept if keep_packets else None)
+    out.trace_flags = flags
+    return out
+
+
 # ---- MTF through focus ----------------------------------------------------------
 # the PSF stack through_focus_mtf holds at once: larger maps run rox_focus_psf / rox_focus_mtf
 # over consecutive groups of items (the results do not depend on the grouping)

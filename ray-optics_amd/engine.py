@@ -188,6 +188,34 @@ SA_ITEM_DTYPE = np.dtype([('n_ok', np.int64), ('n_cells', np.int64, (5,))] +
 assert SA_ITEM_DTYPE.itemsize == C.sizeof(abi.SaItem)
 
 
+# rox_seg_focus: what segment_foci returns
+SEG_FOCUS_DTYPE = np.dtype([(name, np.int64) for name in ('n', 'n_flat', 'n_bad', 'n_in')] +
+                           [('w_sum', np.float64), ('w_in', np.float64), ('a_mean', np.float64, (2,)),
+                            ('b_mean', np.float64, (2,))] +
+                           [(name, np.float64) for name in ('m_aa', 'm_ab', 'm_bb', 'z_in_min', 'z_in_max',
+                                                            'z_out_min', 'z_out_max')])
+assert SEG_FOCUS_DTYPE.itemsize == C.sizeof(abi.SegFocus)
+
+
+def seg_focus_derive(rec):
+    """what the host derives from rox_seg_focus records (any shape): ``(zeta, ms_min, ms_0,
+    inside)`` -- the plane z = zeta* = -m_ab/m_bb of the slot's frame at which the weighted
+    mean-square radius of the bundle about its centroid is smallest, its value there
+    (m_aa - m_ab^2/m_bb)/w_sum (clipped at 0), its value m_aa/w_sum at z = 0, and whether zeta*
+    lies between the z_in and the z_out range (the focus is in the segment).  NaN / False where
+    nothing counted; a collimated bundle (m_bb == 0) has zeta* = NaN and ms_min = ms_0."""
+    with np.errstate(divide='ignore', invalid='ignore'):
+        maa, mab, mbb, w = rec['m_aa'], rec['m_ab'], rec['m_bb'], rec['w_sum']
+        conv = mbb > 0
+        zeta = np.where(conv, -mab / np.where(conv, mbb, 1.0), np.nan)
+        ms_0 = maa / w
+        ms_min = np.where(conv, np.maximum(maa - mab * mab / np.where(conv, mbb, 1.0), 0.0) / w, ms_0)
+        lo = np.minimum(rec['z_in_min'], rec['z_out_min'])
+        hi = np.maximum(rec['z_in_max'], rec['z_out_max'])
+        inside = conv & (zeta >= lo) & (zeta <= hi)
+    return zeta, ms_min, ms_0, inside
+
+
 # rox_zernike_stats: what focus_zernike returns
 ZERNIKE_STATS_DTYPE = np.dtype([('n', np.int64), ('n_outside', np.int64), ('rms', np.float64),
                                 ('rms_residual', np.float64), ('pv_residual', np.float64),
@@ -1399,6 +1427,42 @@ class TraceEngine:
             _check(self.lib.rox_projected_solid_angle(n_items, num, outs, dir_row, p_w, stride, p_item, p_cells,
                                                       self._stream()), 'rox_projected_solid_angle')
         return item, cells
+
+    @_in_flight
+    def segment_foci(self, results, trace_flags, weight=None, weight_row=0, window=None, on_device=False):
+        """rox_segment_foci over the FULL packets of finished launches (``results``, ``trace_flags``
+        as surface_footprints): per (item, slot) the weighted moments of the straight lines the OK
+        rays leave the slot's interface on, from which ``seg_focus_derive`` finds where the bundle
+        is smallest.  ``weight``: a contiguous float64 device tensor [n_items, n_rows, R], row
+        ``weight_row`` of which weighs the rays -- what surface_thinfilm(..., on_device=True)
+        returns as ``rows``, row 0 its T; None: every weight is 1.  ``window``: (hx, hy), both
+        > 0: ``w_in`` and ``n_in`` count the rays that meet the plane z = 0 of the slot's frame
+        within it.  Returns a SEG_FOCUS_DTYPE array [n_items, n_seg] -- NumPy, or with
+        ``on_device`` a torch uint8 tensor [n_items, n_seg, 136] of the raw records
+        (``records_view`` reads it on the host)."""
+        t = self.torch
+        what = 'segment_foci'
+        results, n_items, n_seg, R, outs = self._packets(results, trace_flags, what)
+        p_w, stride = None, 0
+        if weight is not None:
+            if not hasattr(weight, 'data_ptr') or weight.dim() != 3 or weight.dtype != t.float64 or \
+                    not weight.is_contiguous() or not weight.is_cuda or int(weight.shape[0]) != n_items or \
+                    int(weight.shape[2]) < R or not 0 <= int(weight_row) < int(weight.shape[1]):
+                raise EngineError(f'{what}: weight is a contiguous float64 device tensor [{n_items}, n_rows, '
+                                  f'R >= {R}] and weight_row one of its rows')
+            stride = int(weight.shape[1]) * int(weight.shape[2])
+            p_w = weight.data_ptr() + 8 * int(weight_row) * int(weight.shape[2])
+        win = None
+        if window is not None:
+            win = _f64(window, (2,))
+            if not (win > 0).all():
+                raise EngineError(f'{what}: window (hx, hy) must be > 0')
+        rec, p_rec = self._records_out(on_device, (n_items, n_seg), SEG_FOCUS_DTYPE)
+        with t.cuda.device(self.device):
+            _check(self.lib.rox_segment_foci(self._handle, int(trace_flags), n_items, outs, R, p_w, stride,
+                                             win.ctypes.data if win is not None else None, p_rec,
+                                             self._stream()), 'rox_segment_foci')
+        return rec
 
     @_in_flight
     def focus_psf_ee(self, psf, pitch, centers, radii, want_centroid=True):
