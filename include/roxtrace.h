@@ -1148,6 +1148,67 @@ int rox_segment_foci(rox_system *sys, uint32_t trace_flags, int32_t n_items, con
                      int64_t n_rays, const double *weight, int64_t weight_stride,
                      const double *window, rox_seg_focus *rec, void *stream);
 
+/* Weighted maps: numpy.histogram2d(weights=) of where the rays of ROX_OUT_FULL packets reach one
+ * slot, summed exactly.  The count maps of rox_surface_footprints take no weight; here every ray
+ * carries one (rox_surface_thinfilm's row 0 times a spectral factor: an irradiance picture of a
+ * ghost, several wavelengths into one map), and the sums are 64-bit fixed point at a power-of-two
+ * scale per map, so that they do not depend on any order -- of rays, waves, workgroups or launches.
+ *   trace_flags, n_items, outs, n_rays   as rox_segment_foci.
+ *   slot   in [0, n_seg), or -1 for the last slot (the image).  Of that slot rows 0 and 1 (p.x,
+ *          p.y) are read, of rays with status ROX_OK only: no row and no weight of any other ray.
+ *   weight, weight_stride   as rox_segment_foci: optional DEVICE, NULL = every weight is 1.
+ *   item_factor  optional HOST [n_items], finite and >= 0 (the item's spectral weight); NULL = 1.
+ *   item_map     optional HOST [n_items], in [0, n_maps): the map item i adds into.  NULL: item i
+ *          adds into map i and n_maps == n_items.  Several items may share a map.
+ *   n_maps in [1, ROX_MAX_FOCUS_ITEMS]; nbx, nby in [1, 1024].
+ *   window HOST [n_maps][4] = (cx, cy, hx, hy), finite, hx and hy > 0, cx - hx < cx + hx (and y).
+ *          Map m is numpy.histogram2d(x, y, bins=(nbx, nby), range=[[cx - hx, cx + hx],
+ *          [cy - hy, cy + hy]], weights=...), x the first axis: with lo = cx - hx, hi = cx + hx
+ *          edge j is lo + j*((hi - lo)/nbx) (one quotient, one product, one sum) and the last
+ *          edge hi -- numpy.linspace's bits; y likewise.  A value is placed by comparison with
+ *          the edges: bins are half-open, the last one closed, values outside and NaN dropped.
+ *          With cx = cy = 0 and hx = hy these are the edges of rox_surface_footprints' maps.
+ *   wmaps  host or device [n_maps][nbx][nby] int64; counts host or device, the same shape in
+ *          uint32 (optional); scale_exp host or device [n_maps] (required with wmaps); item host
+ *          or device [n_items] (optional).  wmaps, counts and item may not all be NULL.
+ * Arithmetic, in operation order (IEEE double, no FMA).  Per OK ray r of item i:
+ *          v = weight[i*weight_stride + r] * item_factor[i] (one product; absent operands are 1).
+ *          A ray whose weight is not finite or is negative (NaN included), or whose v is not
+ *          finite, adds to n_bad and to nothing else.  Every other OK ray is usable.
+ *   Pass 1: per map m, vmax = the largest v over the usable rays of its items (an exact
+ *          selection) and N = n_rays * the number of its items.  frexp(vmax) = (f, E), vmax =
+ *          f*2^E with f in [0.5, 1): scale_exp[m] = 61 - ceil(log2(N)) - E, clamped to
+ *          [-1000, 1000]; 0 where the map has no usable ray or vmax == 0.  Every q below is then
+ *          <= 2^(61 - ceil(log2 N)) and no sum over a map's rays reaches 2^62: nothing overflows.
+ *   Pass 2: q = llrint(ldexp(v, scale_exp[m])) (the ldexp is exact where q != 0; round to
+ *          nearest even).  A usable ray inside the window adds q to wmaps[m][bx][by], 1 to
+ *          counts[m][bx][by], and to its item's n_in and q_in; outside (NaN position included) to
+ *          n_out and q_out.
+ * The map in the caller's units is ldexp((double)wmaps, -scale_exp[m]), left to the caller.  Per
+ * ray the quantisation error is at most 2^-(scale_exp + 1): about vmax * N * 2^-61.
+ * Integer addition is exact and associative: identical calls, host and device destinations, any
+ * permutation of an item's rays and one call over n items into n maps against n calls over one
+ * item each give the same bits, and sum(wmaps[m]) == the sum of q_in over map m's items.
+ * Argument errors return ROX_E_ARG naming the parameter and item before anything is enqueued and
+ * leave the outputs untouched.  Scratch per launch is 32 MiB or, where that is more, what one item
+ * (pass 1: 8 bytes per wave of 256 rays) or one map bound for host memory needs; larger jobs run as
+ * consecutive launches with the same results.  Asynchronous on `stream` unless an output is host
+ * memory.  ROX_WMAPS_PATH=lds / global forces one of the kernel's two scatter paths (same bits). */
+typedef struct rox_wmap_item {
+    int64_t n_in;            /* usable rays inside the map's window (binned)                  */
+    int64_t n_out;           /* usable rays outside it (NaN position included)                */
+    int64_t n_bad;           /* OK rays left out for their weight                             */
+    int64_t q_in;            /* sum of q over the binned rays                                 */
+    int64_t q_out;           /* sum of q over the usable rays outside                         */
+} rox_wmap_item;             /* 40 bytes */
+int rox_weighted_maps(rox_system *sys, uint32_t trace_flags, int32_t n_items, const rox_out *outs,
+                      int64_t n_rays, int32_t slot,
+                      const double *weight, int64_t weight_stride,
+                      const double *item_factor, const int32_t *item_map, int32_t n_maps,
+                      const double *window, int32_t nbx, int32_t nby,
+                      int64_t *wmaps, uint32_t *counts, int32_t *scale_exp,
+                      rox_wmap_item *item, void *stream);
+
 /* chief-ray aiming ------------------------------------------------------- */
 /* One problem per (field, wavelength): trace.iterate_ray
  * (rayoptics/raytr/trace.py:313-415) as trace.aim_chief_ray calls it

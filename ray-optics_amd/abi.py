@@ -250,6 +250,15 @@ class SegFocus(C.Structure):
                 ('z_out_max', C.c_double)]
 
 
+class WmapItem(C.Structure):
+    """rox_wmap_item: the rays and fixed-point sums one item added to its weighted map"""
+    _fields_ = [('n_in', C.c_int64), ('n_out', C.c_int64), ('n_bad', C.c_int64), ('q_in', C.c_int64),
+                ('q_out', C.c_int64)]
+
+
+MAX_WMAP_BINS = 1024        # include/roxtrace.h rox_weighted_maps: nbx, nby
+
+
 class Vig(C.Structure):
     _fields_ = [('fld', Field), ('start_dir', C.c_double * 2), ('unit_dir', C.c_double * 2),
                 ('xy', C.c_int32), ('wvl_idx', C.c_int32), ('stop_surf', C.c_int32),
@@ -282,6 +291,7 @@ assert C.sizeof(TxSurface) == 64
 assert C.sizeof(TxItem) == 72
 assert C.sizeof(SaItem) == 144
 assert C.sizeof(SegFocus) == 136
+assert C.sizeof(WmapItem) == 40
 
 # every symbol include/roxtrace.h declares (checked by tests/test_abi.py) ...
 EXPORTS = ('rox_abi_version', 'rox_device_count', 'rox_set_device',
@@ -294,7 +304,7 @@ EXPORTS = ('rox_abi_version', 'rox_device_count', 'rox_set_device',
            'rox_spot_stats', 'rox_trace_through_focus', 'rox_trace_through_focus_grids',
            'rox_focus_psf', 'rox_focus_mtf', 'rox_focus_ee', 'rox_focus_gmtf', 'rox_focus_psf_ee',
            'rox_focus_zernike', 'rox_surface_footprints', 'rox_surface_transmission',
-           'rox_surface_thinfilm', 'rox_projected_solid_angle', 'rox_segment_foci')
+           'rox_surface_thinfilm', 'rox_projected_solid_angle', 'rox_segment_foci', 'rox_weighted_maps')
 # ... and the measurement / self-test helpers of include/roxtrace_diag.h
 DIAG_EXPORTS = ('rox_time_pupil_grid', 'rox_selftest_fp64', 'rox_diag_pack_launches')
 
@@ -381,6 +391,9 @@ def declare(lib):
     lib.rox_projected_solid_angle.argtypes = [i32, i32, P(Out), i32, vp, i64, vp, vp, vp]
     lib.rox_segment_foci.restype = C.c_int
     lib.rox_segment_foci.argtypes = [vp, C.c_uint32, i32, P(Out), i64, vp, i64, vp, vp, vp]
+    lib.rox_weighted_maps.restype = C.c_int
+    lib.rox_weighted_maps.argtypes = [vp, C.c_uint32, i32, P(Out), i64, i32, vp, i64, vp, vp, i32, vp, i32, i32, vp, vp,
+                                      vp, vp, vp]
     lib.rox_time_pupil_grid.restype = C.c_int
     lib.rox_time_pupil_grid.argtypes = [vp, P(Field), P(Grid), i32, P(Opts),
                                         P(Out), vp, i32, P(dbl)]

@@ -1341,6 +1341,30 @@ def transmission(opt_model, flds=None, wvls=None, num_rays=64, coatings=None, ch
 
 
 # ---- radiometric relative illumination from the image-space solid angle -------------
+def _coating_stack_tables(table, coatings, what):
+    """``coatings`` of :func:`transmission` -> (coat_kind, coat_value, the stack tables of
+    coatings.stack_tables or None without a Coating), checked"""
+    kind, value, stacks = _coating_tables(table, coatings)
+    return kind, value, stack_tables(table, stacks, what) if stacks else None
+
+
+def _transmission_rows(eng, results, flags, wis, tables):
+    """the transmission (or, with a Coating, thin-film) call of :func:`transmission` over packets
+    in HBM with the per-ray rows left there; ``tables`` from _coating_stack_tables -> (rows: a
+    device tensor [n_items, 4, R], row 0 = T; the raw rox_tx_item records [n_items, 72], also in HBM)"""
+    kind, value, film = tables
+    if film is None:
+        rows, _surf, item = eng.surface_transmission(results, flags, wis, coat_kind=kind, coat_value=value,
+                                                     on_device=True)
+    else:
+        first, thick, index, sub = film
+        rows, _surf, item = eng.surface_thinfilm(results, flags, wis, [float(eng.table.wvls[w]) for w in wis],
+                                                 coat_kind=kind, coat_value=value, stack_first=first,
+                                                 layer_thickness=thick, layer_index=index, sub_index=sub,
+                                                 on_device=True)
+    return rows, item
+
+
 class RelativeIllumination:
     """what :func:`relative_illumination` returns.
 
@@ -1471,18 +1495,10 @@ def relative_illumination(opt_model, flds=None, wvls=None, num_rays=128, coating
     rows = None
     if weighted:
         bare = isinstance(coatings, str) and coatings == 'bare'
-        kind, value, stacks = _coating_tables(eng.table, None if bare else coatings)
-        film = stack_tables(eng.table, stacks, 'relative_illumination') if stacks else None
+        tables = _coating_stack_tables(eng.table, None if bare else coatings, 'relative_illumination')
     results = _trace_packets(eng, fs, wis, opts_list, num_rays)
-    if weighted and film is None:
-        rows, _surf, _item = eng.surface_transmission(results, flags, wis, coat_kind=kind, coat_value=value,
-                                                      on_device=True)
-    elif weighted:
-        first, thick, index, sub = film
-        rows, _surf, _item = eng.surface_thinfilm(results, flags, wis, [float(eng.table.wvls[w]) for w in wis],
-                                                  coat_kind=kind, coat_value=value, stack_first=first,
-                                                  layer_thickness=thick, layer_index=index, sub_index=sub,
-                                                  on_device=True)
+    if weighted:
+        rows, _item = _transmission_rows(eng, results, flags, wis, tables)
     items, cells = eng.projected_solid_angle(results, num_rays, weight=rows, weight_row=0, want_cells=bool(cell_maps))
     if cells is not None:
         cells = cells.reshape(F, W, num_rays - 1, num_rays - 1)
@@ -1514,9 +1530,22 @@ class Ghosts:
                       list of dicts (pair, field, wvl, source, pass_, gap, zeta, rms_min)
     ``results``       the device packets of every pair, with ``keep_packets``; ``trace_flags`` the
                       rox_opts.flags they were traced with
-    Items without a ray, or whose weights sum to 0, are NaN in the derived figures."""
+    Items without a ray, or whose weights sum to 0, are NaN in the derived figures.
 
-    def __init__(self, pairs, skipped, records, slots, signal, spectral_wts, results=None):
+    With ``maps`` (rox_weighted_maps over the detector, a field's wavelengths summed into one map
+    with the normalised spectral weights; None of these without):
+    ``map_edges``     (x edges [nbx + 1], y edges [nby + 1]) of the detector's bins
+    ``irradiance``    [P, F, nbx, nby] the ghost's flux per bin over the bin's area and over the
+                      field's polychromatic signal flux (1 / length^2): its sum times the bin area
+                      is poly_ratio times the share of the flux inside the detector
+    ``irradiance_total``  [F, nbx, nby] the sum over the pairs, in pair order
+    ``signal_irradiance`` [F, nbx, nby] the same of the nominal path
+    ``peak``          [P, F] the ghost's brightest bin; ``peak_over_signal`` [P, F] that over the
+                      signal's brightest bin on the same grid (NaN for a field whose image point
+                      lies off the detector: there is no signal to compare with)
+    ``ray_counts``    [P, F, nbx, nby] the rays behind each bin"""
+
+    def __init__(self, pairs, skipped, records, slots, signal, spectral_wts, results=None, maps=None):
         from .engine import seg_focus_derive
         self.pairs = [tuple(p) for p in pairs]
         self.skipped = list(skipped)
@@ -1530,6 +1559,10 @@ class Ghosts:
         for p, rec in enumerate(self.records):
             img[p] = rec[:, :, -1]
         self.internal_foci = []
+        self.map_edges = self.irradiance = self.irradiance_total = self.signal_irradiance = None
+        self.peak = self.peak_over_signal = self.ray_counts = None
+        if maps is not None:
+            self._set_maps(**maps)
         if P == 0:
             z = np.zeros((0, F, W))
             self.rays = z.astype(np.int64)
@@ -1559,38 +1592,75 @@ class Ghosts:
                                                gap=int(sl['gap'][k]), zeta=float(zeta[f, w, k]),
                                                rms_min=float(np.sqrt(ms_min[f, w, k]))))
 
+    def _set_maps(self, window, wmaps, scale_exp, counts, signal_wmaps, signal_scale_exp):
+        """the map attributes from the integer sums of rox_weighted_maps: ``window`` = the
+        detector's (hx, hy); ``wmaps`` int64 [P, F, nbx, nby] with ``scale_exp`` [P, F] and
+        ``counts`` [P, F, nbx, nby] of the pairs, ``signal_wmaps`` [F, nbx, nby] with
+        ``signal_scale_exp`` [F] of the nominal path -- each map the sum over the field's
+        wavelengths of the normalised spectral weight times the rays' weights"""
+        hx, hy = (float(v) for v in window)
+        sig = np.asarray(signal_wmaps, dtype=np.int64)
+        F, nbx, nby = sig.shape
+        P = len(self.pairs)
+        wm = np.asarray(wmaps, dtype=np.int64).reshape(P, F, nbx, nby)
+        self.map_edges = (np.linspace(-hx, hx, nbx + 1), np.linspace(-hy, hy, nby + 1))
+        area = (2.0 * hx / nbx) * (2.0 * hy / nby)
+        poly_signal = _weighted_mean(self.signal, self.spectral_wts)
+        with np.errstate(divide='ignore', invalid='ignore'):
+            flux = np.ldexp(wm.astype(np.float64), -np.asarray(scale_exp, dtype=np.int32).reshape(P, F, 1, 1))
+            self.irradiance = flux / area / poly_signal[None, :, None, None]
+            sflux = np.ldexp(sig.astype(np.float64), -np.asarray(signal_scale_exp, dtype=np.int32).reshape(F, 1, 1))
+            self.signal_irradiance = sflux / area / poly_signal[:, None, None]
+            self.irradiance_total = np.zeros((F, nbx, nby))
+            for p in range(P):
+                self.irradiance_total = self.irradiance_total + self.irradiance[p]
+            self.peak = self.irradiance.max(axis=(2, 3)) if P else np.zeros((0, F))
+            top = self.signal_irradiance.max(axis=(1, 2))
+            self.peak_over_signal = self.peak / np.where(top > 0.0, top, np.nan)[None]
+        self.ray_counts = np.asarray(counts).reshape(P, F, nbx, nby).astype(np.int64)
+
     def _figure(self):
         """[P, F] poly_ratio / (pi * poly_rms_patch^2), -inf where a field has no flux or no patch"""
         with np.errstate(divide='ignore', invalid='ignore'):
             fig = self.poly_ratio / (np.pi * self.poly_rms_patch ** 2)
         return np.where(np.isnan(fig), -np.inf, fig)
 
-    def ranking(self):
+    def ranking(self, by='area'):
         """the pairs by their largest poly_ratio / (pi * poly_rms_patch^2) over the fields -- flux
         over patch area, the brightest ghost first: a list of (pair index, figure); a pair without
-        flux ranks last"""
-        fig = self._figure()
+        flux ranks last.  ``by='peak'`` (with maps): by their largest peak_over_signal instead."""
+        if by not in ('area', 'peak'):
+            raise ValueError(f"Ghosts.ranking: by {by!r} is not 'area' or 'peak'")
+        if by == 'peak':
+            if self.peak_over_signal is None:
+                raise ValueError("Ghosts.ranking: by='peak' needs ghost_analysis(..., maps=...)")
+            fig = np.where(np.isnan(self.peak_over_signal), -np.inf, self.peak_over_signal)
+        else:
+            fig = self._figure()
         best = fig.max(axis=1) if fig.size else np.zeros(0)
         order = sorted(range(len(self.pairs)), key=lambda p: (-best[p], p))
         return [(p, float(best[p])) for p in order]
 
     def table(self, n=10):
         """the ``n`` worst ghosts as text, one line per pair (its worst field)"""
-        lines = [' pair (j, i)   flux/signal   RMS patch   focus from image   in detector   flux/signal/area']
+        with_maps = self.peak_over_signal is not None
+        lines = [' pair (j, i)   flux/signal   RMS patch   focus from image   in detector   flux/signal/area' +
+                 ('   peak/signal peak' if with_maps else '')]
         figure = self._figure()
         for p, fig in self.ranking()[:n]:
             f = int(np.argmax(figure[p]))
             j, i = self.pairs[p]
             lines.append(f' ({j:3d}, {i:3d})   {self.poly_ratio[p, f]:11.3e}   {self.poly_rms_patch[p, f]:9.4g}   '
                          f'{_weighted_mean(self.focus_distance[p], self.spectral_wts)[f]:16.4g}   '
-                         f'{_weighted_mean(self.in_detector[p], self.spectral_wts)[f]:11.3f}   {fig:16.3e}')
+                         f'{_weighted_mean(self.in_detector[p], self.spectral_wts)[f]:11.3f}   {fig:16.3e}' +
+                         (f'   {self.peak_over_signal[p, f]:18.3e}' if with_maps else ''))
         for (j, i), why in self.skipped:
             lines.append(f' ({j:3d}, {i:3d})   skipped: {why}')
         return '\n'.join(lines)
 
 
 def ghost_analysis(opt_model, flds=None, wvls=None, num_rays=64, coatings=None, surfaces=None, pairs=None,
-                   check_apertures=True, detector=None, keep_packets=False):
+                   check_apertures=True, detector=None, keep_packets=False, maps=None):
     """Two-reflection ghosts, on the device: for every pair of refracting surfaces (j, i) the light
     reflected at j and again at the earlier i, followed to the image.  Items and defaults as
     :func:`transmission`.  Per pair: the unfolded table (ghost.unfold) on its own engine, one FULL
@@ -1602,11 +1672,22 @@ def ghost_analysis(opt_model, flds=None, wvls=None, num_rays=64, coatings=None, 
     ``coatings`` as :func:`transmission` takes them; ``surfaces`` restricts the reflecting
     interfaces; ``pairs`` names the (j, i) to analyse (each must be one ghost.ghost_pairs finds
     or skips); ``detector``: (hx, hy), the half-widths of a detector centred on the image axis.
+    ``maps``: an int or (nbx, nby) -- irradiance maps over the ``detector`` (required then): per
+    pair one rox_weighted_maps call on the packets and rows already in HBM, the field's wavelengths
+    summed into one map with the normalised spectral weights; the nominal path, whose packets and
+    rows then stay in HBM too, gets the same call (``signal_irradiance``).
     Not followed: the sensor as a reflector, more than two reflections, pairs with a mirror, a
     phase element or a thin lens between them (reported in ``skipped``).  Returns :class:`Ghosts`."""
     from . import ghost
     num_rays = int(num_rays)
     what = 'ghost_analysis'
+    bins = None
+    if maps is not None:
+        if detector is None:
+            raise ValueError(f'{what}: maps needs a detector (hx, hy): the maps cover it')
+        bins = (int(maps), int(maps)) if np.ndim(maps) == 0 else tuple(int(b) for b in maps)
+        if len(bins) != 2 or not all(1 <= b <= abi.MAX_WMAP_BINS for b in bins):
+            raise ValueError(f'{what}: maps {maps!r} is not an int or (nbx, nby) in [1, {abi.MAX_WMAP_BINS}]')
     eng, flds, wvls, spectral_wts, fs, wis, opts_list, flags = _packet_items(opt_model, flds, wvls, num_rays,
                                                                              check_apertures, what)
     F, W = len(flds), len(wvls)
@@ -1625,8 +1706,24 @@ def ghost_analysis(opt_model, flds=None, wvls=None, num_rays=64, coatings=None, 
         window = np.asarray(detector, dtype=np.float64).reshape(-1)
         if window.shape[0] != 2 or not (window > 0).all():
             raise ValueError(f'{what}: detector {detector!r} is not a pair (hx, hy) > 0')
-    nominal = transmission(opt_model, flds, wvls, num_rays, coatings, check_apertures, pupil_maps=False)
     wvls_nm = [float(table.wvls[w]) for w in wis]
+    map_kw, gmaps = None, None
+    if bins is None:
+        signal = transmission(opt_model, flds, wvls, num_rays, coatings, check_apertures,
+                              pupil_maps=False).items['t_sum']
+    else:
+        # a field's W items add into that field's map, each times its normalised spectral weight
+        s_norm = np.asarray(spectral_wts, dtype=np.float64)
+        map_kw = dict(slot=-1, weight_row=0, item_factor=np.tile(s_norm / s_norm.sum(), F),
+                      item_map=np.repeat(np.arange(F), W), n_maps=F, window=(0.0, 0.0, window[0], window[1]),
+                      bins=bins, raw=True)
+        results = _trace_packets(eng, fs, wis, opts_list, num_rays)
+        rows, item = _transmission_rows(eng, results, flags, wis, _coating_stack_tables(table, coatings, what))
+        from .engine import TX_ITEM_DTYPE, records_view
+        signal = records_view(item, TX_ITEM_DTYPE)['t_sum'].reshape(F, W)
+        swm, _cnt, sexp, _it = eng.weighted_maps(results, flags, weight=rows, **map_kw)
+        gmaps = dict(window=window, wmaps=[], scale_exp=[], counts=[], signal_wmaps=swm, signal_scale_exp=sexp)
+        del results, rows
     records, slots, kept = [], [], []
     for j, i in found:
         unf = ghost.unfold(table, j, i)
@@ -1640,12 +1737,17 @@ def ghost_analysis(opt_model, flds=None, wvls=None, num_rays=64, coatings=None, 
         rows, _surf, _item = geng.surface_thinfilm(results, flags, wis, wvls_nm, on_device=True,
                                                    **ghost.coating_tables(table, unf, coatings))
         rec = geng.segment_foci(results, flags, weight=rows, weight_row=0, window=window)
+        if gmaps is not None:
+            wm, cnt, exp, _it = geng.weighted_maps(results, flags, weight=rows, want_counts=True, **map_kw)
+            gmaps['wmaps'].append(wm)
+            gmaps['scale_exp'].append(exp)
+            gmaps['counts'].append(cnt)
         sl = geng.slot_interfaces(flags)
         records.append(rec.reshape(F, W, len(sl)))
         slots.append(dict(source=unf.source[sl], pass_=unf.segment_pass[sl], gap=unf.segment_gap[sl]))
         if keep_packets:
             kept.append(results)
-    out = Ghosts(found, skipped, records, slots, nominal.items['t_sum'], spectral_wts, kept if keep_packets else None)
+    out = Ghosts(found, skipped, records, slots, signal, spectral_wts, kept if keep_packets else None, gmaps)
     out.trace_flags = flags
     return out
 

@@ -1,6 +1,6 @@
 // rox_bins.hpp -- device helpers shared by the units that histogram rays (spotstats.hip, ee.hip,
-// gmtf.hip): the bin decision of numpy.histogram with explicit edges, and the wave-merged integer
-// count.
+// gmtf.hip, wmaps.hip): the bin decision of numpy.histogram with explicit edges, the wave-merged
+// integer count and the wave-merged 64-bit integer sum.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -49,6 +49,41 @@ __device__ __forceinline__ void wave_count(uint32_t *h, int b)
         const uint64_t same = __ballot(b == bl) & todo;
         if (lane == lead)
             atomicAdd(&h[bl], (uint32_t)__popcll(same));
+        todo &= ~same;
+    }
+}
+
+// the weighted variant (wmaps.hip): adds q per lane to h[b], and 1 per lane to c[b] where c is
+// given, for every lane with b >= 0.  Lanes of the same bin merge first: the leader adds their
+// sum, gathered lane by lane where they are few and by a butterfly over the wave where they are
+// many.  Integer sums: the result does not depend on which lanes merge.  Every lane of the wave
+// must call it.
+__device__ __forceinline__ void wave_add(unsigned long long *h, uint32_t *c, int b, unsigned long long q)
+{
+    const int lane = threadIdx.x & 63;
+    uint64_t todo = __ballot(b >= 0);
+    while (todo) {
+        const int lead = __builtin_ctzll(todo);
+        const int bl = __shfl(b, lead);
+        const uint64_t same = __ballot(b == bl) & todo;
+        const int n = __popcll(same);
+        unsigned long long sum;
+        if (n == 1) {
+            sum = q;                            // (the leader's own: only the leader uses it)
+        } else if (n <= 6) {
+            sum = 0;
+            for (uint64_t left = same; left; left &= left - 1)
+                sum += __shfl(q, __builtin_ctzll(left));
+        } else {
+            sum = ((same >> lane) & 1) ? q : 0ull;
+            for (int o = 32; o > 0; o >>= 1)
+                sum += __shfl_xor(sum, o);
+        }
+        if (lane == lead) {
+            atomicAdd(&h[bl], sum);
+            if (c)
+                atomicAdd(&c[bl], (uint32_t)n);
+        }
         todo &= ~same;
     }
 }

@@ -1,6 +1,6 @@
 // rox_packets.hpp -- what the entries that walk the ROX_OUT_FULL packets of finished launches share
-// (footprint.hip, fresnel.hip, segfoci.hip): their argument checks, a system's slot tables as their kernels read
-// them, and the fixed-order merge of their finishing kernels.
+// (footprint.hip, fresnel.hip, segfoci.hip, wmaps.hip): their argument checks, a system's slot tables as
+// their kernels read them, and the fixed-order merge of their finishing kernels.
 #pragma once
 
 #include <cstring>

@@ -196,6 +196,10 @@ SEG_FOCUS_DTYPE = np.dtype([(name, np.int64) for name in ('n', 'n_flat', 'n_bad'
                                                             'z_out_min', 'z_out_max')])
 assert SEG_FOCUS_DTYPE.itemsize == C.sizeof(abi.SegFocus)
 
+# rox_wmap_item: the item records of weighted_maps
+WMAP_ITEM_DTYPE = np.dtype([(name, np.int64) for name in ('n_in', 'n_out', 'n_bad', 'q_in', 'q_out')])
+assert WMAP_ITEM_DTYPE.itemsize == C.sizeof(abi.WmapItem)
+
 
 def seg_focus_derive(rec):
     """what the host derives from rox_seg_focus records (any shape): ``(zeta, ms_min, ms_0,
@@ -1067,6 +1071,21 @@ class TraceEngine:
                 raise EngineError(f'{what}: item {i} is not a FULL packet of {n_seg} segments and {R} rays')
         return results, n_items, n_seg, R, (abi.Out * n_items)(*[r.out_struct() for r in results])
 
+    def _weight_rows(self, what, weight, weight_row, n_items, R):
+        """the ``weight`` of a packet entry -- a contiguous float64 device tensor [n_items, n_rows,
+        >= R], row ``weight_row`` of which weighs the rays; None: no weights -> (the DEVICE
+        pointer of item 0's row or None, weight_stride)"""
+        t = self.torch
+        if weight is None:
+            return None, 0
+        if not hasattr(weight, 'data_ptr') or weight.dim() != 3 or weight.dtype != t.float64 or \
+                not weight.is_contiguous() or not weight.is_cuda or int(weight.shape[0]) != n_items or \
+                int(weight.shape[2]) < R or not 0 <= int(weight_row) < int(weight.shape[1]):
+            raise EngineError(f'{what}: weight is a contiguous float64 device tensor [{n_items}, n_rows, '
+                              f'R >= {R}] and weight_row one of its rows')
+        return (weight.data_ptr() + 8 * int(weight_row) * int(weight.shape[2]),
+                int(weight.shape[1]) * int(weight.shape[2]))
+
     @_in_flight
     def focus_psf(self, focus_rows, ndim, maxdim, wave_scale, want_psf=True):
         """rox_focus_psf over the rows of a through-focus launch (``focus_rows``: the FocusRows
@@ -1410,15 +1429,7 @@ class TraceEngine:
                 raise EngineError(f'{what}: item {i} is not a packet of out_mode {mode}, {n_seg} segments and '
                                   f'{num} x {num} rays')
         dir_row = (n_seg - 1) * abi.SEG_DOUBLES + 3
-        p_w, stride = None, 0
-        if weight is not None:
-            if not hasattr(weight, 'data_ptr') or weight.dim() != 3 or weight.dtype != t.float64 or \
-                    not weight.is_contiguous() or not weight.is_cuda or int(weight.shape[0]) != n_items or \
-                    int(weight.shape[2]) < num * num or not 0 <= int(weight_row) < int(weight.shape[1]):
-                raise EngineError(f'{what}: weight is a contiguous float64 device tensor [{n_items}, n_rows, '
-                                  f'R >= {num * num}] and weight_row one of its rows')
-            stride = int(weight.shape[1]) * int(weight.shape[2])
-            p_w = weight.data_ptr() + 8 * int(weight_row) * int(weight.shape[2])
+        p_w, stride = self._weight_rows(what, weight, weight_row, n_items, num * num)
         outs = (abi.Out * n_items)(*[r.out_struct() for r in results])
         item, p_item = self._records_out(on_device, (n_items,), SA_ITEM_DTYPE)
         cells, p_cells = self._out(on_device, (n_items, num - 1, num - 1), np.float64, t.float64) \
@@ -1443,15 +1454,7 @@ class TraceEngine:
         t = self.torch
         what = 'segment_foci'
         results, n_items, n_seg, R, outs = self._packets(results, trace_flags, what)
-        p_w, stride = None, 0
-        if weight is not None:
-            if not hasattr(weight, 'data_ptr') or weight.dim() != 3 or weight.dtype != t.float64 or \
-                    not weight.is_contiguous() or not weight.is_cuda or int(weight.shape[0]) != n_items or \
-                    int(weight.shape[2]) < R or not 0 <= int(weight_row) < int(weight.shape[1]):
-                raise EngineError(f'{what}: weight is a contiguous float64 device tensor [{n_items}, n_rows, '
-                                  f'R >= {R}] and weight_row one of its rows')
-            stride = int(weight.shape[1]) * int(weight.shape[2])
-            p_w = weight.data_ptr() + 8 * int(weight_row) * int(weight.shape[2])
+        p_w, stride = self._weight_rows(what, weight, weight_row, n_items, R)
         win = None
         if window is not None:
             win = _f64(window, (2,))
@@ -1463,6 +1466,70 @@ class TraceEngine:
                                              win.ctypes.data if win is not None else None, p_rec,
                                              self._stream()), 'rox_segment_foci')
         return rec
+
+    @_in_flight
+    def weighted_maps(self, results, trace_flags, slot=-1, weight=None, weight_row=0, item_factor=None,
+                      item_map=None, n_maps=None, window=None, bins=64, want_counts=False, on_device=False,
+                      raw=False):
+        """rox_weighted_maps over the FULL packets of finished launches (``results``, ``trace_flags``
+        as surface_footprints): numpy.histogram2d(weights=) of where the OK rays reach ``slot``
+        (-1: the image), summed exactly in 64-bit fixed point -- the maps do not depend on the
+        order of anything.  ``weight`` / ``weight_row`` as segment_foci; ``item_factor`` [n_items]
+        multiplies an item's weights (finite, >= 0); ``item_map`` [n_items] names the map each item
+        adds into (``n_maps`` of them; None: one map per item).  ``window``: (cx, cy, hx, hy),
+        one for all maps or [n_maps, 4]; ``bins``: an int or (nbx, nby).  Returns ``(maps,
+        counts, scale_exp, items)``: float64 [n_maps, nbx, nby] = ldexp(the integer sums,
+        -scale_exp) (with ``raw`` the int64 sums themselves), uint32 counts of the same shape
+        (None without ``want_counts``), int32 [n_maps] and a WMAP_ITEM_DTYPE array [n_items] --
+        NumPy, or with ``on_device`` torch tensors (the conversion then runs on the device; the
+        counts as int32 bits, the records as uint8 [n_items, 40]: ``records_view``)."""
+        t = self.torch
+        what = 'weighted_maps'
+        results, n_items, n_seg, R, outs = self._packets(results, trace_flags, what)
+        p_w, stride = self._weight_rows(what, weight, weight_row, n_items, R)
+        if not -1 <= int(slot) < n_seg:
+            raise EngineError(f'{what}: slot {slot} outside [-1, {n_seg})')
+        fac = imap = None
+        if item_factor is not None:
+            fac = _f64(item_factor, (n_items,))
+            if not (np.isfinite(fac) & (fac >= 0)).all():
+                raise EngineError(f'{what}: item_factor must be finite and >= 0')
+        if item_map is not None:
+            imap = np.ascontiguousarray(np.asarray(item_map, dtype=np.int32).reshape(-1))
+            n_maps = int(imap.max()) + 1 if n_maps is None and imap.size else n_maps
+            if imap.shape[0] != n_items or n_maps is None or not (0 <= imap).all() or not (imap < n_maps).all():
+                raise EngineError(f'{what}: item_map is [{n_items}] with values in [0, n_maps)')
+        elif n_maps not in (None, n_items):
+            raise EngineError(f'{what}: n_maps {n_maps} without item_map is not the {n_items} items')
+        n_maps = n_items if n_maps is None else int(n_maps)
+        if not 1 <= n_maps <= abi.MAX_FOCUS_ITEMS:
+            raise EngineError(f'{what}: 1 to {abi.MAX_FOCUS_ITEMS} maps, got {n_maps}')
+        if window is None:
+            raise EngineError(f'{what}: needs window = (cx, cy, hx, hy)')
+        win = _f64(window, (n_maps, 4))
+        if not (np.isfinite(win).all() and (win[:, 2:] > 0).all()):
+            raise EngineError(f'{what}: window (cx, cy, hx, hy) must be finite with hx, hy > 0')
+        nbx, nby = (int(bins), int(bins)) if np.ndim(bins) == 0 else (int(bins[0]), int(bins[1]))
+        if not (1 <= nbx <= abi.MAX_WMAP_BINS and 1 <= nby <= abi.MAX_WMAP_BINS):
+            raise EngineError(f'{what}: bins ({nbx}, {nby}) outside [1, {abi.MAX_WMAP_BINS}]')
+        wm, p_wm = self._out(on_device, (n_maps, nbx, nby), np.int64, t.int64)
+        cnt, p_cnt = self._out(on_device, (n_maps, nbx, nby), np.uint32, t.int32) if want_counts else (None, None)
+        exp, p_exp = self._out(on_device, (n_maps,), np.int32, t.int32)
+        item, p_item = self._records_out(on_device, (n_items,), WMAP_ITEM_DTYPE)
+        with t.cuda.device(self.device):
+            _check(self.lib.rox_weighted_maps(self._handle, int(trace_flags), n_items, outs, R, int(slot), p_w, stride,
+                                              fac.ctypes.data if fac is not None else None,
+                                              imap.ctypes.data if imap is not None else None, n_maps,
+                                              win.ctypes.data, nbx, nby, p_wm, p_cnt, p_exp, p_item,
+                                              self._stream()), 'rox_weighted_maps')
+        if raw:
+            return wm, cnt, exp, item
+        if on_device:
+            # 2^-scale_exp from its bits (scale_exp in [-1000, 1000]: a normal number); the product is
+            # ldexp's correctly rounded result
+            two = ((1023 - exp.to(t.int64)) << 52).view(t.float64)
+            return wm.to(t.float64) * two[:, None, None], cnt, exp, item
+        return np.ldexp(wm.astype(np.float64), -exp[:, None, None]), cnt, exp, item
 
     @_in_flight
     def focus_psf_ee(self, psf, pitch, centers, radii, want_centroid=True):
