@@ -534,10 +534,8 @@ extern "C" int rox_focus_ee(int32_t n_items, int32_t n_planes, const double *row
     ROX_TRY(rox::check_centers(kE, total, centers));
 
     hipStream_t st = (hipStream_t)stream;
-    rox::PerStream<rox::Workspace>::Slot *slot;
-    ROX_TRY(g_ee_ws.take(st, kHipWhere, &slot));
-    std::lock_guard<std::mutex> turn(slot->mu);
-    rox::Workspace *ws = &slot->data;
+    rox::Turn<> ws;
+    ROX_TRY(ws.take(g_ee_ws, st, kHipWhere));
 
     const int nwg = wgs_for(n_rays, kRaysPerWg);
     const int ngroups = (nq + kQGroup - 1) / kQGroup;
@@ -629,10 +627,8 @@ extern "C" int rox_focus_psf_ee(int32_t n_items, int32_t n_planes, const double 
     ROX_TRY(rox::check_centers(kE, total, centers));
 
     hipStream_t st = (hipStream_t)stream;
-    rox::PerStream<rox::Workspace>::Slot *slot;
-    ROX_TRY(g_ee_ws.take(st, kHipWhere, &slot));
-    std::lock_guard<std::mutex> turn(slot->mu);
-    rox::Workspace *ws = &slot->data;
+    rox::Turn<> ws;
+    ROX_TRY(ws.take(g_ee_ws, st, kHipWhere));
 
     const int M = maxdim, nr = n_radii;
     const int nwg = wgs_for(M, 4 * kWaves);              // at least 4 rows per wave

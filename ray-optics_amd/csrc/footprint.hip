@@ -5,18 +5,21 @@
 // What the reference answers with four rim rays per field (vigcalc.max_aperture_at_surf,
 // rayoptics/raytr/vigcalc.py:31-42) is answered here from the dense grid that is already in HBM.
 //
-// A workgroup owns kTile consecutive rays of one item, kRays per thread, and walks the slots in
-// order with the previous slot's direction in registers: of a record's 10 rows it reads p.x, p.y,
-// d and nrml once each, coalesced along the ray axis, and never dst or p.z.  A slot of a ray is
-// read only where the ray has a record there.  Each wave writes one partial record per slot; the
+// A workgroup (rox::PacketTile) owns kTile consecutive rays of one item, kRays per thread, and
+// walks the slots in order with the previous slot's direction in registers: of a record's 10 rows
+// it reads p.x, p.y, d and nrml once each, coalesced along the ray axis, and never dst or p.z.  A
+// slot of a ray is read only where the ray has a record there.  Each wave writes one partial
+// record per slot, its counts merged in the same butterfly as its moments (rox::wave_merge); the
 // finishing kernel merges a slot's partial records in a fixed order (Chan / Golub / LeVeque for
 // the centroid and the second moment, both taken about a pivot ray of the item, footprint_pivot).
-// No floating-point atomics; the maps are integer atomics.  (Shared with fresnel.hip: rox_packets.hpp.)
+// No floating-point atomics; the maps are integer atomics.  (The tile, the merges and the host's
+// turn are those of every packet entry: rox_packets.hpp.)
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
 #include <cstdint>
 
+#include "rox_bins.hpp"
 #include "rox_device.hpp"
 #include "rox_packets.hpp"
 
@@ -26,10 +29,8 @@ using rox::kRtDoubles;
 
 constexpr char kHipWhere[] = "rox_surface_footprints: ";
 
-constexpr int kBlock = 256;
-constexpr int kWaves = kBlock / 64;
-constexpr int kRays = 4;                        // rays per thread
-constexpr int kTile = kBlock * kRays;           // rays per workgroup
+using Tile = rox::PacketTile<4>;                // rays per thread
+constexpr int kBlock = Tile::kBlock, kWaves = Tile::kWaves, kRays = Tile::kRays;
 // Device scratch of one launch (partial records, records and maps bound for host memory): a call
 // that needs more per launch runs as consecutive launches over fewer items.
 constexpr size_t kFpScratchBytes = size_t(8) << 20;
@@ -101,34 +102,6 @@ __device__ __forceinline__ void acc_merge(Acc &a, const Acc &b)
     a.cemin = fmin(a.cemin, b.cemin);
 }
 
-__device__ __forceinline__ Acc acc_shfl_xor(const Acc &a, int o)
-{
-    Acc b;
-    b.n = __shfl_xor(a.n, o); b.mx = __shfl_xor(a.mx, o); b.my = __shfl_xor(a.my, o); b.m2 = __shfl_xor(a.m2, o);
-    b.minx = __shfl_xor(a.minx, o); b.miny = __shfl_xor(a.miny, o);
-    b.maxx = __shfl_xor(a.maxx, o); b.maxy = __shfl_xor(a.maxy, o);
-    b.r2 = __shfl_xor(a.r2, o);
-    b.cimin = __shfl_xor(a.cimin, o); b.cisum = __shfl_xor(a.cisum, o); b.cemin = __shfl_xor(a.cemin, o);
-    return b;
-}
-
-// The bin of v among the n_bins + 1 edges -h + j * step (the last one h) as numpy.histogramdd
-// places it: searchsorted(edges, v, 'right') - 1, the last edge in the last bin; -1 = outside.
-// The proportional guess is corrected by comparison with the edges themselves.
-__device__ __forceinline__ int fp_bin(double v, double h, double step, int n)
-{
-    if (!(v >= -h) || !(v <= h))
-        return -1;                              // (NaN included)
-    const double t = (v + h) / (h + h) * (double)n;
-    int g = t < (double)(n - 1) ? (int)t : n - 1;
-    g = g < 0 ? 0 : g;
-    while (g > 0 && v < -h + (double)g * step)
-        --g;
-    while (g < n - 1 && v >= -h + (double)(g + 1) * step)
-        ++g;
-    return g;
-}
-
 // pivot[item][k] = (p.x, p.y) at slot k of one ray of the item that reached the image: the OK ray
 // nearest in index to the middle of the grid (of a square product grid: its centre ray), (0, 0)
 // when there is none.  The moments are accumulated about it, so that the partial means carry
@@ -182,7 +155,7 @@ __global__ __launch_bounds__(kBlock) void footprint_pivot(const ItemIn *__restri
 __global__ __launch_bounds__(kBlock) void footprint_kernel(const FpArgs a)
 {
     const ItemIn it = a.items[blockIdx.y];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
     const int n_seg = a.n_seg;
     const bool with_partial = (a.flags & ROX_FP_PARTIAL) != 0, ok_only = (a.flags & ROX_FP_OK_ONLY) != 0;
 
@@ -192,7 +165,7 @@ __global__ __launch_bounds__(kBlock) void footprint_kernel(const FpArgs a)
     double pdx[kRays], pdy[kRays], pdz[kRays];
 #pragma unroll
     for (int j = 0; j < kRays; ++j) {
-        r[j] = (int64_t)blockIdx.x * kTile + j * kBlock + threadIdx.x;
+        r[j] = Tile::ray(j);
         nfull[j] = 0; pslot[j] = -1; fslot[j] = -1; fst[j] = 0;
         pdx[j] = pdy[j] = pdz[j] = 0.0;
         if (r[j] < a.n_rays) {
@@ -218,8 +191,7 @@ __global__ __launch_bounds__(kBlock) void footprint_kernel(const FpArgs a)
         }
     }
 
-    Part *out = a.part ? a.part + ((size_t)blockIdx.y * a.n_waves + (size_t)blockIdx.x * kWaves + wave) * n_seg
-                       : nullptr;
+    Part *out = a.part ? a.part + Tile::part(a.n_waves, n_seg) : nullptr;
     uint32_t *maps = a.maps ? a.maps + (size_t)blockIdx.y * n_seg * a.n_bins * a.n_bins : nullptr;
 
     for (int k = 0; k < n_seg; ++k) {
@@ -253,21 +225,12 @@ __global__ __launch_bounds__(kBlock) void footprint_kernel(const FpArgs a)
             for (int j = 0; j < kRays; ++j) {
                 int b = -1;
                 if (geo[j]) {
-                    const int bx = fp_bin(x[j], h, step, a.n_bins), by = fp_bin(y[j], h, step, a.n_bins);
+                    const int bx = rox::uniform_bin(x[j], -h, h, step, a.n_bins);
+                    const int by = rox::uniform_bin(y[j], -h, h, step, a.n_bins);
                     if (bx >= 0 && by >= 0)
                         b = bx * a.n_bins + by;
                 }
-                // neighbouring rays of a grid land in the same bins: the lanes of a wave that share a
-                // bin add once (un-merged, a launch's atomics queue on few addresses: 20 x slower)
-                uint64_t todo = __ballot(b >= 0);
-                while (todo) {
-                    const int lead = __builtin_ctzll(todo);
-                    const int bl = __shfl(b, lead);
-                    const uint64_t same = __ballot(b == bl) & todo;
-                    if (lane == lead)
-                        atomicAdd(&m[bl], (uint32_t)__popcll(same));
-                    todo &= ~same;
-                }
+                rox::wave_count(m, b);          // (maps is uniform: every lane of the wave is here)
             }
         }
         if (!out)
@@ -333,18 +296,14 @@ __global__ __launch_bounds__(kBlock) void footprint_kernel(const FpArgs a)
                     t.m2 += ex * ex + ey * ey;
                 }
         }
-        for (int o = 32; o > 0; o >>= 1) {
-            const Acc b = acc_shfl_xor(t, o);
-            acc_merge(t, b);
-            nf += __shfl_xor(nf, o);
-            n_inc += __shfl_xor(n_inc, o);
-        }
-        if (lane == 0) {
-            out[k].a = t;
-            out[k].nf = nf;
-            out[k].n_inc = n_inc;
-            out[k].pad = 0;
-        }
+        Part p{t, nf, n_inc, 0};
+        rox::wave_merge(p, [](Part &m, const Part &b) {
+            acc_merge(m.a, b.a);
+            m.nf += b.nf;
+            m.n_inc += b.n_inc;
+        });
+        if (lane == 0)
+            out[k] = p;
     }
 }
 
@@ -429,14 +388,12 @@ extern "C" int rox_surface_footprints(rox_system *sys, uint32_t trace_flags, uin
     }
 
     hipStream_t st = (hipStream_t)stream;
-    rox::PerStream<rox::Workspace>::Slot *slot;
-    ROX_TRY(g_fp_ws.take(st, kHipWhere, &slot));
-    std::lock_guard<std::mutex> turn(slot->mu);
-    rox::Workspace *ws = &slot->data;
+    rox::Turn<> ws;
+    ROX_TRY(ws.take(g_fp_ws, st, kHipWhere));
 
     const bool maps_host = maps && !rox::is_device(maps);
     const bool host_dst = (fp && !rox::is_device(fp)) || maps_host;
-    const int n_tiles = (int)((n_rays + kTile - 1) / kTile), n_waves = n_tiles * kWaves;
+    const int n_tiles = Tile::tiles(n_rays), n_waves = n_tiles * kWaves;
     const size_t map_item = maps ? sizeof(uint32_t) * (size_t)n_seg * n_bins * n_bins : 0;
     const size_t b_part = fp ? rox::up256(sizeof(Part) * (size_t)n_waves * n_seg) : 0;
     const size_t b_fp = fp ? rox::up256(sizeof(rox_footprint) * (size_t)n_seg) : 0;
@@ -458,10 +415,8 @@ extern "C" int rox_surface_footprints(rox_system *sys, uint32_t trace_flags, uin
     L.add(d_fp, fp ? rox::up256(sizeof(rox_footprint) * (size_t)n_seg * chunk) : 0);
     L.add(d_maps, maps_host ? rox::up256(map_item * chunk) : 0);
     L.add(d_pivot, fp ? rox::up256(sizeof(double) * 2 * (size_t)n_seg * chunk) : 0);
-    HIP_TRY(ws->reserve(L.size()));
-    L.carve(ws->buf);
-    HIP_TRY(ws->stage.acquire(b_tab));
-    char *h = ws->stage.h;
+    char *h;
+    ROX_TRY(ws.carve(L, b_tab, &h));
     for (int32_t i = 0; i < n_items; ++i)
         ((ItemIn *)h)[i] = ItemIn{outs[i].seg, outs[i].status, outs[i].fail_surf, outs[i].ld};
     ps.stage_rt((double *)(h + o_rt));
@@ -470,8 +425,7 @@ extern "C" int rox_surface_footprints(rox_system *sys, uint32_t trace_flags, uin
     for (int32_t i = 0; i < n_ifcs; ++i)
         ((int32_t *)(h + o_nb))[i] = ps.slots[n_ifcs + i];
     ps.stage_slot_ifc((int32_t *)(h + o_si));
-    HIP_TRY(hipMemcpyAsync(d_tab, h, b_tab, hipMemcpyHostToDevice, st));
-    HIP_TRY(ws->stage.record(st));
+    ROX_TRY(ws.upload(d_tab, b_tab));
 
     FpArgs a{};
     a.rt = (const double *)(d_tab + o_rt);

@@ -11,8 +11,8 @@
 // its coating values, the rt of the interfaces in between -- is read through the constant address
 // space at wave-uniform addresses: scalar loads into SGPRs (the kernel's only vector loads are
 // the status byte and the twelve packet reads of a slot).  Each wave writes one partial record per slot and one for the item; the
-// finishing kernel merges them in a fixed order.  No floating-point atomics.  (Shared with
-// footprint.hip: rox_packets.hpp.)
+// finishing kernel merges them in a fixed order.  No floating-point atomics.  (The tile, the
+// merges and the host's turn are those of every packet entry: rox_packets.hpp.)
 //
 // rox_surface_thinfilm is the same walk with complex field vectors and, where an interface has a
 // stack of thin films or a metal behind it, the characteristic matrix of the stack evaluated per
@@ -40,11 +40,9 @@ using rox::kRtDoubles;
 
 constexpr char kHipWhere[] = "rox_surface_transmission: ";
 
-constexpr int kBlock = 256;
-constexpr int kWaves = kBlock / 64;
-constexpr int kRays = 2;                        // rays per thread: 107 VGPRs and 4 waves per SIMD (real), 214 and 2
+using Tile = rox::PacketTile<2>;                // rays per thread: 107 VGPRs and 4 waves per SIMD (real), 214 and 2
                                                 // (complex), no scratch
-constexpr int kTile = kBlock * kRays;           // rays per workgroup
+constexpr int kBlock = Tile::kBlock, kWaves = Tile::kWaves, kRays = Tile::kRays, kTile = Tile::kTile;
 // Device scratch of one launch (partial records, records, rows bound for host memory): a call that
 // needs more per launch runs as consecutive launches over fewer items and, for the rows, fewer
 // rays.  One item's partial records are not split: an item whose records exceed the cap (more than
@@ -154,19 +152,6 @@ __device__ __forceinline__ void part_merge(Part &a, const Part &b)
     a.v[5] = kItem ? fmax(a.v[5], b.v[5]) : fmin(a.v[5], b.v[5]);
     a.v[6] = a.v[6] + b.v[6];
     a.v[7] = kItem ? fmax(a.v[7], b.v[7]) : fmin(a.v[7], b.v[7]);
-}
-
-template <bool kItem>
-__device__ __forceinline__ Part wave_merge(Part t)
-{
-    for (int o = 32; o > 0; o >>= 1) {
-        Part b;
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-            b.v[i] = __shfl_xor(t.v[i], o);
-        part_merge<kItem>(t, b);
-    }
-    return t;
 }
 
 // ---- thin films: complex amplitudes (include/roxtrace.h rox_surface_thinfilm states the order)
@@ -294,7 +279,7 @@ __global__ __launch_bounds__(kBlock) void fresnel_kernel(const Args args)
     using Co = typename std::conditional<kFilm, Cx, double>::type;      // of (ts, tp)
     const TxArgs &a = args;                     // bound to the argument itself: see FilmArgs
     const ItemIn it = a.items[blockIdx.y];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
     const int n_seg = a.n_seg;
     // the tables through the constant address space (rox_device.hpp): a wave-uniform address there is
     // a scalar load into SGPRs, and the stores of the partial records do not order it
@@ -318,15 +303,14 @@ __global__ __launch_bounds__(kBlock) void fresnel_kernel(const Args args)
 #pragma unroll
     for (int j = 0; j < kRays; ++j) {
         Ray<F> &y = ray[j];
-        y.r = a.ray0 + (int64_t)blockIdx.x * kTile + j * kBlock + threadIdx.x;
+        y.r = Tile::ray(j, a.ray0);
         y.ok = y.r < a.n_rays && it.status[y.r] == ROX_OK;
         y.b4 = zero;
         start(y.E1, zero);
         start(y.E2, zero);
         y.q = 1.0;
     }
-    const size_t wave_of_item = (size_t)(a.ray0 / kTile + blockIdx.x) * kWaves + wave;
-    Part *out = a.part ? a.part + ((size_t)blockIdx.y * a.n_waves + wave_of_item) * (n_seg + 1) : nullptr;
+    Part *out = a.part ? a.part + Tile::part(a.n_waves, n_seg + 1, a.ray0) : nullptr;
 
     for (int k = 0; k < n_seg; ++k) {
         const double *rec = it.seg + (size_t)k * ROX_SEG_DOUBLES * it.ld;
@@ -508,7 +492,7 @@ __global__ __launch_bounds__(kBlock) void fresnel_kernel(const Args args)
             b4 = d;
         }
         if (out) {
-            t = wave_merge<false>(t);
+            rox::wave_merge(t, [](Part &m, const Part &b) { part_merge<false>(m, b); });
             if (lane == 0)
                 out[k] = t;
         }
@@ -546,7 +530,7 @@ __global__ __launch_bounds__(kBlock) void fresnel_kernel(const Args args)
         }
     }
     if (out) {
-        t = wave_merge<true>(t);
+        rox::wave_merge(t, [](Part &m, const Part &b) { part_merge<true>(m, b); });
         if (lane == 0)
             out[n_seg] = t;
     }
@@ -729,16 +713,14 @@ int tx_entry(const char *kE, const Film *film, rox_system *sys, uint32_t trace_f
     }
 
     hipStream_t st = (hipStream_t)stream;
-    rox::PerStream<rox::Workspace>::Slot *slot;
-    ROX_TRY(g_tx_ws.take(st, kHipWhere, &slot));
-    std::lock_guard<std::mutex> turn(slot->mu);
-    rox::Workspace *ws = &slot->data;
+    rox::Turn<> ws;
+    ROX_TRY(ws.take(g_tx_ws, st, kHipWhere));
 
     const bool want_rec = surf || item;
     const bool rows_host = rows && !rox::is_device(rows);
     const bool host_dst = rows_host || (surf && !rox::is_device(surf)) || (item && !rox::is_device(item));
     const int n_rows = (tx_flags & ROX_TX_FIELDS) ? (film ? 16 : 10) : 4;
-    const int64_t n_tiles = (n_rays + kTile - 1) / kTile;
+    const int64_t n_tiles = Tile::tiles(n_rays);
     const int n_waves = (int)n_tiles * kWaves;
     // rows bound for host memory pass through the scratch, a range of rays at a time
     const int64_t range_tiles =
@@ -774,10 +756,8 @@ int tx_entry(const char *kE, const Film *film, rox_system *sys, uint32_t trace_f
     L.add(d_part, b_part * chunk);
     L.add(d_surf, b_surf * chunk);
     L.add(d_item, want_rec ? rox::up256(sizeof(rox_tx_item) * (size_t)chunk) : 0);
-    HIP_TRY(ws->reserve(L.size()));
-    L.carve(ws->buf);
-    HIP_TRY(ws->stage.acquire(b_tab));
-    char *h = ws->stage.h;
+    char *h;
+    ROX_TRY(ws.carve(L, b_tab, &h));
     for (int32_t i = 0; i < n_items; ++i)
         ((ItemIn *)h)[i] = ItemIn{outs[i].seg, outs[i].status, outs[i].ld, wvl_idx[i], 0};
     ps.stage_rt((double *)(h + o_rt));
@@ -825,8 +805,7 @@ int tx_entry(const char *kE, const Film *film, rox_system *sys, uint32_t trace_f
         if (coat_kind[j % n_ifcs] == ROX_COAT_STACK && ps.rows[j % n_ifcs].mode == ROX_REFLECT)
             square(film->sub + 2 * j, n2);
     }
-    HIP_TRY(hipMemcpyAsync(d_tab, h, b_tab, hipMemcpyHostToDevice, st));
-    HIP_TRY(ws->stage.record(st));
+    ROX_TRY(ws.upload(d_tab, b_tab));
 
     FilmArgs fa{};
     if (film) {

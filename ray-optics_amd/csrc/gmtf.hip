@@ -263,10 +263,8 @@ extern "C" int rox_focus_gmtf(int32_t n_items, int32_t n_planes, const double *r
         ROX_TRY(rox::check_edges(kE, total * D, B, edges));
 
     hipStream_t st = (hipStream_t)stream;
-    rox::PerStream<rox::Workspace>::Slot *slot;
-    ROX_TRY(g_gmtf_ws.take(st, kHipWhere, &slot));
-    std::lock_guard<std::mutex> turn(slot->mu);
-    rox::Workspace *ws = &slot->data;
+    rox::Turn<> ws;
+    ROX_TRY(ws.take(g_gmtf_ws, st, kHipWhere));
 
     const int nwg = (int)nwg64;
     // frequencies per launch: one plane's partial records take at most half the scratch

@@ -180,10 +180,8 @@ extern "C" int rox_focus_mtf(int32_t n_items, int32_t n_planes, const double *ps
             return rox::host_fail(ROX_E_ARG, "%s: freqs[%d] = %g is not finite and >= 0", kE, q, freqs[q]);
 
     hipStream_t st = (hipStream_t)stream;
-    rox::PerStream<rox::Workspace>::Slot *slot;
-    ROX_TRY(g_mtf_ws.take(st, kHipWhere, &slot));
-    std::lock_guard<std::mutex> turn(slot->mu);
-    rox::Workspace *ws = &slot->data;
+    rox::Turn<> ws;
+    ROX_TRY(ws.take(g_mtf_ws, st, kHipWhere));
 
     const bool dev_dst = rox::is_device(otf);
     const int M = maxdim, Q = n_freq;

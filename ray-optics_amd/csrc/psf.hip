@@ -404,12 +404,10 @@ extern "C" int rox_calc_psf(const double *opd, int32_t ndim, int32_t maxdim, dou
     Shape s{};
     ROX_TRY(psf_shape(kE, ndim, maxdim, &s));
     hipStream_t st = (hipStream_t)stream;
-    rox::PerStream<PsfWorkspace>::Slot *slot;
-    ROX_TRY(g_ws.take(st, kHipWhere, &slot));
     // calls on one stream share the workspace: enqueue them whole, one after the other
     // (stream order then keeps their kernels apart); host-pointer calls hold it until done
-    std::lock_guard<std::mutex> turn(slot->mu);
-    PsfWorkspace *ws = &slot->data;
+    rox::Turn<PsfWorkspace> ws;
+    ROX_TRY(ws.take(g_ws, st, kHipWhere));
 
     const bool host = (flags & ROX_HOST_POINTERS) != 0;
     const size_t b_opd = host ? sizeof(double) * (size_t)s.n * s.n : 0;
@@ -464,10 +462,8 @@ extern "C" int rox_focus_psf(int32_t n_items, int32_t n_planes, const double *ro
         return rox::host_fail(ROX_E_ARG, "%s: psf and stats are both null", kE);
 
     hipStream_t st = (hipStream_t)stream;
-    rox::PerStream<PsfWorkspace>::Slot *slot;
-    ROX_TRY(g_focus_ws.take(st, kHipWhere, &slot));
-    std::lock_guard<std::mutex> turn(slot->mu);
-    PsfWorkspace *ws = &slot->data;
+    rox::Turn<PsfWorkspace> ws;
+    ROX_TRY(ws.take(g_focus_ws, st, kHipWhere));
 
     const int64_t nblk = ((int64_t)n * n + kFocusBlock - 1) / kFocusBlock;
     const int64_t total = (int64_t)n_items * n_planes;

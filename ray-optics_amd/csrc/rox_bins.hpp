@@ -1,6 +1,6 @@
 // rox_bins.hpp -- device helpers shared by the units that histogram rays (spotstats.hip, ee.hip,
-// gmtf.hip, wmaps.hip): the bin decision of numpy.histogram with explicit edges, the wave-merged
-// integer count and the wave-merged 64-bit integer sum.
+// gmtf.hip, footprint.hip, wmaps.hip): the bin decision of numpy.histogram with explicit edges and
+// with uniform ones, the wave-merged integer count and the wave-merged 64-bit integer sum.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -37,8 +37,28 @@ __device__ __forceinline__ int bin_of(const double *e, int n, double v)
     return lo;
 }
 
-// adds 1 per lane to h[b] for every lane with b >= 0: lanes of the same bin merge first.  Every
-// lane of the wave must call it.
+// The bin of v among the n + 1 uniform edges lo + j * step (the last one hi) as numpy.histogramdd
+// places it: searchsorted(edges, v, 'right') - 1, the last edge in the last bin; -1 = outside.
+// The proportional guess is corrected by comparison with the edges themselves.  A box centred on
+// 0 is (lo, hi) = (-h, h): v - (-h) is v + h, h - (-h) is h + h and -h + g * step is one IEEE
+// operation either way, so the bin is the one the expressions written in h give, bit for bit.
+__device__ __forceinline__ int uniform_bin(double v, double lo, double hi, double step, int n)
+{
+    if (!(v >= lo) || !(v <= hi))
+        return -1;                              // (NaN included)
+    const double t = (v - lo) / (hi - lo) * (double)n;
+    int g = t < (double)(n - 1) ? (int)t : n - 1;
+    g = g < 0 ? 0 : g;
+    while (g > 0 && v < lo + (double)g * step)
+        --g;
+    while (g < n - 1 && v >= lo + (double)(g + 1) * step)
+        ++g;
+    return g;
+}
+
+// adds 1 per lane to h[b] for every lane with b >= 0: lanes of the same bin merge first --
+// neighbouring rays of a grid land in the same bins (un-merged, a launch's atomics queue on few
+// addresses: footprint.hip's maps took 20 x longer).  Every lane of the wave must call it.
 __device__ __forceinline__ void wave_count(uint32_t *h, int b)
 {
     const int lane = threadIdx.x & 63;

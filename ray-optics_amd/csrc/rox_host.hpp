@@ -1,10 +1,10 @@
 // rox_host.hpp -- host-side helpers shared by the translation units that define C entry points
 // (roxtrace.hip and the units its header lists, selftest.hip, spotstats.hip, the analyses psf.hip,
 // mtf.hip, ee.hip, gmtf.hip and zernike.hip, and through rox_packets.hpp footprint.hip, fresnel.hip,
-// segfoci.hip and wmaps.hip):
+// solidangle.hip, segfoci.hip and wmaps.hip):
 // the error path and the argument checks, the environment switches, grow-only scratch blocks,
-// scratch kept per (device, stream), the pinned staging of host inputs and the carving of one
-// workspace block.
+// scratch kept per (device, stream), the pinned staging of host inputs, the carving of one
+// workspace block and an entry's turn on its per-stream state.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -321,6 +321,56 @@ class Layout {
     Region regions_[kMaxRegions];
     int n_ = 0;
     size_t size_ = 0;
+};
+
+// An entry's turn on its state T of the current device and stream st: take() finds the slot and
+// holds its mutex until the Turn leaves scope.  The Turn then stands for that state (ws->...).
+// `where` is the entry's kHipWhere, the prefix of the messages of take() and of the two steps
+// below, which spell their HIP calls as the entries did.
+template <class T = Workspace>
+class Turn {
+  public:
+    T *ws = nullptr;
+    hipStream_t st = nullptr;
+
+    // 0, or ROX_E_HIP / ROX_E_NOMEM as PerStream::take
+    int take(PerStream<T> &all, hipStream_t stream, const char *where)
+    {
+        typename PerStream<T>::Slot *slot;
+        ROX_TRY(all.take(stream, where, &slot));
+        lock_ = std::unique_lock<std::mutex>(slot->mu);
+        ws = &slot->data;
+        st = stream;
+        where_ = where;
+        return 0;
+    }
+    T *operator->() const { return ws; }
+
+    // The two steps of an entry that stages one block of tables (the packet entries): the device
+    // block of L reserved and carved and b_tab bytes of the pinned staging free to write at *h ...
+    template <class H>
+    int carve(const Layout &L, size_t b_tab, H **h)
+    {
+        const char *const kHipWhere = where_;
+        HIP_TRY(ws->reserve(L.size()));
+        L.carve(ws->buf);
+        HIP_TRY(ws->stage.acquire(b_tab));
+        *h = reinterpret_cast<H *>(ws->stage.h);
+        return 0;
+    }
+    // ... and, once the host has filled them, on their way to d_tab in stream order
+    int upload(void *d_tab, size_t b_tab)
+    {
+        const char *const kHipWhere = where_;
+        const char *h = ws->stage.h;
+        HIP_TRY(hipMemcpyAsync(d_tab, h, b_tab, hipMemcpyHostToDevice, st));
+        HIP_TRY(ws->stage.record(st));
+        return 0;
+    }
+
+  private:
+    std::unique_lock<std::mutex> lock_;
+    const char *where_ = "";
 };
 
 }  // namespace rox

@@ -1,9 +1,11 @@
 // rox_packets.hpp -- what the entries that walk the ROX_OUT_FULL packets of finished launches share
-// (footprint.hip, fresnel.hip, segfoci.hip, wmaps.hip): their argument checks, a system's slot tables as
-// their kernels read them, and the fixed-order merge of their finishing kernels.
+// (footprint.hip, fresnel.hip, solidangle.hip, segfoci.hip, wmaps.hip): their argument checks, a
+// system's slot tables as their kernels read them, the tile their workgroups walk, the fixed-order
+// merge of a wave's records and that of their finishing kernels.
 #pragma once
 
 #include <cstring>
+#include <type_traits>
 
 #include "rox_host.hpp"
 
@@ -65,6 +67,60 @@ struct PacketSlots {
                 dst[slots[i]] = i;
     }
 };
+
+// ---- the tile walk: a workgroup of kBlock threads owns kTile consecutive rays of one item
+// (blockIdx.y), kRays per thread, ray j of a thread kBlock rays after its ray j - 1, so that a wave
+// reads 64 consecutive rays; each of its kWaves waves writes one partial record per slot
+template <int kRaysPerThread>
+struct PacketTile {
+    static constexpr int kBlock = 256;
+    static constexpr int kWaves = kBlock / 64;
+    static constexpr int kRays = kRaysPerThread;
+    static constexpr int kTile = kBlock * kRays;
+
+    // workgroups per item
+    static int tiles(int64_t n_rays) { return (int)((n_rays + kTile - 1) / kTile); }
+    // ray j of this thread, in a launch whose first ray is ray0
+    static __device__ __forceinline__ int64_t ray(int j, int64_t ray0 = 0)
+    {
+        return ray0 + (int64_t)blockIdx.x * kTile + j * kBlock + threadIdx.x;
+    }
+    // this wave's first partial record in part[items][n_waves][n_seg], n_waves over all of an
+    // item's rays (ray0 a multiple of kTile)
+    static __device__ __forceinline__ size_t part(int n_waves, int n_seg, int64_t ray0 = 0)
+    {
+        return ((size_t)blockIdx.y * n_waves + (size_t)(ray0 / kTile + blockIdx.x) * kWaves + (threadIdx.x >> 6)) *
+               n_seg;
+    }
+};
+
+// ---- the merge of a wave: t becomes the 64 lanes' records merged by the fixed butterfly
+// o = 32, 16, .., 1 of merge(t, partner), the lane's own record first (the callers write lane 0's).
+// The record travels as 32-bit words, whatever its fields: one added to a record is merged with it.
+template <class T>
+__device__ __forceinline__ T shfl_xor(const T &a, int o)
+{
+    static_assert(std::is_trivially_copyable<T>::value, "a record is shuffled as its bytes");
+    static_assert(sizeof(T) % 4 == 0, "a record is shuffled as 32-bit words");
+    constexpr int n = (int)(sizeof(T) / 4);
+    int w[n];
+    __builtin_memcpy(w, &a, sizeof(T));
+#pragma unroll
+    for (int i = 0; i < n; ++i)
+        w[i] = __shfl_xor(w[i], o);
+    T b;
+    __builtin_memcpy(&b, w, sizeof(T));
+    return b;
+}
+
+template <class T, class Merge>
+__device__ __forceinline__ void wave_merge(T &t, Merge merge)
+{
+    for (int o = 32; o > 0; o >>= 1) {
+        const T b = shfl_xor(t, o);
+        merge(t, b);
+    }
+}
 
 // ---- the merge of a finishing kernel, by a workgroup of kBlock threads: the n records p[w * stride]
 // into one, in one fixed order whatever the launch -- thread t merges w = t, t + kBlock, ... in that

@@ -4,11 +4,12 @@
 // of the slot's frame, b = its slopes -- from which the host finds where between this interface and
 // the next the weighted bundle is smallest (the ghost analysis' internal foci, analyses.ghost_analysis).
 //
-// The shape of footprint.hip: a workgroup owns kTile consecutive rays of one item, kRays per
-// thread, and walks the slots in order; of a record's 10 rows it reads p, d and dst once each,
-// coalesced along the ray axis, and only of rays that count.  Each wave writes one partial record
-// per slot; the finishing kernel merges a slot's partial records in the fixed order of
-// rox::block_merge (Chan / Golub / LeVeque, weighted).  No floating-point atomics, no LDS in the walk.
+// The shape of footprint.hip (rox::PacketTile): a workgroup owns kTile consecutive rays of one
+// item, kRays per thread, and walks the slots in order; of a record's 10 rows it reads p, d and dst
+// once each, coalesced along the ray axis, and only of rays that count.  Each wave writes one
+// partial record per slot (rox::wave_merge); the finishing kernel merges a slot's partial records in
+// the fixed order of rox::block_merge (Chan / Golub / LeVeque, weighted).  No floating-point
+// atomics, no LDS in the walk.
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
@@ -21,10 +22,8 @@ namespace {
 
 constexpr char kHipWhere[] = "rox_segment_foci: ";
 
-constexpr int kBlock = 256;
-constexpr int kWaves = kBlock / 64;
-constexpr int kRays = 4;                        // rays per thread
-constexpr int kTile = kBlock * kRays;           // rays per workgroup
+using Tile = rox::PacketTile<4>;                // rays per thread
+constexpr int kBlock = Tile::kBlock, kWaves = Tile::kWaves, kRays = Tile::kRays;
 // Device scratch of one launch (partial records and records bound for host memory), or what one
 // item needs where that is more: a call that needs more per launch runs as consecutive launches
 // over fewer items.
@@ -95,23 +94,10 @@ __device__ __forceinline__ void acc_merge(Acc &a, const Acc &b)
     a.n += b.n; a.n_flat += b.n_flat; a.n_bad += b.n_bad; a.n_in += b.n_in;
 }
 
-__device__ __forceinline__ Acc acc_shfl_xor(const Acc &a, int o)
-{
-    Acc b;
-    b.w = __shfl_xor(a.w, o); b.w_in = __shfl_xor(a.w_in, o);
-    b.ax = __shfl_xor(a.ax, o); b.ay = __shfl_xor(a.ay, o); b.bx = __shfl_xor(a.bx, o); b.by = __shfl_xor(a.by, o);
-    b.maa = __shfl_xor(a.maa, o); b.mab = __shfl_xor(a.mab, o); b.mbb = __shfl_xor(a.mbb, o);
-    b.zi_min = __shfl_xor(a.zi_min, o); b.zi_max = __shfl_xor(a.zi_max, o);
-    b.zo_min = __shfl_xor(a.zo_min, o); b.zo_max = __shfl_xor(a.zo_max, o);
-    b.n = __shfl_xor(a.n, o); b.n_flat = __shfl_xor(a.n_flat, o);
-    b.n_bad = __shfl_xor(a.n_bad, o); b.n_in = __shfl_xor(a.n_in, o);
-    return b;
-}
-
 __global__ __launch_bounds__(kBlock) void segfoci_kernel(const SfArgs a)
 {
     const ItemIn it = a.items[blockIdx.y];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
     const int n_seg = a.n_seg;
 
     // per ray: whether it counts (status ROX_OK and a weight that is finite and >= 0) and its weight
@@ -121,7 +107,7 @@ __global__ __launch_bounds__(kBlock) void segfoci_kernel(const SfArgs a)
     uint32_t n_bad = 0;
 #pragma unroll
     for (int j = 0; j < kRays; ++j) {
-        r[j] = (int64_t)blockIdx.x * kTile + j * kBlock + threadIdx.x;
+        r[j] = Tile::ray(j);
         use[j] = false;
         w[j] = 1.0;
         if (r[j] < a.n_rays && it.status[r[j]] == ROX_OK) {
@@ -132,7 +118,7 @@ __global__ __launch_bounds__(kBlock) void segfoci_kernel(const SfArgs a)
         }
     }
 
-    Acc *out = a.part + ((size_t)blockIdx.y * a.n_waves + (size_t)blockIdx.x * kWaves + wave) * n_seg;
+    Acc *out = a.part + Tile::part(a.n_waves, n_seg);
 
     for (int k = 0; k < n_seg; ++k) {
         const double *rec = it.seg + (size_t)k * ROX_SEG_DOUBLES * it.ld;
@@ -176,10 +162,7 @@ __global__ __launch_bounds__(kBlock) void segfoci_kernel(const SfArgs a)
                 acc_merge(t, q);
             }
         }
-        for (int o = 32; o > 0; o >>= 1) {
-            const Acc b = acc_shfl_xor(t, o);
-            acc_merge(t, b);
-        }
+        rox::wave_merge(t, [](Acc &m, const Acc &b) { acc_merge(m, b); });
         if (lane == 0)
             out[k] = t;
     }
@@ -251,13 +234,11 @@ extern "C" int rox_segment_foci(rox_system *sys, uint32_t trace_flags, int32_t n
     const int32_t n_seg = ps.n_seg;
 
     hipStream_t st = (hipStream_t)stream;
-    rox::PerStream<rox::Workspace>::Slot *slot;
-    ROX_TRY(g_sf_ws.take(st, kHipWhere, &slot));
-    std::lock_guard<std::mutex> turn(slot->mu);
-    rox::Workspace *ws = &slot->data;
+    rox::Turn<> ws;
+    ROX_TRY(ws.take(g_sf_ws, st, kHipWhere));
 
     const bool host_dst = !rox::is_device(rec);
-    const int n_tiles = (int)((n_rays + kTile - 1) / kTile), n_waves = n_tiles * kWaves;
+    const int n_tiles = Tile::tiles(n_rays), n_waves = n_tiles * kWaves;
     const size_t b_part = rox::up256(sizeof(Acc) * (size_t)n_waves * n_seg);
     const size_t b_rec = rox::up256(sizeof(rox_seg_focus) * (size_t)n_seg);
     const int64_t chunk = rox::chunk_for(n_items, b_part + b_rec + 256, kSfScratchBytes);
@@ -270,14 +251,11 @@ extern "C" int rox_segment_foci(rox_system *sys, uint32_t trace_flags, int32_t n
     L.add(d_tab, rox::up256(b_tab));
     L.add(d_part, rox::up256(sizeof(Acc) * (size_t)n_waves * n_seg * chunk));
     L.add(d_rec, rox::up256(sizeof(rox_seg_focus) * (size_t)n_seg * chunk));
-    HIP_TRY(ws->reserve(L.size()));
-    L.carve(ws->buf);
-    HIP_TRY(ws->stage.acquire(b_tab));
-    ItemIn *h = (ItemIn *)ws->stage.h;
+    ItemIn *h;
+    ROX_TRY(ws.carve(L, b_tab, &h));
     for (int32_t i = 0; i < n_items; ++i)
         h[i] = ItemIn{outs[i].seg, outs[i].status, weight ? weight + (size_t)i * weight_stride : nullptr, outs[i].ld};
-    HIP_TRY(hipMemcpyAsync(d_tab, h, b_tab, hipMemcpyHostToDevice, st));
-    HIP_TRY(ws->stage.record(st));
+    ROX_TRY(ws.upload(d_tab, b_tab));
 
     SfArgs a{};
     a.n_seg = n_seg; a.n_waves = n_waves; a.n_rays = n_rays;

@@ -20,8 +20,8 @@ namespace {
 
 constexpr char kHipWhere[] = "rox_projected_solid_angle: ";
 
-constexpr int kBlock = 256;
-constexpr int kWaves = kBlock / 64;
+// the workgroup of the packet entries; the rays are dealt in strips, not in its tiles
+constexpr int kBlock = rox::PacketTile<1>::kBlock, kWaves = rox::PacketTile<1>::kWaves;
 constexpr int kStrip = 63;                      // cells per wave and row
 // Device scratch of one launch (partial records, records and cells bound for host memory): a call
 // that needs more per launch runs as consecutive launches over fewer items.
@@ -72,18 +72,6 @@ __device__ __forceinline__ void acc_merge(Acc &a, const Acc &b)
     a.l_min = fmin(a.l_min, b.l_min); a.l_max = fmax(a.l_max, b.l_max);
     a.m_min = fmin(a.m_min, b.m_min); a.m_max = fmax(a.m_max, b.m_max);
     a.r2 = fmax(a.r2, b.r2);
-}
-
-__device__ __forceinline__ Acc acc_shfl_xor(const Acc &a, int o)
-{
-    Acc b;
-    b.a_full = __shfl_xor(a.a_full, o); b.a_tri = __shfl_xor(a.a_tri, o); b.a_abs = __shfl_xor(a.a_abs, o);
-    b.aw_full = __shfl_xor(a.aw_full, o); b.aw_tri = __shfl_xor(a.aw_tri, o);
-    b.l_sum = __shfl_xor(a.l_sum, o); b.m_sum = __shfl_xor(a.m_sum, o);
-    b.l_min = __shfl_xor(a.l_min, o); b.l_max = __shfl_xor(a.l_max, o);
-    b.m_min = __shfl_xor(a.m_min, o); b.m_max = __shfl_xor(a.m_max, o);
-    b.r2 = __shfl_xor(a.r2, o);
-    return b;
 }
 
 __global__ __launch_bounds__(kBlock) void solid_angle_kernel(const SaArgs a)
@@ -160,20 +148,15 @@ __global__ __launch_bounds__(kBlock) void solid_angle_kernel(const SaArgs a)
     if (!a.part)
         return;
     // the wave's record by a fixed butterfly
-    for (int o = 32; o > 0; o >>= 1) {
-        const Acc b = acc_shfl_xor(t, o);
-        acc_merge(t, b);
-        n_ok += __shfl_xor(n_ok, o);
+    Part p{t, n_ok, {nc[0], nc[1], nc[2], nc[3], nc[4]}};
+    rox::wave_merge(p, [](Part &m, const Part &b) {
+        acc_merge(m.a, b.a);
+        m.n_ok += b.n_ok;
         for (int k = 0; k < 5; ++k)
-            nc[k] += __shfl_xor(nc[k], o);
-    }
-    if (lane == 0) {
-        Part *out = a.part + (size_t)blockIdx.y * a.n_units + unit;
-        out->a = t;
-        out->n_ok = n_ok;
-        for (int k = 0; k < 5; ++k)
-            out->n_cells[k] = nc[k];
-    }
+            m.n_cells[k] += b.n_cells[k];
+    });
+    if (lane == 0)
+        a.part[(size_t)blockIdx.y * a.n_units + unit] = p;
 }
 
 // what an item's partial records merge into, and a count as either holds it
@@ -244,10 +227,8 @@ extern "C" int rox_projected_solid_angle(int32_t n_items, int32_t num, const rox
         ROX_TRY(rox::check_packet_item(kE, i, outs[i], n_rays, false));
 
     hipStream_t st = (hipStream_t)stream;
-    rox::PerStream<rox::Workspace>::Slot *slot;
-    ROX_TRY(g_sa_ws.take(st, kHipWhere, &slot));
-    std::lock_guard<std::mutex> turn(slot->mu);
-    rox::Workspace *ws = &slot->data;
+    rox::Turn<> ws;
+    ROX_TRY(ws.take(g_sa_ws, st, kHipWhere));
 
     const bool cells_host = cells && !rox::is_device(cells);
     const bool host_dst = (item && !rox::is_device(item)) || cells_host;
@@ -269,16 +250,13 @@ extern "C" int rox_projected_solid_angle(int32_t n_items, int32_t num, const rox
     L.add(d_part, item ? rox::up256(sizeof(Part) * (size_t)n_units * chunk) : 0);
     L.add(d_item, item ? rox::up256(sizeof(rox_sa_item) * (size_t)chunk) : 0);
     L.add(d_cells, cells_host ? rox::up256(cells_item * chunk) : 0);
-    HIP_TRY(ws->reserve(L.size()));
-    L.carve(ws->buf);
-    HIP_TRY(ws->stage.acquire(b_tab));
-    ItemIn *h = (ItemIn *)ws->stage.h;
+    ItemIn *h;
+    ROX_TRY(ws.carve(L, b_tab, &h));
     for (int32_t i = 0; i < n_items; ++i) {
         const double *seg = outs[i].seg + (size_t)dir_row * outs[i].ld;
         h[i] = ItemIn{seg, seg + outs[i].ld, outs[i].status, weight ? weight + (size_t)i * weight_stride : nullptr};
     }
-    HIP_TRY(hipMemcpyAsync(d_tab, h, b_tab, hipMemcpyHostToDevice, st));
-    HIP_TRY(ws->stage.record(st));
+    ROX_TRY(ws.upload(d_tab, b_tab));
 
     SaArgs a{};
     a.num = num; a.rows = rows; a.n_strips = n_strips; a.n_units = n_units;

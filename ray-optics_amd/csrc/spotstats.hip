@@ -183,14 +183,10 @@ extern "C" int rox_spot_stats(const double *seg, int64_t ld, const uint8_t *stat
     const size_t d_need = (want_hist ? b_edges + b_copies : 0) + b_part;
     const size_t h_hist = (((size_t)bins * 4) + 255) & ~size_t(255);
     const size_t h_need = 256 + h_hist + (want_hist ? b_edges : 0);
-    int device = 0;
-    HIP_TRY(hipGetDevice(&device));
-    auto *slot = g_scratch.get(device, st);
-    if (!slot)
-        return host_fail(ROX_E_NOMEM, "rox_spot_stats: out of host memory");
     // calls on one stream take turns: the scratch is theirs until the results are read back
-    std::lock_guard<std::mutex> turn(slot->mu);
-    StatScratch &sc = slot->data;
+    Turn<StatScratch> turn;
+    ROX_TRY(turn.take(g_scratch, st, kHipWhere));
+    StatScratch &sc = *turn.ws;
     if (sc.d_cap < d_need)
         HIP_TRY(regrow(sc.d, sc.d_cap, d_need + d_need / 4, d_need + d_need / 4));
     if (sc.h_cap < h_need)

@@ -8,7 +8,7 @@
 //
 // Pass 1 (wmaps_vmax, wmaps_vmax_finish, wmaps_scale): the largest usable v = weight * factor of
 // every item, per wave, then per item by rox::block_merge, then per map with its scale exponent.
-// A maximum is an exact selection.  Pass 2 (wmaps_kernel): the tile partition of segfoci_kernel --
+// A maximum is an exact selection.  Pass 2 (wmaps_kernel): the tile of rox::PacketTile --
 // a workgroup owns kTile consecutive rays of one item, kRays per thread; it reads status, weight
 // and the slot's p.x and p.y, of OK rays only.  Where the bins its rays fall into span a box of at
 // most kLdsBins bins the workgroup sums them in LDS (64-bit integer adds and a 32-bit count) and
@@ -30,10 +30,8 @@ namespace {
 
 constexpr char kHipWhere[] = "rox_weighted_maps: ";
 
-constexpr int kBlock = 256;
-constexpr int kWaves = kBlock / 64;
-constexpr int kRays = 4;                        // rays per thread
-constexpr int kTile = kBlock * kRays;           // rays per workgroup
+using Tile = rox::PacketTile<4>;                // rays per thread
+constexpr int kBlock = Tile::kBlock, kWaves = Tile::kWaves, kRays = Tile::kRays;
 // the LDS window of a workgroup: 12 bytes per bin, 48 KiB -- three workgroups per CU
 constexpr int kLdsBins = 4096;
 // Device scratch of one launch (pass 1's partial maxima; maps bound for host memory), or what one
@@ -68,23 +66,6 @@ struct WmArgs {
 // whether a ray of weight w and value v = w * factor is usable (NaN: not)
 __device__ __forceinline__ bool usable(double w, double v) { return w >= 0.0 && w <= DBL_MAX && v <= DBL_MAX; }
 
-// The bin of v among the n + 1 edges lo + j * step (the last one hi) as numpy.histogramdd places
-// it: searchsorted(edges, v, 'right') - 1, the last edge in the last bin; -1 = outside.  The
-// proportional guess is corrected by comparison with the edges themselves (footprint.hip's fp_bin).
-__device__ __forceinline__ int wm_bin(double v, double lo, double hi, double step, int n)
-{
-    if (!(v >= lo) || !(v <= hi))
-        return -1;                              // (NaN included)
-    const double t = (v - lo) / (hi - lo) * (double)n;
-    int g = t < (double)(n - 1) ? (int)t : n - 1;
-    g = g < 0 ? 0 : g;
-    while (g > 0 && v < lo + (double)g * step)
-        --g;
-    while (g < n - 1 && v >= lo + (double)(g + 1) * step)
-        ++g;
-    return g;
-}
-
 // part[item][wave] = the largest usable v of the wave's rays, -1 where it has none
 __global__ __launch_bounds__(kBlock) void wmaps_vmax(const ItemIn *__restrict__ items, int64_t n_rays, int n_waves,
                                                      double *__restrict__ part)
@@ -93,7 +74,7 @@ __global__ __launch_bounds__(kBlock) void wmaps_vmax(const ItemIn *__restrict__ 
     double vm = -1.0;
 #pragma unroll
     for (int j = 0; j < kRays; ++j) {
-        const int64_t r = (int64_t)blockIdx.x * kTile + j * kBlock + threadIdx.x;
+        const int64_t r = Tile::ray(j);
         if (r < n_rays && it.status[r] == ROX_OK) {
             const double w = it.weight ? it.weight[r] : 1.0;
             const double v = w * it.factor;
@@ -104,7 +85,7 @@ __global__ __launch_bounds__(kBlock) void wmaps_vmax(const ItemIn *__restrict__ 
     for (int o = 32; o > 0; o >>= 1)
         vm = fmax(vm, __shfl_xor(vm, o));
     if ((threadIdx.x & 63) == 0)
-        part[(size_t)blockIdx.y * n_waves + (size_t)blockIdx.x * kWaves + (threadIdx.x >> 6)] = vm;
+        part[Tile::part(n_waves, 1)] = vm;
 }
 
 // vitem[item] from part[item][w], w = 0 .. n_waves - 1
@@ -162,7 +143,7 @@ __global__ __launch_bounds__(kBlock) void wmaps_kernel(const WmArgs a)
     int x0 = nbx, x1 = -1, y0 = nby, y1 = -1;
 #pragma unroll
     for (int j = 0; j < kRays; ++j) {
-        const int64_t r = (int64_t)blockIdx.x * kTile + j * kBlock + threadIdx.x;
+        const int64_t r = Tile::ray(j);
         bx[j] = by[j] = -1;
         q[j] = 0;
         if (r < a.n_rays && it.status[r] == ROX_OK) {
@@ -173,7 +154,8 @@ __global__ __launch_bounds__(kBlock) void wmaps_kernel(const WmArgs a)
                 continue;
             }
             q[j] = (unsigned long long)llrint(ldexp(v, e));
-            const int gx = wm_bin(rec[r], lox, hix, stx, nbx), gy = wm_bin(rec[it.ld + r], loy, hiy, sty, nby);
+            const int gx = rox::uniform_bin(rec[r], lox, hix, stx, nbx);
+            const int gy = rox::uniform_bin(rec[it.ld + r], loy, hiy, sty, nby);
             if (gx >= 0 && gy >= 0) {
                 bx[j] = gx; by[j] = gy;
                 x0 = min(x0, gx); x1 = max(x1, gx);
@@ -322,15 +304,13 @@ extern "C" int rox_weighted_maps(rox_system *sys, uint32_t trace_flags, int32_t 
         return rox::host_fail(ROX_E_ARG, "%s: slot %d outside [-1, %d)", kE, slot, n_seg);
 
     hipStream_t st = (hipStream_t)stream;
-    rox::PerStream<rox::Workspace>::Slot *wslot;
-    ROX_TRY(g_wm_ws.take(st, kHipWhere, &wslot));
-    std::lock_guard<std::mutex> turn(wslot->mu);
-    rox::Workspace *ws = &wslot->data;
+    rox::Turn<> ws;
+    ROX_TRY(ws.take(g_wm_ws, st, kHipWhere));
 
     const bool w_host = wmaps && !rox::is_device(wmaps), c_host = counts && !rox::is_device(counts);
     const bool e_host = scale_exp && !rox::is_device(scale_exp), i_host = item && !rox::is_device(item);
     const size_t nb = (size_t)nbx * nby;
-    const int n_tiles = (int)((n_rays + kTile - 1) / kTile), n_waves = n_tiles * kWaves;
+    const int n_tiles = Tile::tiles(n_rays), n_waves = n_tiles * kWaves;
     // pass 1 runs over chunk1 items per launch, pass 2 over the items of chunk2 maps
     const int64_t chunk1 = rox::chunk_for(n_items, rox::up256(sizeof(double) * (size_t)n_waves), kWmScratchBytes);
     const size_t map_host = (w_host ? sizeof(int64_t) * nb : 0) + (c_host ? sizeof(uint32_t) * nb : 0);
@@ -353,10 +333,8 @@ extern "C" int rox_weighted_maps(rox_system *sys, uint32_t trace_flags, int32_t 
     L.add(d_item, rox::up256(sizeof(rox_wmap_item) * (size_t)n_items));
     L.add(d_w, w_host ? rox::up256(sizeof(int64_t) * nb * chunk2) : 0);
     L.add(d_c, c_host ? rox::up256(sizeof(uint32_t) * nb * chunk2) : 0);
-    HIP_TRY(ws->reserve(L.size()));
-    L.carve(ws->buf);
-    HIP_TRY(ws->stage.acquire(b_tab));
-    char *h = ws->stage.h;
+    char *h;
+    ROX_TRY(ws.carve(L, b_tab, &h));
     ItemIn *h_items = (ItemIn *)h;
     int32_t *h_first = (int32_t *)(h + o_first), *h_clog = (int32_t *)(h + o_clog);
     // a counting sort of the items by their map, stable: h_first[m] = the first item of map m
@@ -382,8 +360,7 @@ extern "C" int rox_weighted_maps(rox_system *sys, uint32_t trace_flags, int32_t 
         }
     }
     memcpy(h + o_win, window, sizeof(double) * 4 * (size_t)n_maps);
-    HIP_TRY(hipMemcpyAsync(d_tab, h, b_tab, hipMemcpyHostToDevice, st));
-    HIP_TRY(ws->stage.record(st));
+    ROX_TRY(ws.upload(d_tab, b_tab));
     const ItemIn *d_items = (const ItemIn *)d_tab;
     const int32_t *d_first = (const int32_t *)(d_tab + o_first);
 

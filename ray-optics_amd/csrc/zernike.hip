@@ -535,10 +535,8 @@ extern "C" int rox_focus_zernike(int32_t n_items, int32_t n_planes, const double
     }
 
     hipStream_t st = (hipStream_t)stream;
-    rox::PerStream<rox::Workspace>::Slot *slot;
-    ROX_TRY(g_zk_ws.take(st, kHipWhere, &slot));
-    std::lock_guard<std::mutex> turn(slot->mu);
-    rox::Workspace *ws = &slot->data;
+    rox::Turn<> ws;
+    ROX_TRY(ws.take(g_zk_ws, st, kHipWhere));
 
     const int J = n_terms, K = n_planes;
     const int JP = (J + 1 + 15) & ~15;

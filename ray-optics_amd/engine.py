@@ -1057,18 +1057,31 @@ class TraceEngine:
         tensor of the struct's bytes per record (``records_view`` reads it on the host)"""
         return self._out(on_device, shape, dtype, self.torch.uint8, (*shape, dtype.itemsize))
 
-    def _packets(self, results, trace_flags, what):
+    def _packets(self, results, trace_flags, what, modes=(abi.OUT_FULL,), num=None):
         """the FULL packets of finished launches (a single DeviceResult gains the item axis) ->
-        (results, n_items, n_seg, R, outs), outs the abi.Out array a packet entry reads"""
+        (results, n_items, n_seg, R, outs), outs the abi.Out array a packet entry reads.  An entry
+        that reads other packets too names their ``modes`` (every item then has the first one's, and
+        n_seg is what that one holds, 1 for OUT_LAST); one that reads ``num`` x ``num`` product
+        grids names ``num``"""
         results = [results] if isinstance(results, DeviceResult) else list(results)
         n_items = len(results)
         if not 1 <= n_items <= abi.MAX_FOCUS_ITEMS:
             raise EngineError(f'{what}: 1 to {abi.MAX_FOCUS_ITEMS} items, got {n_items}')
-        n_seg = self.num_segments(int(trace_flags))
-        R = int(results[0].R)
+        if num is not None and not 2 <= num <= abi.MAX_SA_NUM:
+            raise EngineError(f'{what}: num {num} outside [2, {abi.MAX_SA_NUM}]')
+        mode = results[0].out_mode if len(modes) > 1 else modes[0]
+        if mode not in modes:
+            raise EngineError(f'{what}: reads OUT_LAST or OUT_FULL packets, not out_mode {mode}')
+        if len(modes) > 1:
+            n_seg = int(results[0].seg.shape[0]) if mode == abi.OUT_FULL else 1
+        else:
+            n_seg = self.num_segments(int(trace_flags))
+        R = int(results[0].R) if num is None else num * num
         for i, r in enumerate(results):
-            if r.out_mode != abi.OUT_FULL or int(r.seg.shape[0]) != n_seg or int(r.R) != R:
-                raise EngineError(f'{what}: item {i} is not a FULL packet of {n_seg} segments and {R} rays')
+            if r.out_mode != mode or (mode == abi.OUT_FULL and int(r.seg.shape[0]) != n_seg) or int(r.R) != R:
+                raise EngineError(f'{what}: item {i} is not a FULL packet of {n_seg} segments and {R} rays'
+                                  if num is None else f'{what}: item {i} is not a packet of out_mode {mode}, '
+                                  f'{n_seg} segments and {num} x {num} rays')
         return results, n_items, n_seg, R, (abi.Out * n_items)(*[r.out_struct() for r in results])
 
     def _weight_rows(self, what, weight, weight_row, n_items, R):
@@ -1413,24 +1426,10 @@ class TraceEngine:
         reads them on the host)."""
         t = self.torch
         what = 'projected_solid_angle'
-        results = [results] if isinstance(results, DeviceResult) else list(results)
-        n_items, num = len(results), int(num)
-        if not 1 <= n_items <= abi.MAX_FOCUS_ITEMS:
-            raise EngineError(f'{what}: 1 to {abi.MAX_FOCUS_ITEMS} items, got {n_items}')
-        if not 2 <= num <= abi.MAX_SA_NUM:
-            raise EngineError(f'{what}: num {num} outside [2, {abi.MAX_SA_NUM}]')
-        mode = results[0].out_mode
-        if mode not in (abi.OUT_LAST, abi.OUT_FULL):
-            raise EngineError(f'{what}: reads OUT_LAST or OUT_FULL packets, not out_mode {mode}')
-        n_seg = int(results[0].seg.shape[0]) if mode == abi.OUT_FULL else 1
-        for i, r in enumerate(results):
-            if r.out_mode != mode or int(r.R) != num * num or \
-                    (mode == abi.OUT_FULL and int(r.seg.shape[0]) != n_seg):
-                raise EngineError(f'{what}: item {i} is not a packet of out_mode {mode}, {n_seg} segments and '
-                                  f'{num} x {num} rays')
+        num = int(num)
+        results, n_items, n_seg, R, outs = self._packets(results, None, what, (abi.OUT_LAST, abi.OUT_FULL), num)
         dir_row = (n_seg - 1) * abi.SEG_DOUBLES + 3
-        p_w, stride = self._weight_rows(what, weight, weight_row, n_items, num * num)
-        outs = (abi.Out * n_items)(*[r.out_struct() for r in results])
+        p_w, stride = self._weight_rows(what, weight, weight_row, n_items, R)
         item, p_item = self._records_out(on_device, (n_items,), SA_ITEM_DTYPE)
         cells, p_cells = self._out(on_device, (n_items, num - 1, num - 1), np.float64, t.float64) \
             if want_cells else (None, None)

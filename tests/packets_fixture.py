@@ -1,5 +1,6 @@
 """TEST INFRASTRUCTURE for the -m gpu tests of the entries that walk the ROX_OUT_FULL packets of
-finished launches (rox_surface_footprints, rox_surface_transmission): the ``torch`` fixture, host
+finished launches (rox_surface_footprints, rox_surface_transmission, rox_surface_thinfilm,
+rox_projected_solid_angle, rox_segment_foci, rox_weighted_maps): the ``torch`` fixture, host
 packets put into HBM, packets traced there and packets copied back."""
 import numpy as np
 import pytest
