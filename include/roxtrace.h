@@ -1209,6 +1209,89 @@ int rox_weighted_maps(rox_system *sys, uint32_t trace_flags, int32_t n_items, co
                       int64_t *wmaps, uint32_t *counts, int32_t *scale_exp,
                       rox_wmap_item *item, void *stream);
 
+/* Wavefront differentials: tolerancing from one trace.  By Fermat's principle the first-order
+ * change of a ray's optical path under a small displacement delta of the surface point it meets
+ * is (n1*b4 - n2*d).delta, b4 and d the ray's unit directions before and after the interface and
+ * n1, n2 the unsigned indices (Hopkins & Tiziani 1966; Rimmer 1970); under a change dn of a gap's
+ * index it is dn*dst.  Per OK ray and selected slot of the ROX_OUT_FULL packets of finished
+ * launches this entry forms eleven such columns -- shifts, rotations about the vertex, curvature,
+ * power, two astigmatic irregularities, the gap's index -- and reduces them, with caller-supplied
+ * per-ray aux rows (the nominal OPD, the pupil coordinates), to the sums a covariance needs:
+ * sensitivity tables, compensators, RSS budgets and Monte Carlo runs are then host linear algebra
+ * on n_cols numbers.  The columns are INCREASES of optical path.
+ *   trace_flags, n_items, outs, n_rays   as rox_segment_foci; of a slot's 10 rows d is read and,
+ *          where the slot is selected, p and dst.
+ *   wvl_idx  HOST [n_items], as rox_surface_transmission: item i's row of the index table.
+ *   sel_slot HOST [n_sel], strictly increasing slots in [0, n_seg), n_sel in [0, n_seg].  NULL:
+ *          every slot, and n_sel == n_seg.
+ *   aux    optional DEVICE: ray r of item i has aux row a at aux[i*aux_stride + a*ld_aux + r];
+ *          n_aux in [0, ROX_MAX_WD_AUX], ld_aux >= n_rays.
+ *   n_cols = n_aux + 11*n_sel, in [1, ROX_MAX_WD_COLS].
+ *   cols   optional, host or device [n_items][n_cols][ld_cols], ld_cols >= n_rays: the columns of
+ *          every ray, NaN (every column) for a ray that is not counted.
+ *   item   host or device [n_items] rox_wd_item; pivot, sums host or device [n_items][n_cols];
+ *          gram host or device [n_items][n_cols][n_cols], symmetric, both triangles written.
+ *          cols, item and gram may not all be NULL; pivot and sums go with item, sums with pivot,
+ *          gram with all three.
+ * Which rays count.  A ray is looked at only if its status is ROX_OK: no row and no aux value of
+ * any other ray is read.  An OK ray with an aux value or a column that is not finite adds to n_bad
+ * and to nothing else.  Every other OK ray is counted.
+ * Columns of an OK ray, in operation order (IEEE double, no FMA: every step is one NumPy float64
+ * operation; dot and cross products as rox_surface_transmission defines them).  Columns
+ * 0 .. n_aux - 1 are the aux values.  For the selected slot j, k = sel_slot[j], s = slot_ifc[k],
+ * p = (x, y, z), d and dst of that slot and b4 the previous slot's d carried into this frame as
+ * rox_surface_transmission carries it (rt.v of every interface in between, unfused, in the row's
+ * rt_order), the columns n_aux + 11*j + c are
+ *          n1 = |n_table[w][s-1]|, n2 = |n_table[w][s]|; at slot 0 b4 = d and n1 = n2 =
+ *          |n_table[w][0]|; at the last slot (the image) n2 = 0.
+ *          g = (n1*b4.x - n2*d.x, n1*b4.y - n2*d.y, n1*b4.z - n2*d.z): 0 at slot 0; n1*b4 at the
+ *          image, where a shift of the slot is a shift of the reference sphere's centre.
+ *   c = 0, 1, 2   g.x, g.y, g.z: a shift of the interface along its own axes.
+ *   c = 3, 4, 5   cross(p, g): a rotation about the interface's vertex ((r x p).g = r.(p x g)).
+ *   c = 6         g.z*(r2/(q*(1.0 + q))), r2 = x*x + y*y, q = sqrt(1.0 - ((ec*cv)*cv)*r2), cv and
+ *                 ec of the interface's rox_surface: a change of vertex curvature (d sag / d cv of
+ *                 the conic base) for the profiles ROX_SPHERICAL, ROX_CONIC, ROX_EVENPOLY and
+ *                 ROX_RADIALPOLY.  For the toroids, ROX_THINLENS, or a radicand that is not > 0:
+ *                 g.z*(r2/2.0).
+ *   c = 7         g.z*r2: power (a test-plate fit).
+ *   c = 8, 9      g.z*(x*x - y*y) and g.z*((x + x)*y): irregularity, astigmatic at 0 and 45 deg.
+ *   c = 10        dst: the index of the gap after this interface; 0.0 at the image slot.
+ * Reduction.  The pivot of an item is its counted ray of lowest index (an exact integer
+ * selection), pivot[c] that ray's column c; sums[c] = sum (col_c - pivot_c) and gram[a][b] = sum
+ * (col_a - pivot_a)*(col_b - pivot_b) over the counted rays, so that the host's cov = gram -
+ * sums sums^T / n subtracts nothing large (rox_surface_footprints' pivot).  n == 0: pivot is NaN,
+ * sums and gram are 0.  The Gram matrix is a rank-n update on the fp64 matrix cores, as
+ * rox_focus_zernike's: an item's rays in chunks (their number ceil(n_rays/512), at most 256; a
+ * function of n_rays alone), a chunk in tiles of 32 rays whose rows [col - pivot | 1] (zero for a
+ * ray that is not counted) are multiplied into 16x16 tiles of the upper triangle with
+ * v_mfma_f64_16x16x4_f64; the chunks' records are added in chunk order.  n, n_bad and the pivot
+ * ray are integer sums and a minimum.  No floating-point atomics: identical calls, host and
+ * device destinations, one call over n items against n calls over one item each, and a job split
+ * for the scratch bound give the same bits.  The order of summation inside a tile is the
+ * hardware's: sums and gram are not promised bit for bit against a host evaluation; cols, pivot
+ * and item are.
+ * n_items in [1, ROX_MAX_FOCUS_ITEMS], n_rays in [1, 2^28], ld >= n_rays.  Argument errors return
+ * ROX_E_ARG naming the parameter and item before anything is enqueued and leave the outputs
+ * untouched.  Scratch per launch is 32 MiB or, where that is more, what one item needs (the
+ * columns of one chunk of rays where they do not go to the caller's device memory, up to 8 MiB of
+ * chunk records of (n_cols + 1 rounded up to 16)^2 doubles, one running record, the outputs);
+ * larger jobs run as consecutive launches over fewer items, ranges of rays and groups of chunks
+ * with the same results.  Asynchronous on `stream` unless an output is host memory.          */
+#define ROX_WD_SLOT_COLS 11
+#define ROX_MAX_WD_AUX 32
+#define ROX_MAX_WD_COLS 512
+typedef struct rox_wd_item {
+    int64_t n;               /* rays counted                                                  */
+    int64_t n_bad;           /* OK rays left out for a value that is not finite               */
+    int64_t pivot_ray;       /* the counted ray of lowest index; -1 where n == 0              */
+} rox_wd_item;               /* 24 bytes */
+int rox_wave_differentials(rox_system *sys, uint32_t trace_flags, int32_t n_items, const rox_out *outs,
+                           int64_t n_rays, const int32_t *wvl_idx,
+                           int32_t n_sel, const int32_t *sel_slot,
+                           int32_t n_aux, const double *aux, int64_t aux_stride, int64_t ld_aux,
+                           double *cols, int64_t ld_cols,
+                           rox_wd_item *item, double *pivot, double *sums, double *gram, void *stream);
+
 /* chief-ray aiming ------------------------------------------------------- */
 /* One problem per (field, wavelength): trace.iterate_ray
  * (rayoptics/raytr/trace.py:313-415) as trace.aim_chief_ray calls it

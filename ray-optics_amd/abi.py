@@ -259,6 +259,16 @@ class WmapItem(C.Structure):
 MAX_WMAP_BINS = 1024        # include/roxtrace.h rox_weighted_maps: nbx, nby
 
 
+class WdItem(C.Structure):
+    """rox_wd_item: the rays of one item rox_wave_differentials counted, and its pivot ray"""
+    _fields_ = [('n', C.c_int64), ('n_bad', C.c_int64), ('pivot_ray', C.c_int64)]
+
+
+WD_SLOT_COLS = 11           # include/roxtrace.h ROX_WD_SLOT_COLS
+MAX_WD_AUX = 32             # ROX_MAX_WD_AUX
+MAX_WD_COLS = 512           # ROX_MAX_WD_COLS
+
+
 class Vig(C.Structure):
     _fields_ = [('fld', Field), ('start_dir', C.c_double * 2), ('unit_dir', C.c_double * 2),
                 ('xy', C.c_int32), ('wvl_idx', C.c_int32), ('stop_surf', C.c_int32),
@@ -292,6 +302,7 @@ assert C.sizeof(TxItem) == 72
 assert C.sizeof(SaItem) == 144
 assert C.sizeof(SegFocus) == 136
 assert C.sizeof(WmapItem) == 40
+assert C.sizeof(WdItem) == 24
 
 # every symbol include/roxtrace.h declares (checked by tests/test_abi.py) ...
 EXPORTS = ('rox_abi_version', 'rox_device_count', 'rox_set_device',
@@ -304,7 +315,8 @@ EXPORTS = ('rox_abi_version', 'rox_device_count', 'rox_set_device',
            'rox_spot_stats', 'rox_trace_through_focus', 'rox_trace_through_focus_grids',
            'rox_focus_psf', 'rox_focus_mtf', 'rox_focus_ee', 'rox_focus_gmtf', 'rox_focus_psf_ee',
            'rox_focus_zernike', 'rox_surface_footprints', 'rox_surface_transmission',
-           'rox_surface_thinfilm', 'rox_projected_solid_angle', 'rox_segment_foci', 'rox_weighted_maps')
+           'rox_surface_thinfilm', 'rox_projected_solid_angle', 'rox_segment_foci', 'rox_weighted_maps',
+           'rox_wave_differentials')
 # ... and the measurement / self-test helpers of include/roxtrace_diag.h
 DIAG_EXPORTS = ('rox_time_pupil_grid', 'rox_selftest_fp64', 'rox_diag_pack_launches')
 
@@ -394,6 +406,9 @@ def declare(lib):
     lib.rox_weighted_maps.restype = C.c_int
     lib.rox_weighted_maps.argtypes = [vp, C.c_uint32, i32, P(Out), i64, i32, vp, i64, vp, vp, i32, vp, i32, i32, vp, vp,
                                       vp, vp, vp]
+    lib.rox_wave_differentials.restype = C.c_int
+    lib.rox_wave_differentials.argtypes = [vp, C.c_uint32, i32, P(Out), i64, vp, i32, vp, i32, vp, i64, i64, vp, i64,
+                                           vp, vp, vp, vp, vp]
     lib.rox_time_pupil_grid.restype = C.c_int
     lib.rox_time_pupil_grid.argtypes = [vp, P(Field), P(Grid), i32, P(Opts),
                                         P(Out), vp, i32, P(dbl)]

@@ -1752,6 +1752,85 @@ def ghost_analysis(opt_model, flds=None, wvls=None, num_rays=64, coatings=None, 
     return out
 
 
+# ---- tolerancing from one trace: wavefront differentials ----------------------------------------
+def _compensator(pert, c):
+    """a compensator -> (name, coefficient vector): 'focus' (the image slot's dz), 'image_x' /
+    'image_y', ('thickness', g), or a tolerance.Tolerance"""
+    if c == 'focus':
+        return 'focus', pert.surface_decenter(pert.image, 'z')
+    if c in ('image_x', 'image_y'):
+        return c, pert.surface_decenter(pert.image, c[-1])
+    if isinstance(c, tuple) and len(c) == 2 and c[0] == 'thickness':
+        return f'thickness {int(c[1])}', pert.thickness(int(c[1]))
+    if hasattr(c, 'coef') and hasattr(c, 'name'):
+        return c.name, c.coef
+    raise ValueError(f"tolerance_sensitivity: compensator {c!r} is not 'focus', 'image_x', 'image_y', "
+                     "('thickness', g) or a Tolerance")
+
+
+def tolerance_sensitivity(opt_model, tolerances=None, flds=None, wvls=None, num_rays=64, compensators=('focus',),
+                          check_apertures=True, keep_cols=False, foc=0.0, grade='commercial', field_wts=None):
+    """As-built performance from ONE nominal trace (rox_wave_differentials): one FULL launch over
+    every (field, wavelength) -- ``num_rays`` x ``num_rays`` rays over each field's vignetted
+    pupil, as beam_footprints traces them -- one through-focus launch of the same grid with the
+    one plane ``foc`` for the nominal OPD, and one wave_differentials call with the OPD in waves
+    and the pupil coordinates as aux rows.  The rest is host algebra on the covariance of the
+    per-ray columns (tolerance.Quadratic): the RMS wavefront per field with every tolerance at
+    +- its magnitude after the ``compensators`` ('focus', 'image_x', 'image_y', ('thickness', g)
+    or a Tolerance; one value for all fields and wavelengths) have been set, RSS, Monte Carlo.
+    ``tolerances``: tolerance.Tolerance objects, or a callable taking the tolerance.Perturbations
+    of this call and returning them; None: tolerance.default_tolerances(``grade``).  First order:
+    the object-space rays are kept, the stop is not re-aimed, and a term of order (transverse
+    aberration x change of ray angle) is left out.  Returns
+    :class:`tolerance.ToleranceSensitivity`."""
+    from . import tolerance as T
+    from .trace import _launch_setup
+    what = 'tolerance_sensitivity'
+    num_rays = int(num_rays)
+    eng, flds, wvls, spectral_wts, fs, wis, opts_list, flags = _packet_items(opt_model, flds, wvls, num_rays,
+                                                                             check_apertures, what)
+    F, W = len(flds), len(wvls)
+    results = _trace_packets(eng, fs, wis, opts_list, num_rays)
+    grid = make_grid((-1., -1.), (1., 1.), num_rays)
+    planes, f2, w2, o2 = [], [], [], []
+    for fld in flds:
+        for wvl in wvls:
+            planes.append(_focus_planes(opt_model, fld, wvl, [float(foc)]))
+            kw = dict(check_apertures=bool(check_apertures), apply_vignetting=True)
+            _eng, f, wi, opts = _launch_setup(opt_model, fld, wvl, kw, abi.OUT_FAN)
+            f2.append(f)
+            w2.append(wi)
+            o2.append(opts)
+    _stats, rows = eng.trace_pupil_grids_focus(f2, w2, [grid] * (F * W), o2, planes, want_rows=True)
+    t = eng.torch
+    R = num_rays * num_rays
+    scale = t.from_numpy(_wave_scales(opt_model, wvls, F * W)).to(rows.rows.device)
+    ax = t.linspace(-1.0, 1.0, num_rays, dtype=t.float64, device=rows.rows.device)
+    aux = t.empty((F * W, 3, R), dtype=t.float64, device=rows.rows.device)
+    aux[:, 0] = rows.rows[:, 0, 2, :R] * scale[:, None]
+    aux[:, 1] = ax.repeat_interleave(num_rays)[None, :]
+    aux[:, 2] = ax.repeat(num_rays)[None, :]
+    item, pivot, sums, gram, cols = eng.wave_differentials(results, flags, wis, aux=aux, want_cols=keep_cols)
+    if (item['n'] < 2).any():
+        raise ValueError(f'{what}: an item has fewer than two rays through (n = {item["n"].tolist()})')
+    pert = T.Perturbations(eng.table, None, 3, wis, flags)
+    if tolerances is None:
+        tolerances = T.default_tolerances(pert, grade, units_per_nm=opt_model.nm_to_sys_units(1.0),
+                                          ref_wvl_idx=wis[0])
+    elif callable(tolerances):
+        tolerances = tolerances(pert)
+    tolerances = list(tolerances)
+    comps = [_compensator(pert, c) for c in compensators]
+    n_cols = pert.n_cols
+    cov = T.covariances(item, sums, gram).reshape(F, W, n_cols, n_cols)
+    if field_wts is None:
+        field_wts = [getattr(f, 'wt', 1.0) for f in flds]
+    quad = T.Quadratic(cov, _wave_scales(opt_model, wvls, F * W), [tol.coef for tol in tolerances],
+                       [c for _n, c in comps], spectral_wts, field_wts)
+    return T.ToleranceSensitivity(tolerances, [n for n, _c in comps], quad, item, pivot, sums, gram, flds, wvls,
+                                  image_cols=(pert.col(-1, 'dx'), pert.col(-1, 'dy')), cols=cols, num_rays=num_rays)
+
+
 # ---- MTF through focus ----------------------------------------------------------
 # the PSF stack through_focus_mtf holds at once: larger maps run rox_focus_psf / rox_focus_mtf
 # over consecutive groups of items (the results do not depend on the grouping)

@@ -106,26 +106,13 @@ struct FilmArgs : TxArgs {                      // n_rows is 4 or 16
     int32_t n_layers;
 };
 
-struct V3 {
-    double x, y, z;
-};
+// V3, dot, cross and carry (rt . v in the row's rt_order, unfused): rox_packets.hpp
+using rox::carry;
+using rox::cross;
+using rox::dot;
+using rox::V3;
 
-__device__ __forceinline__ double dot(const V3 &a, const V3 &b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ V3 cross(const V3 &a, const V3 &b)
-{
-    return V3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
-}
 __device__ __forceinline__ V3 over(const V3 &a, double s) { return V3{a.x / s, a.y / s, a.z / s}; }
-
-// rt . v, the columns summed in the row's rt_order, unfused
-__device__ __forceinline__ V3 carry(ctblp rt, bool c_order, const V3 &v)
-{
-    if (c_order)
-        return V3{(rt[1] * v.y + rt[0] * v.x) + rt[2] * v.z, (rt[4] * v.y + rt[3] * v.x) + rt[5] * v.z,
-                  (rt[7] * v.y + rt[6] * v.x) + rt[8] * v.z};
-    return V3{(rt[0] * v.x + rt[1] * v.y) + rt[2] * v.z, (rt[3] * v.x + rt[4] * v.y) + rt[5] * v.z,
-              (rt[6] * v.x + rt[7] * v.y) + rt[8] * v.z};
-}
 
 // E <- (ts*(s . E))*s + (tp*(p_in . E))*p_out
 __device__ __forceinline__ V3 through(const V3 &E, const V3 &s, const V3 &pi, const V3 &po, double ts, double tp)

@@ -1,7 +1,8 @@
 // rox_packets.hpp -- what the entries that walk the ROX_OUT_FULL packets of finished launches share
-// (footprint.hip, fresnel.hip, solidangle.hip, segfoci.hip, wmaps.hip): their argument checks, a
+// (footprint.hip, fresnel.hip, solidangle.hip, segfoci.hip, wmaps.hip, wavediff.hip): their argument checks, a
 // system's slot tables as their kernels read them, the tile their workgroups walk, the fixed-order
-// merge of a wave's records and that of their finishing kernels.
+// merge of a wave's records and that of their finishing kernels, and the carried direction of
+// fresnel.hip and wavediff.hip.
 #pragma once
 
 #include <cstring>
@@ -67,6 +68,30 @@ struct PacketSlots {
                 dst[slots[i]] = i;
     }
 };
+
+// ---- a ray's direction carried from one slot's frame into the next (rox_surface_transmission's
+// statement of it, which rox_wave_differentials promises to follow): three doubles, the dot and
+// cross products in the operation order include/roxtrace.h gives, and rt . v with the columns
+// summed in the row's rt_order, unfused.  P is a pointer to the staged row (kRtDoubles).
+struct V3 {
+    double x, y, z;
+};
+
+__device__ __forceinline__ double dot(const V3 &a, const V3 &b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+__device__ __forceinline__ V3 cross(const V3 &a, const V3 &b)
+{
+    return V3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
+}
+
+template <class P>
+__device__ __forceinline__ V3 carry(P rt, bool c_order, const V3 &v)
+{
+    if (c_order)
+        return V3{(rt[1] * v.y + rt[0] * v.x) + rt[2] * v.z, (rt[4] * v.y + rt[3] * v.x) + rt[5] * v.z,
+                  (rt[7] * v.y + rt[6] * v.x) + rt[8] * v.z};
+    return V3{(rt[0] * v.x + rt[1] * v.y) + rt[2] * v.z, (rt[3] * v.x + rt[4] * v.y) + rt[5] * v.z,
+              (rt[6] * v.x + rt[7] * v.y) + rt[8] * v.z};
+}
 
 // ---- the tile walk: a workgroup of kBlock threads owns kTile consecutive rays of one item
 // (blockIdx.y), kRays per thread, ray j of a thread kBlock rays after its ray j - 1, so that a wave

@@ -198,6 +198,9 @@ assert SEG_FOCUS_DTYPE.itemsize == C.sizeof(abi.SegFocus)
 
 # rox_wmap_item: the item records of weighted_maps
 WMAP_ITEM_DTYPE = np.dtype([(name, np.int64) for name in ('n_in', 'n_out', 'n_bad', 'q_in', 'q_out')])
+# rox_wd_item: what wave_differentials returns per item
+WD_ITEM_DTYPE = np.dtype([(name, np.int64) for name in ('n', 'n_bad', 'pivot_ray')])
+assert WD_ITEM_DTYPE.itemsize == C.sizeof(abi.WdItem)
 assert WMAP_ITEM_DTYPE.itemsize == C.sizeof(abi.WmapItem)
 
 
@@ -1529,6 +1532,58 @@ class TraceEngine:
             two = ((1023 - exp.to(t.int64)) << 52).view(t.float64)
             return wm.to(t.float64) * two[:, None, None], cnt, exp, item
         return np.ldexp(wm.astype(np.float64), -exp[:, None, None]), cnt, exp, item
+
+    @_in_flight
+    def wave_differentials(self, results, trace_flags, wvl_idxs, slots=None, aux=None, want_cols=False,
+                           on_device=False, want_gram=True):
+        """rox_wave_differentials over the FULL packets of finished launches (``results``,
+        ``trace_flags`` as surface_footprints; ``wvl_idxs`` as surface_transmission): per OK ray
+        the first-order change of optical path under the eleven perturbations of every selected
+        slot (``slots``: strictly increasing FULL-packet slots, None = all; tolerance.COLUMN_KINDS
+        names the eleven), behind the ``aux`` rows -- a contiguous float64 device tensor
+        [n_items, n_aux, >= R] of per-ray functions that join the covariance, or None.  Returns
+        ``(item, pivot, sums, gram, cols)``: a WD_ITEM_DTYPE array [n_items] (n, n_bad,
+        pivot_ray), float64 [n_items, n_cols] twice and [n_items, n_cols, n_cols] (None without
+        ``want_gram``) -- NumPy, or with ``on_device`` torch tensors (the records as uint8
+        [n_items, 24]: ``records_view``) -- and, with ``want_cols``, the columns left in HBM as a
+        float64 tensor [n_items, n_cols, R], NaN where a ray is not counted (else None)."""
+        t = self.torch
+        what = 'wave_differentials'
+        results, n_items, n_seg, R, outs = self._packets(results, trace_flags, what)
+        wi = np.ascontiguousarray(np.asarray(wvl_idxs, dtype=np.int32).reshape(-1))
+        if wi.shape[0] != n_items:
+            raise EngineError(f'{what}: {wi.shape[0]} wvl_idxs for {n_items} items')
+        sel = None
+        n_sel = n_seg
+        if slots is not None:
+            sel = np.ascontiguousarray(np.asarray(slots, dtype=np.int32).reshape(-1))
+            n_sel = int(sel.shape[0])
+        n_aux, p_aux, aux_stride, ld_aux = 0, None, 0, 0
+        if aux is not None:
+            if not hasattr(aux, 'data_ptr') or aux.dim() != 3 or aux.dtype != t.float64 or \
+                    not aux.is_contiguous() or not aux.is_cuda or int(aux.shape[0]) != n_items or \
+                    int(aux.shape[2]) < R:
+                raise EngineError(f'{what}: aux is a contiguous float64 device tensor [{n_items}, n_aux, R >= {R}]')
+            n_aux, ld_aux = int(aux.shape[1]), int(aux.shape[2])
+            p_aux, aux_stride = (aux.data_ptr() if n_aux else None), n_aux * ld_aux
+        n_cols = n_aux + abi.WD_SLOT_COLS * n_sel
+        if not 1 <= n_cols <= abi.MAX_WD_COLS:
+            raise EngineError(f'{what}: n_cols = n_aux + {abi.WD_SLOT_COLS}*n_sel = {n_cols} outside '
+                              f'[1, {abi.MAX_WD_COLS}]')
+        cols = t.empty((n_items, n_cols, R), dtype=t.float64, device=self.device) if want_cols else None
+        item, p_item = self._records_out(on_device, (n_items,), WD_ITEM_DTYPE)
+        pivot, p_pivot = self._out(on_device, (n_items, n_cols), np.float64, t.float64)
+        sums, p_sums = self._out(on_device, (n_items, n_cols), np.float64, t.float64)
+        gram, p_gram = self._out(on_device, (n_items, n_cols, n_cols), np.float64, t.float64) if want_gram \
+            else (None, None)
+        with t.cuda.device(self.device):
+            _check(self.lib.rox_wave_differentials(self._handle, int(trace_flags), n_items, outs, R, wi.ctypes.data,
+                                                   n_sel, sel.ctypes.data if sel is not None else None,
+                                                   n_aux, p_aux, aux_stride, ld_aux,
+                                                   cols.data_ptr() if cols is not None else None, R,
+                                                   p_item, p_pivot, p_sums, p_gram, self._stream()),
+                   'rox_wave_differentials')
+        return item, pivot, sums, gram, cols
 
     @_in_flight
     def focus_psf_ee(self, psf, pitch, centers, radii, want_centroid=True):
