@@ -124,7 +124,9 @@ int main(int argc, char **argv)
         memset(&out, 0, sizeof out);
         out.seg = (double *)d_pairs;
         out.n_hits = (int64_t *)d_count;
-        out.ld = (int64_t)n_rays;               /* room for every ray */
+        /* packed hits: ld is the room of seg in pairs, one for every ray.  (The other output
+         * modes write rows ld doubles apart: allocate those with ld = rox_packet_ld(n_rays).) */
+        out.ld = (int64_t)n_rays;
 
         CHECK(rox_trace_pupil_grid(sys, &fld, &grid, 0, &opts, &out, NULL));
         CHECK(rox_synchronize(NULL));

@@ -37,6 +37,14 @@ int rox_selftest_fp64(uint64_t n, uint64_t seed, uint64_t counts[4]);
  * ROX_PACK_TWO_PASS=1).  Tests use it to see which form a call took. */
 int rox_diag_pack_launches(uint64_t counts[2]);
 
+/* the workgroup -> tile map of a ROX_OUT_FULL launch, walked as the kernel walks it: `grid`
+ * workgroups stride over n_tiles tiles, tiles[t] = the tile that walk index t (workgroup
+ * t % grid on its pass t / grid) traces with `group` tiles per XCD run (0 = identity; the
+ * library's own choice, or ROX_FULL_TILE_GROUP, is not consulted).  wg0 = linear id of the
+ * launch item's first workgroup (blockIdx.y * gridDim.x of a batched launch).  No device needed. */
+int rox_diag_full_tile_map(int64_t n_tiles, int32_t group, int64_t grid, int32_t wg0,
+                           int64_t *tiles);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

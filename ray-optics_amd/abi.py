@@ -316,9 +316,10 @@ EXPORTS = ('rox_abi_version', 'rox_device_count', 'rox_set_device',
            'rox_focus_psf', 'rox_focus_mtf', 'rox_focus_ee', 'rox_focus_gmtf', 'rox_focus_psf_ee',
            'rox_focus_zernike', 'rox_surface_footprints', 'rox_surface_transmission',
            'rox_surface_thinfilm', 'rox_projected_solid_angle', 'rox_segment_foci', 'rox_weighted_maps',
-           'rox_wave_differentials')
+           'rox_wave_differentials', 'rox_packet_ld')
 # ... and the measurement / self-test helpers of include/roxtrace_diag.h
-DIAG_EXPORTS = ('rox_time_pupil_grid', 'rox_selftest_fp64', 'rox_diag_pack_launches')
+DIAG_EXPORTS = ('rox_time_pupil_grid', 'rox_selftest_fp64', 'rox_diag_pack_launches',
+                'rox_diag_full_tile_map')
 
 
 def declare(lib):
@@ -409,6 +410,8 @@ def declare(lib):
     lib.rox_wave_differentials.restype = C.c_int
     lib.rox_wave_differentials.argtypes = [vp, C.c_uint32, i32, P(Out), i64, vp, i32, vp, i32, vp, i64, i64, vp, i64,
                                            vp, vp, vp, vp, vp]
+    lib.rox_packet_ld.restype = i64
+    lib.rox_packet_ld.argtypes = [i64]
     lib.rox_time_pupil_grid.restype = C.c_int
     lib.rox_time_pupil_grid.argtypes = [vp, P(Field), P(Grid), i32, P(Opts),
                                         P(Out), vp, i32, P(dbl)]
@@ -416,4 +419,6 @@ def declare(lib):
     lib.rox_selftest_fp64.argtypes = [C.c_uint64, C.c_uint64, P(C.c_uint64)]
     lib.rox_diag_pack_launches.restype = C.c_int
     lib.rox_diag_pack_launches.argtypes = [P(C.c_uint64)]
+    lib.rox_diag_full_tile_map.restype = C.c_int
+    lib.rox_diag_full_tile_map.argtypes = [i64, i32, i64, i32, P(i64)]
     return lib

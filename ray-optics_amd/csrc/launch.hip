@@ -164,6 +164,24 @@ int64_t rays_per_launch()
     return v;
 }
 
+// FULL packets: tiles per XCD run of the workgroup -> tile map (rox_device.hpp full_tile_map()).
+// Measured (DESIGN.md section 3.1 "Stores", profiles/r17_full_placement.jsonl): with 32, a die's
+// workgroups of one round of 1024-thread workgroups write one contiguous eighth of every
+// packet row -- double Gauss 188.9 -> 182.1 us per 2^20 rays, .zmx zoom 192.0 -> 185.5,
+// lithography lens 681 -> 662; 16, 64 and 128 gain less, 2 to 8 lose.  Launches in small
+// workgroups (want_small(): they do not fill the chip several times over) keep the identity:
+// BASELINE configs[3] measured 32.6 us as it is, 32.9 mapped.
+// ROX_FULL_TILE_GROUP=<G> (read once; 0 = identity) sets the group of every FULL launch, small
+// workgroups included (A/B runs, tests).
+constexpr int32_t kFullTileGroup = 32;
+int32_t full_tile_group(bool small)
+{
+    static const long long env = env_int("ROX_FULL_TILE_GROUP", -1);
+    if (env >= 0)
+        return (int32_t)(env > kMaxTileGroup ? kMaxTileGroup : env);
+    return small ? 0 : kFullTileGroup;
+}
+
 // the leanest compiled instance that covers `need` (index into kInstances).
 // ROX_FORCE_INSTANCE=<index> (experiments: what a richer instance costs on a plain table) is
 // honoured when that instance covers the need.
@@ -347,6 +365,7 @@ int launch(rox_system *sys, TraceArgs &a, int gen, hipStream_t st)
     const int64_t total = a.n_rays;
     int64_t chunk_max = rays_per_launch();
     k.small = !prw && want_small(sys, total, a.opts.out_mode, kInstances[inst]);   // (per-ray-wavelength lists keep the regular kernels)
+    a.tile_group = a.opts.out_mode == ROX_OUT_FULL ? full_tile_group(k.small) : 0;
     const bool compact = a.opts.out_mode == ROX_OUT_HITS_COMPACT;
     StreamCtx *cx = nullptr;
     bool two_pass = false;
@@ -461,7 +480,38 @@ int launch(rox_system *sys, TraceArgs &a, int gen, hipStream_t st)
 
 }  // namespace rox
 
+// ---- include/roxtrace.h
+// The row pitch of a packet buffer of n_rays rays: the ray count rounded up to 4 KiB plus
+// kPadDoubles, an odd multiple of 2 KiB, so that the ~130 component rows a lane writes never
+// lie a power of two bytes apart.  Measured under the shipped kernel at 1024 x 1024
+// (profiles/r17_full_placement.jsonl): pads of 256 to 2304 doubles within 1 % of each other,
+// 0 and 64 slower (1 % and 2 % under the tile map, 16 % and 10 % without it), 8448 2 to 7 % slower
+// -- today's 256 stays.  The buffer never grows by more than max(256, n_rays / 16) doubles a
+// row: a small ragged grid, where the rounding alone would, gets the largest pitch of whole
+// 64-byte lines within that.
+extern "C" int64_t rox_packet_ld(int64_t n_rays)
+{
+    constexpr int64_t kPadDoubles = 256;
+    if (n_rays <= 0)
+        return 1;
+    const int64_t cap = n_rays / 16 > 256 ? n_rays / 16 : 256;
+    const int64_t want = (n_rays + 511) / 512 * 512 + kPadDoubles;
+    return want - n_rays <= cap ? want : (n_rays + cap) / 8 * 8;
+}
+
 // ---- include/roxtrace_diag.h
+extern "C" int rox_diag_full_tile_map(int64_t n_tiles, int32_t group, int64_t grid, int32_t wg0,
+                                      int64_t *tiles)
+{
+    if (n_tiles < 0 || n_tiles > INT32_MAX || group < 0 || group > rox::kMaxTileGroup || grid < 1 ||
+        wg0 < 0 || (n_tiles > 0 && !tiles))
+        return rox::fail(ROX_E_ARG, "rox_diag_full_tile_map: bad argument");
+    for (int64_t wg = 0; wg < grid; ++wg)
+        for (int64_t t = wg; t < n_tiles; t += grid)
+            tiles[t] = rox::full_tile_map(t, n_tiles, group, (uint32_t)wg0 % rox::kXcds);
+    return 0;
+}
+
 extern "C" int rox_diag_pack_launches(uint64_t counts[2])
 {
     if (!counts)

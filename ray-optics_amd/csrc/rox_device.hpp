@@ -306,6 +306,8 @@ struct TraceArgs {
     uint32_t epoch;
     // the first `small_tiles` tickets are tiles of kSmallTile rays (see compact_tiles())
     int32_t small_tiles;
+    // FULL: tiles per XCD run of the workgroup -> tile map (full_tile_map()); 0 = identity
+    int32_t tile_group;
     rox_field fld;
     rox_opts opts;
     rox_out out;
@@ -2331,6 +2333,31 @@ __host__ __device__ inline int64_t compact_tiles(int64_t n_rays, int32_t want_sm
     return s + (n_rays - s * kSmallTile + kB - 1) / kB;
 }
 
+// FULL tile placement.  The hardware deals consecutive workgroups of a launch round-robin over
+// the kXcds dies, so under the identity map die x writes tiles x, x + 8, ...: consecutive row
+// pieces of a packet row leave through eight different L2s.  full_tile_map() permutes the walk
+// index t of trace_tiles() (workgroup + pass x grid) so that, over each whole block of
+// kXcds * group consecutive tiles, the walk indices of one die -- those with (t + wg0) % kXcds
+// equal, wg0 the linear id of the item's first workgroup -- get `group` contiguous tiles.  The
+// ragged remainder and group <= 0 keep the identity.  A bijection of [0, n_tiles) for every
+// wg0 and grid; the die it names is the workgroup's own wherever the grid is a multiple of
+// kXcds (every capped grid on a chip whose CU count is).
+constexpr int kXcds = 8;
+// (32-bit arithmetic: a launch has at most 2^28 rays, so fewer than 2^31 tiles; group is
+// clamped by the host to kMaxTileGroup)
+constexpr int32_t kMaxTileGroup = 1 << 16;
+__host__ __device__ constexpr int64_t full_tile_map(int64_t t, int64_t n_tiles, int32_t group, uint32_t wg0)
+{
+    if (group <= 0)
+        return t;
+    const uint32_t span = (uint32_t)kXcds * (uint32_t)group;
+    const uint32_t start = (uint32_t)t / span * span;
+    if ((int64_t)start + span > n_tiles)
+        return t;
+    const uint32_t j = (uint32_t)t - start;
+    return (int64_t)(start + (j + wg0) % kXcds * (uint32_t)group + j / kXcds);
+}
+
 // ------------------------------------------------------------------ through focus
 // rox_trace_through_focus: a lane has traced its ray once (as for ROX_OUT_FAN) and evaluates it
 // at every focus plane with the very expressions of the FAN epilogue in trace_tiles() -- the
@@ -2568,6 +2595,8 @@ __device__ __forceinline__ void trace_tiles(ARGS &a)
             tile = (int64_t)__builtin_amdgcn_readfirstlane((int)s_tile);
         } else {
             tile = (int64_t)blockIdx.x + it * gridDim.x;
+            if constexpr (OUT_MODE == ROX_OUT_FULL)     // (blockIdx.y: the item of a batched launch)
+                tile = full_tile_map(tile, n_tiles, a.tile_group, blockIdx.y * gridDim.x % kXcds);
         }
         if (tile >= n_tiles)
             break;

@@ -147,6 +147,7 @@ int blocks_per_cu(int bs);
 int compact_blocks_per_cu();
 int32_t compact_small_want(const rox_system *sys, int64_t n_rays);
 bool want_small(const rox_system *sys, int64_t total_rays, int out_mode, int feat, int64_t n_items = 1);
+int32_t full_tile_group(bool small);
 int check_opts(const rox_system *sys, const rox_opts *o, const rox_out *out, int64_t n_rays);
 int check_field(const rox_field *fld);
 const TraceInstanceFns &trace_fns(int inst, const LaunchCfg &k);

@@ -333,6 +333,9 @@ int rox_trace_pupil_grids(rox_system *sys, int32_t n_grids, const rox_field *fld
     k.small = want_small(sys, (int64_t)n_grids * R, opts[0].out_mode, kInstances[inst], n_grids);
     const int bs = block_of(opts[0].out_mode, kInstances[inst], k.small);
     int64_t blocks = (R + bs - 1) / bs;
+    if (opts[0].out_mode == ROX_OUT_FULL)
+        for (int32_t i = 0; i < n_grids; ++i)
+            items[i].tile_group = full_tile_group(k.small);
     if (compact) {
         // per-item tickets
         if ((int64_t)n_grids > b.tickets_cap)

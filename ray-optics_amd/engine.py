@@ -256,13 +256,11 @@ def _f64(x, shape):
 
 
 def padded_ld(R):
-    """row pitch (in doubles) of the SoA packet buffer.  Rows exactly 2^k bytes
-    apart put one ray's 130 packet components on the same HBM channel; a pitch
-    of 2 KiB mod 4 KiB spreads them (tools/store_ld.hip: 5.9 vs 5.0 TB/s for the
-    same store stream)."""
-    if R <= 0:
-        return 1
-    return (R + 511) // 512 * 512 + 256
+    """row pitch (in doubles) of the SoA packet buffer: the native library's
+    ``rox_packet_ld`` (include/roxtrace.h), which C callers use too.  Rows exactly
+    2^k bytes apart put one ray's 130 packet components on the same HBM channel;
+    the library's pitch spreads them."""
+    return int(load_library().rox_packet_ld(int(R)))
 
 
 def _default_pool_budget():
