@@ -154,7 +154,7 @@ enum { ROX_CHECK_APERTURES = 1u,     /* raytrace.py:198-202                    *
  * traces at -- and the reduced-output modes (LAST, HITS, HITS_COMPACT, OPD, FAN), which are bound
  * by instruction issue, run on kernels that are still IEEE binary64 but use reciprocal /
  * reciprocal-square-root seeds with Newton-Raphson refinement, fused multiply-adds and Horner
- * series instead of NumPy's operation order (csrc/rox_device.hpp, "tolerance mode"; observed
+ * series instead of NumPy's operation order (csrc/rox_math_fast.hpp, "tolerance mode"; observed
  * deviation <= 1e-12).  A ray whose miss / total-internal-reflection radicand or aperture margin
  * lies within rounding of zero may be classified the other way.  The flag is a permission: the
  * library takes it where it buys time and answers bit-exactly (which is within any tolerance)

@@ -4,7 +4,7 @@
 
 hipcc cross-compiles without a GPU.  -ffp-contract=off is load-bearing: the
 kernels restate NumPy's unfused elementwise arithmetic and spell the BLAS dot
-sites as explicit fma() (see csrc/rox_device.hpp header).
+sites as explicit fma() (see csrc/rox_device.hpp header and csrc/rox_math.hpp).
 
 The trace kernel is compiled once per feature instance (csrc/inst_*.hip), each
 in its own translation unit so that the instances build in parallel; objects

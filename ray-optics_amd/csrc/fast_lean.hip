@@ -1,5 +1,5 @@
 // fast_lean.hip -- the tolerance-mode (ROX_FAST_FP64) trace kernels of feature instance
-// 0 (rox_device.hpp, "tolerance mode"): every output mode (FULL packets: taken by the host where they pay).  One translation unit per
+// 0 (rox_math_fast.hpp, "tolerance mode"): every output mode (FULL packets: taken by the host where they pay).  One translation unit per
 // instance so that the instances compile in parallel.
 #include "rox_device.hpp"
 

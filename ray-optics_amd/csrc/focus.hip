@@ -1,7 +1,7 @@
 // focus.hip -- rox_trace_through_focus and rox_trace_through_focus_grids (include/roxtrace.h): one
 // trace of a pupil grid evaluated at many focus positions, the host side and its two small
 // kernels (the pupil axes of several grid definitions, the finishing merge of the statistics).
-// The trace itself is trace_tiles<MODE_FOCUS> of rox_device.hpp.
+// The trace itself is trace_tiles<MODE_FOCUS> of rox_kernel.hpp.
 #include <algorithm>
 #include <cstdio>
 #include <cstring>

@@ -20,7 +20,7 @@
 #include <cstdint>
 
 #include "rox_bins.hpp"
-#include "rox_device.hpp"
+#include "rox_config.hpp"
 #include "rox_packets.hpp"
 
 namespace {

@@ -28,7 +28,7 @@
 #include <cstdint>
 #include <type_traits>
 
-#include "rox_device.hpp"
+#include "rox_math.hpp"
 #include "rox_packets.hpp"
 #include "rox_system.hpp"
 
@@ -268,7 +268,7 @@ __global__ __launch_bounds__(kBlock) void fresnel_kernel(const Args args)
     const ItemIn it = a.items[blockIdx.y];
     const int lane = threadIdx.x & 63;
     const int n_seg = a.n_seg;
-    // the tables through the constant address space (rox_device.hpp): a wave-uniform address there is
+    // the tables through the constant address space (rox_math.hpp): a wave-uniform address there is
     // a scalar load into SGPRs, and the stores of the partial records do not order it
     const ctbli slot_ifc = (ctbli)a.slot_ifc, model_of = (ctbli)a.model;
     const ctblp rt_of = (ctblp)a.rt, coat = (ctblp)a.coat;

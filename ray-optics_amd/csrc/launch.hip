@@ -19,7 +19,7 @@ bool force_gtab()
     return v;
 }
 
-// The LDS need of a launch of instance `inst` (rox_device.hpp trace_tiles), the packed-hits stash
+// The LDS need of a launch of instance `inst` (rox_kernel.hpp trace_tiles), the packed-hits stash
 // included.  gtab: the general instance over a table in global memory; otherwise gtab_of() says
 // where the instance reads it.  There the clear-aperture thresholds get an array instead.
 static size_t launch_lds(const rox_system *s, int inst, bool per_ray_wvl, bool fast, bool gtab, int out_mode)
@@ -35,7 +35,7 @@ static size_t launch_lds(const rox_system *s, int inst, bool per_ray_wvl, bool f
                ((size_t)s->n_wvls + N) * sizeof(double) + 2 * N * sizeof(int32_t);
     if (fast && !gtab)  // (mu, mu^2, sg) per (wavelength row, interface) behind the slot map
         b += Wn * 3 * N * sizeof(double);
-    if (out_mode == ROX_OUT_HITS_COMPACT)       // two tiles of packed pairs (rox_device.hpp)
+    if (out_mode == ROX_OUT_HITS_COMPACT)       // two tiles of packed pairs (rox_kernel.hpp)
         b += 16 + 2 * 16 * (size_t)block_of(ROX_OUT_HITS_COMPACT, feat);
     return up16(b);
 }
@@ -138,7 +138,7 @@ int compact_blocks_per_cu()
     return v > 0 ? v : 1;
 }
 
-// HITS_COMPACT: how many first tickets take small tiles (rox_device.hpp compact_tiles).
+// HITS_COMPACT: how many first tickets take small tiles (rox_args.hpp compact_tiles).
 // A launch that small tiles spread over no more workgroups than the chip has CUs (a
 // 256 x 256 grid: 256 tiles of 256 rays instead of 64 of 1024) runs all of it that way:
 // 30 vs 40 us into HBM, 41 vs 53 us into pinned memory.  Larger launches take full tiles
@@ -164,7 +164,7 @@ int64_t rays_per_launch()
     return v;
 }
 
-// FULL packets: tiles per XCD run of the workgroup -> tile map (rox_device.hpp full_tile_map()).
+// FULL packets: tiles per XCD run of the workgroup -> tile map (rox_args.hpp full_tile_map()).
 // Measured (DESIGN.md section 3.1 "Stores", profiles/r17_full_placement.jsonl): with 32, a die's
 // workgroups of one round of 1024-thread workgroups write one contiguous eighth of every
 // packet row -- double Gauss 188.9 -> 182.1 us per 2^20 rays, .zmx zoom 192.0 -> 185.5,
@@ -197,7 +197,7 @@ static int pick_instance(int need)
     return n - 1;
 }
 
-// Workgroup size of a launch (rox_device.hpp block_of()), measured rule
+// Workgroup size of a launch (rox_config.hpp block_of()), measured rule
 // (profiles/r05_block_rule.jsonl, tools/block_rule_sweep.py):
 //  * FULL packets (1024-thread workgroups, one per CU, whose waves write packet rows in step
 //    -- worth 13-23 % of the store rate on launches that fill the chip): a launch of at most

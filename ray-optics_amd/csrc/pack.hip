@@ -3,7 +3,7 @@
 // ROX_OUT_HITS_COMPACT is what SequentialModel.trace_grid(spot, ..., form='list',
 // append_if_none=False) returns (rayoptics/seq/sequential.py:1058-1085 around
 // rayoptics/mpl/axisarrayfigure.py:229-238): the (x, y) of the rays that got through, packed in
-// ray order.  The fused instance (rox_device.hpp trace_tiles<HITS_COMPACT>) compacts inside the
+// ray order.  The fused instance (rox_kernel.hpp trace_tiles<HITS_COMPACT>) compacts inside the
 // trace: one persistent 1024-thread workgroup per CU, three workgroup barriers and a look-back
 // per 1024 rays -- cheap on a shallow system, but on a deep one (44 interfaces: the lithography
 // lens of BASELINE configs[4]) or one with Newton iterations the waves of a tile finish far
@@ -13,7 +13,8 @@
 // written per survivor) that puts every pair exactly where the fused instance would have --
 // same ticket / tile-state / running-base protocol, so chunked launches, ROX_HITS_APPEND and
 // the capacity clamp behave identically.
-#include "rox_device.hpp"
+#include "rox_args.hpp"
+#include "rox_compact.hpp"
 
 namespace rox {
 

@@ -968,7 +968,7 @@ void launch_aim_instance(const AimArgs &a, size_t lds, hipStream_t st)
     hipLaunchKernelGGL(aim_kernel<FEAT>, dim3(a.wave_per_problem ? a.n : (a.n + 63) / 64), dim3(64), lds, st, a);
 }
 
-// what a translation unit csrc/search_<name>.hip defines for its instance (rox_device.hpp
+// what a translation unit csrc/search_<name>.hip defines for its instance (rox_args.hpp
 // SearchInstanceFns)
 #define ROX_SEARCH_INSTANCE(name, FEAT)                                                          \
     SearchInstanceFns search_##name = {launch_aim_instance<FEAT>, launch_enp_instance<FEAT>, \

@@ -6,7 +6,7 @@
 #include <mutex>
 #include <vector>
 
-#include "rox_device.hpp"
+#include "rox_args.hpp"
 #include "rox_host.hpp"
 
 namespace rox {
@@ -51,7 +51,7 @@ struct StageArena {
 };
 
 // trace_entries.hip rox_trace_pupil_grids: the launch items of a batch of MORE than kInlineItems
-// items (smaller batches travel in the kernel argument, rox_device.hpp BatchArgs).  Written into
+// items (smaller batches travel in the kernel argument, rox_args.hpp BatchArgs).  Written into
 // one of kSlots pinned slots (a slot is reused only after the copy that read it has completed),
 // copied to d_items in stream order, read by the kernel through scalar loads.
 struct BatchItems {

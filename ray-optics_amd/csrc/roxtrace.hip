@@ -237,7 +237,7 @@ int rox_system_create(const rox_surface *rows, int32_t n_ifcs, const double *n_t
         for (int i = 0; i < n_ifcs; ++i) {
             drows[i].pub = rows[i];
             // device copy only: rt is exactly the identity (every centred interface) -- the
-            // kernels then transform with `v + 0.0` instead of the dgemv chain (rox_device.hpp)
+            // kernels then transform with `v + 0.0` instead of the dgemv chain (rox_ray.hpp)
             {
                 static const double eye[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
                 bool ident = true;
@@ -246,7 +246,7 @@ int rox_system_create(const rox_surface *rows, int32_t n_ifcs, const double *n_t
                 // device copy of flags: bit 1 = identity rotation (bit 0 = ROX_SURF_CV_INT_ZERO)
                 drows[i].pub.flags = (rows[i].flags & ROX_SURF_CV_INT_ZERO) | (ident ? 2 : 0);
             }
-            // device copy only: `-self.cv` as Spherical/Conic.df forms it (rox_device.hpp reads
+            // device copy only: `-self.cv` as Spherical/Conic.df forms it (rox_ray.hpp reads
             // it from the cR slot, which only toroids use): +0.0 for an integer-zero curvature
             if (rows[i].profile <= ROX_CONIC)
                 drows[i].pub.cR = (rows[i].flags & ROX_SURF_CV_INT_ZERO) ? 0.0 : -rows[i].cv;

@@ -15,7 +15,7 @@
 #include <cfloat>
 #include <cstdint>
 
-#include "rox_device.hpp"
+#include "rox_config.hpp"
 #include "rox_packets.hpp"
 
 namespace {

@@ -1,8 +1,8 @@
-// selftest.hip -- rox_selftest_fp64 (include/roxtrace_diag.h): the slim fp64 paths of rox_device.hpp
+// selftest.hip -- rox_selftest_fp64 (include/roxtrace_diag.h): the slim fp64 paths of rox_math.hpp
 // against the plain operators, on the device.
 #include <hip/hip_runtime.h>
 
-#include "rox_device.hpp"
+#include "rox_math.hpp"
 #include "rox_host.hpp"
 #include "../../include/roxtrace_diag.h"
 

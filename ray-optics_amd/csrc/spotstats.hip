@@ -19,7 +19,6 @@
 #include <cstring>
 
 #include "rox_bins.hpp"
-#include "rox_device.hpp"
 #include "rox_host.hpp"
 
 namespace rox {

@@ -371,7 +371,7 @@ int rox_trace_pupil_grids(rox_system *sys, int32_t n_grids, const rox_field *fld
     if (blocks > cap)
         blocks = cap;
     k.grid = dim3((unsigned)blocks, (unsigned)n_grids);
-    // a few items: in the kernel argument itself (rox_device.hpp BatchArgs) -- nothing to upload
+    // a few items: in the kernel argument itself (rox_args.hpp BatchArgs) -- nothing to upload
     static const bool no_inline = env_flag("ROX_BATCH_NO_INLINE");  // (the A/B switch of tools/ab_bench.py)
     if (n_grids <= kInlineItems && !no_inline) {
         k.n_inline = n_grids;

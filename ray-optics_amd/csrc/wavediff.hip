@@ -28,7 +28,7 @@
 #include <cfloat>
 #include <cstdint>
 
-#include "rox_device.hpp"
+#include "rox_math.hpp"
 #include "rox_packets.hpp"
 #include "rox_system.hpp"
 

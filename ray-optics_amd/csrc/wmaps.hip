@@ -23,7 +23,7 @@
 #include <cstring>
 
 #include "rox_bins.hpp"
-#include "rox_device.hpp"
+#include "rox_config.hpp"
 #include "rox_packets.hpp"
 
 namespace {

@@ -1,5 +1,5 @@
 """CPU checks of the FULL-packet placement helpers of libroxtrace.so: the workgroup -> tile map
-(rox_device.hpp full_tile_map(), through rox_diag_full_tile_map) is a bijection of [0, n_tiles)
+(rox_args.hpp full_tile_map(), through rox_diag_full_tile_map) is a bijection of [0, n_tiles)
 for every group size and grid, and rox_packet_ld keeps its footprint cap.  No device needed."""
 import ctypes as C
 import os

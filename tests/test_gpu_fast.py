@@ -1,5 +1,5 @@
 """-m gpu: ROX_FAST_FP64, the tolerance mode of the reduced-output modes (include/roxtrace.h;
-csrc/rox_device.hpp "tolerance mode").  north_star's bar is 1e-10 on ray intercepts against the
+csrc/rox_math_fast.hpp "tolerance mode").  north_star's bar is 1e-10 on ray intercepts against the
 reference's NumPy path; the default kernels are bit-exact, these are not, so here the bar is
 asserted directly:
 

@@ -266,7 +266,7 @@ def _flat_table(aps, max_aperture=50.0):
 ])
 def test_aperture_edges_decided_as_the_square_root_decides_them(aps):
     """the aperture tests compare x^2 + y^2 with a staged threshold instead of taking the square
-    root (rox_device.hpp sqrt_le_threshold / stage_aperture_thresholds).  Rays parallel to the
+    root (rox_math.hpp sqrt_le_threshold, rox_profiles.hpp stage_aperture_thresholds).  Rays parallel to the
     axis land on a flat surface exactly where they start, so their start points are laid within
     +-6 ulp of every circular edge (radius + fuzz, along 97 directions) and of the rectangular
     ones: blocked / passed must be the oracle's -- which takes the square root, like the

@@ -1,5 +1,5 @@
 """-m gpu, round 6: tables beyond the LDS of a workgroup (the general instance over a table left
-in global memory, read with scalar loads: rox_device.hpp F_GTAB) -- a SequentialModel has no
+in global memory, read with scalar loads: rox_config.hpp F_GTAB) -- a SequentialModel has no
 size limit (rayoptics/seq/sequential.py:167-202), round 5 returned ROX_E_UNSUPPORTED beyond
 ~220 interfaces -- and the same instance forced onto the regular fixtures."""
 import ctypes as C
@@ -396,7 +396,7 @@ def test_degenerate_rays_bit_exact(name):
 @pytest.mark.parametrize('mode', [abi.OUT_FULL, abi.OUT_HITS, abi.OUT_HITS_COMPACT])
 def test_batches_either_side_of_the_inline_limit(n_items, mode):
     """rox_trace_pupil_grids hands up to 16 items to the kernel inside its argument block and
-    uploads larger batches to device memory (csrc/rox_device.hpp BatchArgs): item for item the
+    uploads larger batches to device memory (csrc/rox_args.hpp BatchArgs): item for item the
     same bits as the single-grid entry, on both sides of the limit and in a sequence that
     alternates between the two on one stream"""
     from rayoptics_amd import workloads

@@ -23,7 +23,8 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-ffp-contract=off', '-fno-fast-math']
+sys.path.insert(0, os.path.join(ROOT, 'ray-optics_amd'))
+from build import FLAGS  # noqa: E402  (the build's own flags: the assembly audited is the assembly shipped)
 
 CLASSES = [
     ('fp64 fma', r'v_fma_f64|v_fmac_f64'),

@@ -9,7 +9,7 @@
 //      [segment][component][ray], a barrier per segment, ten 8-byte nt stores per lane and
 //      segment in bursts of 4 / 3 / 3, optionally `work` dependent fp64 FMAs in front of each
 //      burst (the trace arithmetic's place) -- with the row pitch (n + pad doubles) and the
-//      workgroup -> tile map (rox_device.hpp full_tile_map(), `group` tiles per XCD run) as
+//      workgroup -> tile map (rox_args.hpp full_tile_map(), `group` tiles per XCD run) as
 //      parameters.
 //   hipcc --offload-arch=gfx950 -O3 tools/store_map.hip -o store_map && ./store_map [stride|shape]
 #include <hip/hip_runtime.h>
@@ -39,7 +39,7 @@ __global__ void __launch_bounds__(512) stride_blocks(char *buf, int window_log2,
     }
 }
 
-// the tile map of the trace kernel (csrc/rox_device.hpp full_tile_map(), wg0 = 0)
+// the tile map of the trace kernel (csrc/rox_args.hpp full_tile_map(), wg0 = 0)
 __host__ __device__ constexpr long tile_map(long t, long n_tiles, int group)
 {
     if (group <= 0)
