@@ -37,6 +37,16 @@ int rox_selftest_fp64(uint64_t n, uint64_t seed, uint64_t counts[4]);
  * ROX_PACK_TWO_PASS=1).  Tests use it to see which form a call took. */
 int rox_diag_pack_launches(uint64_t counts[2]);
 
+/* how many trace-kernel launches this process has issued in each form (a batched launch
+ * counts once): counts[(inst * 2 + fast) * 2 + small], the first n of 32 counters.
+ * inst = 0..6, the compiled feature instances in the order the host tries them (lean, even,
+ * radial, poly, aplist, evenap, general), 7 = the general instance over a table in global
+ * memory; fast = the tolerance-mode twin; small = the small-workgroup kernels were asked for
+ * (ROX_OUT_HITS_COMPACT has no such kernel: its fused launches count under the launch rule's
+ * answer all the same).  Entries past the 32nd are set to 0.  Tests use it to see which kernel
+ * a call took. */
+int rox_diag_trace_launches(uint64_t *counts, int32_t n);
+
 /* the workgroup -> tile map of a ROX_OUT_FULL launch, walked as the kernel walks it: `grid`
  * workgroups stride over n_tiles tiles, tiles[t] = the tile that walk index t (workgroup
  * t % grid on its pass t / grid) traces with `group` tiles per XCD run (0 = identity; the

@@ -319,7 +319,7 @@ EXPORTS = ('rox_abi_version', 'rox_device_count', 'rox_set_device',
            'rox_wave_differentials', 'rox_packet_ld')
 # ... and the measurement / self-test helpers of include/roxtrace_diag.h
 DIAG_EXPORTS = ('rox_time_pupil_grid', 'rox_selftest_fp64', 'rox_diag_pack_launches',
-                'rox_diag_full_tile_map')
+                'rox_diag_full_tile_map', 'rox_diag_trace_launches')
 
 
 def declare(lib):
@@ -421,4 +421,6 @@ def declare(lib):
     lib.rox_diag_pack_launches.argtypes = [P(C.c_uint64)]
     lib.rox_diag_full_tile_map.restype = C.c_int
     lib.rox_diag_full_tile_map.argtypes = [i64, i32, i64, i32, P(i64)]
+    lib.rox_diag_trace_launches.restype = C.c_int
+    lib.rox_diag_trace_launches.argtypes = [P(C.c_uint64), i32]
     return lib

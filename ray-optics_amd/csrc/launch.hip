@@ -239,9 +239,15 @@ bool want_small(const rox_system *sys, int64_t total_rays, int out_mode, int fea
 }
 
 // the entry points of trace instance kInstances[inst] -- or of its tolerance-mode twin, or of the
-// general instance over a table in global memory -- as launch_setup chose in k
+// general instance over a table in global memory -- as launch_setup chose in k.  Every launch
+// of a trace kernel asks here (launch(), the batched entry, the through-focus entry), so this
+// is where rox_diag_trace_launches counts them by form.
+constexpr int kTraceForms = 32;      // (inst * 2 + fast) * 2 + small; inst 7 = the global-table general instance
+static std::atomic<uint64_t> g_trace_launches[kTraceForms];
 const TraceInstanceFns &trace_fns(int inst, const LaunchCfg &k)
 {
+    g_trace_launches[((k.gtab ? 7 : inst) * 2 + (k.fast ? 1 : 0)) * 2 + (k.small ? 1 : 0)]
+        .fetch_add(1, std::memory_order_relaxed);
 #define ROX_TRACE_FNS(name, FEAT) &trace_##name,
 #define ROX_TRACE_FAST_FNS(name, FEAT) &trace_##name##_fast,
     static const TraceInstanceFns *const fns[] = {ROX_TRACE_INSTANCES(ROX_TRACE_FNS)};
@@ -518,5 +524,14 @@ extern "C" int rox_diag_pack_launches(uint64_t counts[2])
         return rox::fail(ROX_E_ARG, "null argument");
     counts[0] = rox::g_fused_pack_launches.load();
     counts[1] = rox::g_two_pass_launches.load();
+    return 0;
+}
+
+extern "C" int rox_diag_trace_launches(uint64_t *counts, int32_t n)
+{
+    if (!counts || n < 0)
+        return rox::fail(ROX_E_ARG, "rox_diag_trace_launches: bad argument");
+    for (int32_t i = 0; i < n; ++i)
+        counts[i] = i < rox::kTraceForms ? rox::g_trace_launches[i].load(std::memory_order_relaxed) : 0;
     return 0;
 }

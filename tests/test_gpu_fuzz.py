@@ -98,6 +98,13 @@ def random_rays(rng, tbl, R):
     return pt0, d
 
 
+# rays with status OK per seed, the three modes summed, as the oracle counts them on the CPU:
+# most of these systems let few rays through (tests/test_gpu_stratified.py is the suite's test on
+# rays that traverse); the numbers also pin the generator's random stream
+EXPECTED_OK = (9480, 336, 6, 8859, 195, 0, 9228, 8178, 1794, 9102, 1314, 2430,
+               9267, 1842, 678, 8973, 3270, 1077, 8217, 411, 168, 4860, 555, 2070)
+
+
 @pytest.mark.parametrize('seed', range(24))
 def test_random_systems_bit_exact(seed):
     from oracle import oracle
@@ -132,4 +139,4 @@ def test_random_systems_bit_exact(seed):
         assert np.array_equal(dev.op, orc.op, equal_nan=True)
         n_ok += int((dev.status == 0).sum())
     eng.close()
-    assert n_ok >= 0
+    assert n_ok == EXPECTED_OK[seed]
