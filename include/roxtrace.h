@@ -1299,6 +1299,58 @@ int rox_wave_differentials(rox_system *sys, uint32_t trace_flags, int32_t n_item
                            double *cols, int64_t ld_cols,
                            rox_wd_item *item, double *pivot, double *sums, double *gram, void *stream);
 
+/* Image simulation: what a scene looks like through the lens.  rox_varying_blur convolves a
+ * picture with a point spread function that changes across it -- given at the nodes of a
+ * rectilinear grid and blended between them by hat functions, every SOURCE pixel spreading with
+ * its own local PSF -- and rox_image_warp resamples a picture under a displacement field given on
+ * such a grid (distortion).  Neither reads a system: the PSF stack is the caller's, for instance
+ * rox_weighted_maps of the node fields' packets on the detector's pixel pitch.
+ *   scene  host or device [C][H][W] float64; out likewise, written whole.  scene and out may not
+ *          overlap.  1 <= C <= 16, 1 <= H, W <= 16384.
+ *   psf    host or device [C][GY][GX][S][S], S odd in [1, 65], r = (S - 1)/2: tap [a][b] is the
+ *          light displaced by (a - r) rows and (b - r) columns.
+ *   node_y HOST [GY], node_x HOST [GX]: finite, strictly increasing pixel coordinates; they may
+ *          lie outside the picture or between pixels.  1 <= GY*GX <= ROX_MAX_FOCUS_ITEMS.
+ *   flags  ROX_BLUR_EDGE_ZERO or ROX_BLUR_EDGE_REPLICATE.
+ * Arithmetic, in operation order (IEEE double, no FMA).  The hat weights wy[0 .. GY - 1] of source
+ * row i: with GY == 1, or i < node_y[0], wy[0] = 1; with i >= node_y[GY-1], wy[GY-1] = 1;
+ * otherwise, k such that node_y[k] <= i < node_y[k+1], t = (i - node_y[k]) / (node_y[k+1] -
+ * node_y[k]), wy[k] = 1 - t and wy[k+1] = t; every other weight is 0.  wx[0 .. GX - 1] of source
+ * column j likewise from node_x.  The weighted source of node n = (ky, kx) is
+ *          sw_n(i, j) = scene[c][i][j] * (wy[ky] * wx[kx])
+ * and an output starts at acc = 0 and takes, over the nodes in row-major order and inside a node
+ * over the taps (a, b) in row-major order,
+ *          acc = acc + sw_n(i - (a - r), j - (b - r)) * psf[c][n][a][b]
+ * A source outside the picture is skipped with ROX_BLUR_EDGE_ZERO; with ROX_BLUR_EDGE_REPLICATE
+ * its row and column are clamped into the picture (the weights are those of the clamped pixel).
+ * Terms whose hat weight is exactly zero may be skipped: results compare equal with ==, where
+ * +0 == -0.  Inputs are finite; anything else is unspecified.  With the zero edge and a stack
+ * whose every node sums to g, the output holds g times the scene's light up to what leaves the
+ * frame.  Identical calls, and host and device arrays, give the same bits.
+ * rox_image_warp:
+ *   in     host or device [C][H][W]; out likewise; they may not overlap.
+ *   disp   HOST [GY][GX][2] = (dy, dx) in pixels at the nodes, finite.
+ * With k, ty the cell and fraction t of OUTPUT row i as above (k = 0, ty = 0 before the first node
+ * or with GY == 1; k = GY - 1, ty = 0 from the last node on; a row k + 1 that does not exist is
+ * read as row k, its factor being 0), l, tx those of column j and D = disp[.][.][0]:
+ *          dy = (1 - ty)*((1 - tx)*D[k][l] + tx*D[k][l+1]) + ty*((1 - tx)*D[k+1][l] + tx*D[k+1][l+1])
+ * and dx likewise from disp[.][.][1].  y = i + dy, x = j + dx, y0 = floor(y), fy = y - y0 (x0 and
+ * fx likewise) and, I = in[c] with a tap outside the picture read as 0,
+ *          out = (1 - fy)*((1 - fx)*I[y0][x0] + fx*I[y0][x0+1]) + fy*((1 - fx)*I[y0+1][x0] + fx*I[y0+1][x0+1])
+ * A zero displacement returns the input (its bits, but +0 for -0).
+ * Argument errors return ROX_E_ARG naming the parameter before anything is enqueued and without
+ * touching a device.  Host pictures and stacks are mirrored in device scratch of their size.
+ * Asynchronous on `stream` unless scene / in, psf or out is host memory.                      */
+#define ROX_BLUR_EDGE_ZERO 0u
+#define ROX_BLUR_EDGE_REPLICATE 1u
+int rox_varying_blur(int32_t C, int32_t H, int32_t W, const double *scene,
+                     int32_t S, int32_t GY, int32_t GX, const double *psf,
+                     const double *node_y, const double *node_x,
+                     double *out, uint32_t flags, void *stream);
+int rox_image_warp(int32_t C, int32_t H, int32_t W, const double *in,
+                   int32_t GY, int32_t GX, const double *node_y, const double *node_x,
+                   const double *disp, double *out, void *stream);
+
 /* chief-ray aiming ------------------------------------------------------- */
 /* One problem per (field, wavelength): trace.iterate_ray
  * (rayoptics/raytr/trace.py:313-415) as trace.aim_chief_ray calls it

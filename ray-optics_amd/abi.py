@@ -268,6 +268,11 @@ WD_SLOT_COLS = 11           # include/roxtrace.h ROX_WD_SLOT_COLS
 MAX_WD_AUX = 32             # ROX_MAX_WD_AUX
 MAX_WD_COLS = 512           # ROX_MAX_WD_COLS
 
+BLUR_EDGE_ZERO = 0          # include/roxtrace.h ROX_BLUR_EDGE_*
+BLUR_EDGE_REPLICATE = 1
+MAX_BLUR_TAPS = 65          # rox_varying_blur: S
+MAX_BLUR_CHANNELS = 16      # C
+
 
 class Vig(C.Structure):
     _fields_ = [('fld', Field), ('start_dir', C.c_double * 2), ('unit_dir', C.c_double * 2),
@@ -316,7 +321,7 @@ EXPORTS = ('rox_abi_version', 'rox_device_count', 'rox_set_device',
            'rox_focus_psf', 'rox_focus_mtf', 'rox_focus_ee', 'rox_focus_gmtf', 'rox_focus_psf_ee',
            'rox_focus_zernike', 'rox_surface_footprints', 'rox_surface_transmission',
            'rox_surface_thinfilm', 'rox_projected_solid_angle', 'rox_segment_foci', 'rox_weighted_maps',
-           'rox_wave_differentials', 'rox_packet_ld')
+           'rox_wave_differentials', 'rox_packet_ld', 'rox_varying_blur', 'rox_image_warp')
 # ... and the measurement / self-test helpers of include/roxtrace_diag.h
 DIAG_EXPORTS = ('rox_time_pupil_grid', 'rox_selftest_fp64', 'rox_diag_pack_launches',
                 'rox_diag_full_tile_map', 'rox_diag_trace_launches')
@@ -410,6 +415,10 @@ def declare(lib):
     lib.rox_wave_differentials.restype = C.c_int
     lib.rox_wave_differentials.argtypes = [vp, C.c_uint32, i32, P(Out), i64, vp, i32, vp, i32, vp, i64, i64, vp, i64,
                                            vp, vp, vp, vp, vp]
+    lib.rox_varying_blur.restype = C.c_int
+    lib.rox_varying_blur.argtypes = [i32, i32, i32, vp, i32, i32, i32, vp, vp, vp, vp, C.c_uint32, vp]
+    lib.rox_image_warp.restype = C.c_int
+    lib.rox_image_warp.argtypes = [i32, i32, i32, vp, i32, i32, vp, vp, vp, vp, vp]
     lib.rox_packet_ld.restype = i64
     lib.rox_packet_ld.argtypes = [i64]
     lib.rox_time_pupil_grid.restype = C.c_int

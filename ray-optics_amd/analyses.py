@@ -22,6 +22,9 @@
                         direction, from the rays in HBM (rox_focus_gmtf)
   relative_illumination (new) radiometric relative illumination from the image-space solid
                         angle of each field's pupil grid (rox_projected_solid_angle)
+  image_simulation   (new) a scene through the lens: geometric polychromatic PSFs of a grid of
+                        field nodes (rox_weighted_maps), a field-varying blur and the distortion
+                        warp (rox_varying_blur, rox_image_warp)
 """
 import numpy as np
 
@@ -1750,6 +1753,304 @@ def ghost_analysis(opt_model, flds=None, wvls=None, num_rays=64, coatings=None, 
     out = Ghosts(found, skipped, records, slots, signal, spectral_wts, kept if keep_packets else None, gmaps)
     out.trace_flags = flags
     return out
+
+
+# ---- image simulation: field-varying blur and distortion of a scene ------------------------------
+def hat_cells(coord, node):
+    """the cell k and fraction t of every coordinate among the strictly increasing ``node``, as
+    rox_varying_blur places a pixel (include/roxtrace.h): k = 0, t = 0 before the first node or
+    with one node; k = len - 1, t = 0 from the last node on; else node[k] <= coord < node[k + 1]
+    and t = (coord - node[k]) / (node[k + 1] - node[k])"""
+    coord = np.asarray(coord, dtype=np.float64)
+    node = np.asarray(node, dtype=np.float64)
+    k = np.zeros(coord.shape, dtype=np.int64)
+    t = np.zeros(coord.shape, dtype=np.float64)
+    if len(node) > 1:
+        last = coord >= node[-1]
+        k[last] = len(node) - 1
+        mid = ~(coord < node[0]) & ~last
+        km = np.searchsorted(node, coord[mid], 'right') - 1
+        k[mid] = km
+        t[mid] = (coord[mid] - node[km]) / (node[km + 1] - node[km])
+    return k, t
+
+
+def hat_interp(v, node_y, node_x, y, x):
+    """node values ``v`` [GY, GX, ...] blended by the hat functions at the points (y, x) (arrays of
+    one shape): constant beyond the outermost nodes"""
+    v = np.asarray(v, dtype=np.float64)
+    k, ty = hat_cells(y, node_y)
+    l, tx = hat_cells(x, node_x)
+    k1, l1 = np.minimum(k + 1, v.shape[0] - 1), np.minimum(l + 1, v.shape[1] - 1)
+    ty = ty.reshape(ty.shape + (1,) * (v.ndim - 2))
+    tx = tx.reshape(tx.shape + (1,) * (v.ndim - 2))
+    return (1.0 - ty) * ((1.0 - tx) * v[k, l] + tx * v[k, l1]) + ty * ((1.0 - tx) * v[k1, l] + tx * v[k1, l1])
+
+
+def distortion_displacement(node_y, node_x, err, steps=8):
+    """The displacement field rox_image_warp takes, on the node grid, from the distortion ``err``
+    [GY, GX, 2] = (real - ideal) chief-ray point at the nodes in pixels (row, column): the light of
+    the ideal point q lands at q + e(q), so the output pixel p shows q = p + D with D = -e(p + D),
+    solved by ``steps`` fixed-point steps from D = 0, e blended between the nodes by the hat
+    functions.  A step shrinks the error by the steepest slope of the blended e (a few per cent
+    for a camera lens: under 5 %, eight steps reach 1e-9 px)."""
+    err = np.asarray(err, dtype=np.float64)
+    py, px = np.meshgrid(np.asarray(node_y, dtype=np.float64), np.asarray(node_x, dtype=np.float64), indexing='ij')
+    d = np.zeros_like(err)
+    for _ in range(int(steps)):
+        d = -hat_interp(err, node_y, node_x, py + d[..., 0], px + d[..., 1])
+    return d
+
+
+def _chief_ray_image_pts(opt_model, flds, wvls, what, prepared=None):
+    """[F, W, 2] the image point (x, y) of the chief ray of every (field, wavelength), field-major:
+    one small launch (pupil (0, 0) is the first ray of a 2 x 2 grid, and the fixed point of the
+    vignetting map) written straight to the host.  ``prepared``: the (engine, fields, wavelength
+    indices, options) of _packet_items, else each item is set up as _packet_items does"""
+    if prepared is None:
+        fs, wis, opts_list = [], [], []
+        for fld in flds:
+            for wvl in wvls:
+                eng, f, wi, opts = _launch_setup(opt_model, fld, wvl, dict(check_apertures=False,
+                                                                           apply_vignetting=True), abi.OUT_FULL)
+                fs.append(f), wis.append(wi), opts_list.append(opts)
+    else:
+        eng, fs, wis, opts_list = prepared
+    host = eng.trace_pupil_grids_host(fs, wis, make_grid((0., 0.), (1., 1.), 2), opts_list)
+    pts = np.empty((len(fs), 2))
+    for i, h in enumerate(host):
+        if int(h.status[0]) != abi.OK:
+            raise ValueError(f'{what}: the chief ray of field {i // len(wvls)} at {wvls[i % len(wvls)]} nm '
+                             f'does not reach the image (status {int(h.status[0])})')
+        pts[i] = h.seg[-1, 0:2, 0]
+    return pts.reshape(len(flds), len(wvls), 2)
+
+
+class SimulatedImage:
+    """What :func:`image_simulation` returns.
+
+    ``image``          [C, H, W] (or [H, W] as the scene came) the simulated picture
+    ``blurred``        the picture before the distortion warp (``image`` itself without one)
+    ``psfs``           [C, GY, GX, S, S] the PSF stack, tap [a][b] = rows, columns; in HBM
+    ``node_px``        (node_y [GY], node_x [GX]) the nodes in pixel coordinates
+    ``image_pts``      [node, wvl, 2] the chief-ray image point (x, y) of every node and wavelength
+    ``distortion_px``  [GY, GX, 2] (real - ideal) chief-ray point in pixels (row, column), or None
+    ``displacement``   [GY, GX, 2] what the warp took (distortion_displacement), or None
+    ``gain``           [C, node] the PSF sums: the node's relative transmission, vignetting
+                       included, times ``window_share``
+    ``window_share``   [C, node] the share of the node's light inside its PSF window (NaN: none)"""
+
+    def __init__(self, image, blurred, psfs, node_px, image_pts, distortion_px, displacement, gain, window_share):
+        self.image, self.blurred, self.psfs, self.node_px = image, blurred, psfs, node_px
+        self.image_pts, self.distortion_px, self.displacement = image_pts, distortion_px, displacement
+        self.gain, self.window_share = gain, window_share
+
+
+def _field_measure(fov, xy):
+    """the quantity the ideal image point is linear in, of field coordinates (x, y) in the units of
+    ``fov``: the tangents of the chief ray's direction for an angular field, else the height"""
+    x, y = float(xy[0]), float(xy[1])
+    if fov.key[1] != 'angle':
+        return np.array([x, y])
+    ax, ay = np.deg2rad(x), np.deg2rad(y)
+    return np.array([np.tan(ax), np.tan(ay) / np.cos(ax)])
+
+
+def _field_of_measure(fov, u):
+    if fov.key[1] != 'angle':
+        return float(u[0]), float(u[1])
+    ax = np.arctan(u[0])
+    return float(np.rad2deg(ax)), float(np.rad2deg(np.arctan(u[1] * np.cos(ax))))
+
+
+def _simulation_nodes(opt_model, nodes, H, W, pitch, what):
+    """a live model's node fields on a regular gy x gx grid of ideal image points spanning the
+    picture, edge pixels included -> (fields row-major, node_y, node_x, ideal points [n, 2]).
+    The ideal map is linear in the field measure, its slope the real chief-ray image point (at the
+    central wavelength) of 1/1024 of the outermost field per unit measure."""
+    import copy
+    from .trace import aim_chief_rays
+    from .workloads import TableModel
+    if isinstance(opt_model, TableModel):
+        raise ValueError(f'{what}: a TableModel carries prebuilt fields only: pass flds and node_px')
+    gy, gx = int(nodes[0]), int(nodes[1])
+    if gy < 1 or gx < 1 or gy * gx + 1 > abi.MAX_FOCUS_ITEMS:
+        raise ValueError(f'{what}: nodes {nodes!r} outside 1 to {abi.MAX_FOCUS_ITEMS - 1} in all')
+    fov = opt_model['osp']['fov']
+    scale = float(fov.value) if fov.is_relative else 1.0
+    _value, k = fov.max_field()
+    outer = fov.fields[k]
+    u_outer = _field_measure(fov, (outer.x * scale, outer.y * scale))
+    if not np.any(u_outer):
+        raise ValueError(f'{what}: the outermost field is on the axis: the ideal map has no slope')
+
+    def field_at(u):
+        f = copy.copy(outer)
+        x, y = _field_of_measure(fov, u)
+        f.x, f.y = x / scale, y / scale
+        f.vux = f.vuy = f.vlx = f.vly = 0.0
+        f.chief_ray = f.ref_sphere = None
+        return f
+
+    def aim(flds):
+        for f, a in zip(flds, aim_chief_rays(opt_model, flds)):
+            f.aim_info = a
+
+    u_small = u_outer / 1024.0
+    probe = [field_at(u_small)]
+    aim(probe)
+    r_small = _chief_ray_image_pts(opt_model, probe, [opt_model['osp']['wvls'].central_wvl], what)[0, 0]
+    slope = float(np.dot(r_small, u_small) / np.dot(u_small, u_small))
+    if not (np.isfinite(slope) and slope != 0.0):
+        raise ValueError(f'{what}: the chief ray of a small field gives no image scale')
+    node_y = np.linspace(0.0, H - 1.0, gy) if gy > 1 else np.array([(H - 1) / 2.0])
+    node_x = np.linspace(0.0, W - 1.0, gx) if gx > 1 else np.array([(W - 1) / 2.0])
+    ideal = np.array([[(x - (W - 1) / 2.0) * pitch, (y - (H - 1) / 2.0) * pitch] for y in node_y for x in node_x])
+    flds = [field_at(r / slope) for r in ideal]
+    aim(flds)
+    return flds, node_y, node_x, ideal
+
+
+def image_simulation(opt_model, scene, pixel_pitch, nodes=(5, 5), flds=None, node_px=None, ideal_pts=None, wvls=None,
+                     channels=None, num_rays=128, psf_size=33, check_apertures=True, distortion=True, edge='zero',
+                     on_device=False):
+    """What a scene looks like through the lens, on the device: sharp where the lens is sharp,
+    soft and darker where it is not, with the colour fringes of lateral colour and the lens's
+    distortion.  ``scene`` is [H, W] or [C, H, W]; the image frame's origin is the centre of the
+    picture, columns along +x and rows along +y, ``pixel_pitch`` in system units.
+
+    1. Nodes.  On a live model ``nodes`` = (gy, gx) puts node fields on a regular grid of ideal
+       image points spanning the picture, edge pixels included: copies of the outermost field
+       without vignetting factors, aimed in one batch; the ideal map is linear in the field (in its
+       tangents for an angular field), its slope taken from the real chief ray of 1/1024 of the
+       outermost field, and assumes a rotationally symmetric lens.  With ``flds`` (gy*gx prebuilt
+       fields, row-major) and ``node_px`` = (node_y, node_x) the nodes are taken as given -- a
+       workloads.TableModel works this way; ``ideal_pts`` [gy*gx, 2] = (x, y), needed for the
+       distortion, is then optional.
+    2. One FULL launch of every node x wavelength item, ``num_rays`` x ``num_rays`` rays over the
+       node's pupil, and one small launch for their chief rays.
+    3. PSFs: per channel one rox_weighted_maps call, one map per node, the node's wavelengths
+       its items with the channel's spectral factors -- ``channels`` None: one channel weighted by
+       the spectral weights; else a [C, n_wvl] matrix, RGB responses for instance (a [H, W] scene
+       is then seen by every channel).  The window of ``psf_size`` bins of one pixel is centred on
+       the node's chief-ray image point at the reference (first given, else central) wavelength, so
+       lateral colour stays in the PSF.  A ray's weight is the item's spectral factor times the
+       share of the unit pupil box the field's vignetting factors leave (a prebuilt field's grid
+       covers the shrunken box; a live node has none and the clear apertures vignette).  The stack
+       is scaled by the reciprocal of the usable flux (inside the window or not) of the channel's
+       brightest node and stays in HBM.
+    4. rox_varying_blur and, with ``distortion`` where the ideal points are known,
+       rox_image_warp by :func:`distortion_displacement`.
+
+    Limits.  Geometric PSFs only: right where the spot, not the aperture, sets the contrast.  A
+    PSF's shape is not stretched by the local distortion.  Vignetting is counted; cos^4 and the
+    area change of distortion are not (:func:`relative_illumination` has those).  No coatings.
+    A node more than 1 % of whose light misses its window raises a warning: enlarge ``psf_size``.
+    Returns :class:`SimulatedImage`; with ``on_device`` its pictures are torch tensors."""
+    import warnings
+    from .engine import WMAP_ITEM_DTYPE, records_view
+    what = 'image_simulation'
+    S, pitch = int(psf_size), float(pixel_pitch)
+    if not (1 <= S <= abi.MAX_BLUR_TAPS and S % 2 == 1):
+        raise ValueError(f'{what}: psf_size {psf_size} is not odd in [1, {abi.MAX_BLUR_TAPS}]')
+    if not (np.isfinite(pitch) and pitch > 0.0):
+        raise ValueError(f'{what}: pixel_pitch {pixel_pitch!r} is not finite and > 0')
+    if edge not in ('zero', 'replicate'):
+        raise ValueError(f"{what}: edge is 'zero' or 'replicate', not {edge!r}")
+    if not hasattr(scene, 'shape'):
+        scene = np.asarray(scene, dtype=np.float64)
+    shape = tuple(int(n) for n in scene.shape)
+    if len(shape) not in (2, 3):
+        raise ValueError(f'{what}: scene is [H, W] or [C, H, W], not {shape}')
+    H, W = shape[-2:]
+    if flds is None:
+        flds, node_y, node_x, ideal_pts = _simulation_nodes(opt_model, nodes, H, W, pitch, what)
+    else:
+        if node_px is None:
+            raise ValueError(f'{what}: flds needs node_px = (node_y, node_x)')
+        node_y = np.asarray(node_px[0], dtype=np.float64).reshape(-1)
+        node_x = np.asarray(node_px[1], dtype=np.float64).reshape(-1)
+        flds = list(flds)
+        if len(flds) != len(node_y) * len(node_x):
+            raise ValueError(f'{what}: {len(flds)} flds for {len(node_y)} x {len(node_x)} nodes')
+    GY, GX = len(node_y), len(node_x)
+    N = GY * GX
+    ref_first = wvls is not None and len(wvls) > 0
+    eng, flds, wvls, spectral_wts, fs, wis, opts_list, flags = _packet_items(opt_model, flds, wvls, int(num_rays),
+                                                                             check_apertures, what)
+    Wn = len(wvls)
+    factors = np.asarray(spectral_wts if channels is None else channels, dtype=np.float64).reshape(-1, Wn)
+    C = factors.shape[0]
+    if not (1 <= C <= abi.MAX_BLUR_CHANNELS and np.isfinite(factors).all() and (factors >= 0).all()):
+        raise ValueError(f'{what}: channels is [C, {Wn}], finite and >= 0, C in [1, {abi.MAX_BLUR_CHANNELS}]')
+    if len(shape) == 3 and shape[0] != C:
+        raise ValueError(f'{what}: the scene has {shape[0]} channels, channels {C}')
+    t = eng.torch
+    scene_t = scene if isinstance(scene, t.Tensor) else t.from_numpy(np.ascontiguousarray(scene, dtype=np.float64))
+    scene_t = scene_t.to(device=eng.device, dtype=t.float64).reshape(-1, H, W)
+    if len(shape) == 2 and C > 1:
+        scene_t = scene_t.expand(C, H, W)
+    scene_t = scene_t.contiguous()
+
+    # the chief rays: the window centres, and the distortion
+    image_pts = _chief_ray_image_pts(opt_model, flds, wvls, what, (eng, fs, wis, opts_list)).reshape(N, Wn, 2)
+    # the reference wavelength of _packet_items: the first one given, else the central one
+    ref = 0 if ref_first else wvls.index(float(opt_model['osp']['wvls'].central_wvl))
+    centre = image_pts[:, ref]
+    window = np.concatenate([centre, np.full((N, 2), S * pitch / 2.0)], axis=1)
+
+    # a field's vignetting factors shrink the pupil box its grid covers: a ray stands for less pupil
+    area = np.array([(2.0 - getattr(f, 'vlx', 0.0) - getattr(f, 'vux', 0.0)) / 2.0 *
+                     ((2.0 - getattr(f, 'vly', 0.0) - getattr(f, 'vuy', 0.0)) / 2.0) for f in flds])
+    results = _trace_packets(eng, fs, wis, opts_list, int(num_rays))
+    psfs = t.empty((C, GY, GX, S, S), dtype=t.float64, device=eng.device)
+    gain, share = np.zeros((C, N)), np.full((C, N), np.nan)
+    for c in range(C):
+        maps, _cnt, exp, item = eng.weighted_maps(results, flags, item_factor=(area[:, None] * factors[c]).reshape(-1),
+                                                  item_map=np.repeat(np.arange(N), Wn), n_maps=N, window=window,
+                                                  bins=S, on_device=True)
+        flux_in, flux = simulation_flux(records_view(item, WMAP_ITEM_DTYPE), exp.cpu().numpy(), N)
+        top = flux.max()
+        if top > 0.0:
+            # x is the maps' first axis; the product with the reciprocal is one IEEE rounding wherever it runs
+            psfs[c] = (maps.transpose(1, 2) * (1.0 / float(top))).reshape(GY, GX, S, S)
+            gain[c] = flux_in / top
+            share[c] = np.where(flux > 0.0, flux_in / np.where(flux > 0.0, flux, 1.0), np.nan)
+        else:
+            psfs[c] = 0.0
+    del results
+    low = np.argwhere(share < 0.99)
+    if len(low):
+        c, n = low[np.argmin(share[low[:, 0], low[:, 1]])]
+        warnings.warn(f'{what}: {len(low)} (channel, node) PSF windows miss more than 1 % of their light '
+                      f'(channel {c}, node {n}: {1 - share[c, n]:.1%}): enlarge psf_size', stacklevel=2)
+
+    blurred = eng.varying_blur(scene_t, psfs, node_y, node_x, edge=edge, on_device=True)
+    image, err, disp = blurred, None, None
+    if ideal_pts is not None:
+        ideal = np.asarray(ideal_pts, dtype=np.float64).reshape(N, 2)
+        err = ((centre - ideal) / pitch)[:, ::-1].reshape(GY, GX, 2)        # (x, y) -> (row, column)
+        if distortion:
+            disp = distortion_displacement(node_y, node_x, err)
+            image = eng.image_warp(blurred, node_y, node_x, disp, on_device=True)
+    if len(shape) == 2 and C == 1:
+        image, blurred = image[0], blurred[0]
+    if not on_device:
+        blurred = blurred.cpu().numpy()
+        image = blurred if disp is None else image.cpu().numpy()
+    elif disp is None:
+        image = blurred
+    return SimulatedImage(image, blurred, psfs, (node_y, node_x), image_pts, err, disp, gain, share)
+
+
+def simulation_flux(item, scale_exp, n_nodes):
+    """(the flux inside the window, the usable flux) [n_nodes] of the nodes' maps from the item
+    records and scale exponents of image_simulation's rox_weighted_maps call (items node-major):
+    the integer sums of a node's items, converted as the maps are"""
+    q_in = item['q_in'].reshape(n_nodes, -1).sum(axis=1)
+    q_all = q_in + item['q_out'].reshape(n_nodes, -1).sum(axis=1)
+    e = -np.asarray(scale_exp, dtype=np.int64)
+    return np.ldexp(q_in.astype(np.float64), e), np.ldexp(q_all.astype(np.float64), e)
 
 
 # ---- tolerancing from one trace: wavefront differentials ----------------------------------------

@@ -1531,6 +1531,77 @@ class TraceEngine:
             return wm.to(t.float64) * two[:, None, None], cnt, exp, item
         return np.ldexp(wm.astype(np.float64), -exp[:, None, None]), cnt, exp, item
 
+    def _picture(self, what, name, x, tail):
+        """a float64 picture or stack of an image-simulation entry, ``tail`` trailing axes behind
+        an optional channel axis -> (the array the call reads, kept by the caller; its pointer; its
+        shape with the channel axis; whether it came without one).  A torch tensor must be
+        contiguous float64 on this engine's device; anything else goes through NumPy."""
+        t = self.torch
+        if isinstance(x, t.Tensor):
+            if x.dtype != t.float64 or not x.is_contiguous() or not x.is_cuda or x.device != self.device:
+                raise EngineError(f'{what}: {name} as a tensor is contiguous float64 on {self.device}')
+            ptr = x.data_ptr()
+        else:
+            x = np.ascontiguousarray(x, dtype=np.float64)
+            ptr = x.ctypes.data
+        if x.ndim not in (tail, tail + 1):
+            raise EngineError(f'{what}: {name} has {tail} or {tail + 1} axes, not {x.ndim}')
+        bare = x.ndim == tail
+        shape = ((1,) if bare else ()) + tuple(int(n) for n in x.shape)
+        return x, ptr, shape, bare
+
+    def _node_axes(self, what, node_y, node_x):
+        ny = np.ascontiguousarray(np.asarray(node_y, dtype=np.float64).reshape(-1))
+        nx = np.ascontiguousarray(np.asarray(node_x, dtype=np.float64).reshape(-1))
+        if not (1 <= ny.shape[0] and 1 <= nx.shape[0] and ny.shape[0] * nx.shape[0] <= abi.MAX_FOCUS_ITEMS):
+            raise EngineError(f'{what}: 1 to {abi.MAX_FOCUS_ITEMS} nodes, got {ny.shape[0]} x {nx.shape[0]}')
+        return ny, nx
+
+    @_in_flight
+    def varying_blur(self, scene, psf, node_y, node_x, edge='zero', on_device=False):
+        """rox_varying_blur: ``scene`` [H, W] or [C, H, W] convolved with the PSFs ``psf``
+        [GY, GX, S, S] or [C, GY, GX, S, S] given at the nodes ``node_y`` [GY] x ``node_x`` [GX]
+        (pixel coordinates, strictly increasing) and blended between them by hat functions, every
+        source pixel spreading with its own local PSF; tap [a][b] is the light displaced by
+        a - (S - 1)/2 rows and b - (S - 1)/2 columns.  ``edge``: 'zero' (light from outside the
+        picture is none) or 'replicate'.  Pictures and stacks are contiguous float64 torch tensors
+        on this engine's device, or anything NumPy converts.  Returns the picture in the scene's
+        shape -- NumPy, or with ``on_device`` a torch tensor.  include/roxtrace.h states the
+        arithmetic; tests/imgsim_ref.py restates it."""
+        t = self.torch
+        what = 'varying_blur'
+        scene, p_scene, (C, H, W), bare = self._picture(what, 'scene', scene, 2)
+        psf, p_psf, pshape, _b = self._picture(what, 'psf', psf, 4)
+        ny, nx = self._node_axes(what, node_y, node_x)
+        S = pshape[-1]
+        if pshape != (C, ny.shape[0], nx.shape[0], S, S):
+            raise EngineError(f'{what}: psf {pshape} is not [{C}, {ny.shape[0]}, {nx.shape[0]}, S, S]')
+        if edge not in ('zero', 'replicate'):
+            raise EngineError(f"{what}: edge is 'zero' or 'replicate', not {edge!r}")
+        flags = abi.BLUR_EDGE_REPLICATE if edge == 'replicate' else abi.BLUR_EDGE_ZERO
+        out, p_out = self._out(on_device, (C, H, W), np.float64, t.float64)
+        with t.cuda.device(self.device):
+            _check(self.lib.rox_varying_blur(C, H, W, p_scene, S, ny.shape[0], nx.shape[0], p_psf, ny.ctypes.data,
+                                             nx.ctypes.data, p_out, flags, self._stream()), 'rox_varying_blur')
+        return out[0] if bare else out
+
+    @_in_flight
+    def image_warp(self, image, node_y, node_x, disp, on_device=False):
+        """rox_image_warp: ``image`` [H, W] or [C, H, W] resampled bilinearly at (i + dy, j + dx),
+        (dy, dx) the displacements ``disp`` [GY, GX, 2] (pixels, host) at the nodes blended
+        bilinearly between them; a tap outside the picture reads 0.  Arrays and the return as
+        varying_blur."""
+        t = self.torch
+        what = 'image_warp'
+        image, p_in, (C, H, W), bare = self._picture(what, 'image', image, 2)
+        ny, nx = self._node_axes(what, node_y, node_x)
+        d = _f64(disp, (ny.shape[0], nx.shape[0], 2))
+        out, p_out = self._out(on_device, (C, H, W), np.float64, t.float64)
+        with t.cuda.device(self.device):
+            _check(self.lib.rox_image_warp(C, H, W, p_in, ny.shape[0], nx.shape[0], ny.ctypes.data, nx.ctypes.data,
+                                           d.ctypes.data, p_out, self._stream()), 'rox_image_warp')
+        return out[0] if bare else out
+
     @_in_flight
     def wave_differentials(self, results, trace_flags, wvl_idxs, slots=None, aux=None, want_cols=False,
                            on_device=False, want_gram=True):
