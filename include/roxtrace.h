@@ -1351,6 +1351,56 @@ int rox_image_warp(int32_t C, int32_t H, int32_t W, const double *in,
                    int32_t GY, int32_t GX, const double *node_y, const double *node_x,
                    const double *disp, double *out, void *stream);
 
+/* Huygens point spread functions on the detector's pixel grid, through focus.  Every OK ray is a
+ * plane wavelet with its own amplitude, phase and direction of arrival; their complex sum is
+ * taken at the pixels of a product grid, for every plane of every item, and squared.  The entry
+ * reads no system: the rows are the caller's (analyses.huygens_psf builds them from one
+ * ROX_OUT_LAST and one ROX_OUT_OPD launch).
+ *   rows   DEVICE [n_items][4][ld] = phi, xi, eta, zeta: phi in cycles, (xi, eta, zeta) =
+ *          n (L, M, N) / lambda of the ray at the image, in cycles per system unit.  Only the
+ *          first n_rays rays count, and of those only the ones with status ROX_OK; the rows of a
+ *          failed ray are never read, and it enters the sum as a zero.
+ *   amp    DEVICE [n_items][ld], the wavelets' amplitudes a_r, or NULL (every a_r = 1, with the
+ *          bits of an array of ones).
+ *   status DEVICE [n_items][ld].
+ *   planes HOST [n_items][n_planes][3] = (x0, y0, dz), finite: pixel (a, b) of plane k is the
+ *          image point (x0 + a pitch_x, y0 + b pitch_y), displaced dz along the image z axis.
+ *   psf    optional, DEVICE [n_items][n_planes][nx][ny]; field optional, DEVICE [...][nx][ny][2]
+ *          = (re, im) of U; stats optional, host or device [n_items][n_planes].  Not all NULL.
+ * Arithmetic (IEEE double; every product and sum below is one rounding, summed left to right, no
+ * contraction into FMA):
+ *          t_A = phi + zeta*dz + xi*x0 + eta*y0 + xi*(a*pitch_x)         t_B = eta*(b*pitch_y)
+ * each reduced as rox_focus_gmtf reduces its arguments, r = t - rint(t) (exact), (s, c) =
+ * sincospi(2 r), and
+ *          A[k, a][r] = a_r (c_A + i s_A)      B[b][r] = c_B + i s_B
+ *          U[k][a][b] = sum over r of A[k, a][r] B[b][r]      psf = re(U)^2 + im(U)^2
+ * The sum over r runs on the fp64 matrix cores in ascending r; its rounding is that of a sum of
+ * 2 n_rays products in some fixed order, the same for every element, plane and call.
+ * rox_huygens_stats of a plane: n the OK rays; norm = (sum of a_r)^2, the peak of a perfect
+ * wavefront; sum the sum of psf over the window; peak its maximum, at pixel (peak_ix, peak_iy)
+ * (the first in row-major order); strehl = psf at the pixel nearest the plane's origin, (a, b) =
+ * (rint(-x0/pitch_x), rint(-y0/pitch_y)) clamped into the window, over norm -- meaningful when
+ * the caller puts the origin on a pixel.  With n == 0 every double is NaN and the pixel is
+ * (-1, -1); psf and field are then zero.  Every reduction runs in a fixed order without floating
+ * point atomics: identical calls give identical bits, host and device stats alike, however the
+ * job is split.
+ * n_items in [1, ROX_MAX_FOCUS_ITEMS], n_planes in [1, ROX_MAX_FOCUS_PLANES], nx and ny in
+ * [1, 4096], ld in [1, 2^28], n_rays in [1, ld], pitch_x and pitch_y finite and > 0.  Argument
+ * errors return ROX_E_ARG naming the parameter before anything is enqueued.  Scratch (the
+ * operands and U) is bounded by 1 GiB per launch; larger jobs run as consecutive launches over
+ * items, or over the planes of one item, with the same results.  The least a launch holds is one
+ * plane: about 16 n_rays (nx' + ny') bytes, nx' and ny' the pixel counts rounded up to 64; a shape
+ * whose single plane exceeds the bound is an argument error (n_rays).  Asynchronous on `stream` unless stats is host memory.                                */
+typedef struct rox_huygens_stats {
+    int64_t n;
+    double norm, sum, peak, strehl;
+    int32_t peak_ix, peak_iy;
+} rox_huygens_stats;         /* 48 bytes */
+int rox_huygens_psf(int32_t n_items, int32_t n_planes, int64_t n_rays,
+                    const double *rows, int64_t ld, const double *amp, const uint8_t *status,
+                    const double *planes, int32_t nx, int32_t ny, double pitch_x, double pitch_y,
+                    double *psf, double *field, rox_huygens_stats *stats, void *stream);
+
 /* chief-ray aiming ------------------------------------------------------- */
 /* One problem per (field, wavelength): trace.iterate_ray
  * (rayoptics/raytr/trace.py:313-415) as trace.aim_chief_ray calls it

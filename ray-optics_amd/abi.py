@@ -272,6 +272,13 @@ BLUR_EDGE_ZERO = 0          # include/roxtrace.h ROX_BLUR_EDGE_*
 BLUR_EDGE_REPLICATE = 1
 MAX_BLUR_TAPS = 65          # rox_varying_blur: S
 MAX_BLUR_CHANNELS = 16      # C
+MAX_HUYGENS_PIXELS = 4096   # rox_huygens_psf: nx, ny
+
+
+class HuygensStats(C.Structure):
+    """rox_huygens_stats"""
+    _fields_ = [('n', C.c_int64), ('norm', C.c_double), ('sum', C.c_double), ('peak', C.c_double),
+                ('strehl', C.c_double), ('peak_ix', C.c_int32), ('peak_iy', C.c_int32)]
 
 
 class Vig(C.Structure):
@@ -321,7 +328,8 @@ EXPORTS = ('rox_abi_version', 'rox_device_count', 'rox_set_device',
            'rox_focus_psf', 'rox_focus_mtf', 'rox_focus_ee', 'rox_focus_gmtf', 'rox_focus_psf_ee',
            'rox_focus_zernike', 'rox_surface_footprints', 'rox_surface_transmission',
            'rox_surface_thinfilm', 'rox_projected_solid_angle', 'rox_segment_foci', 'rox_weighted_maps',
-           'rox_wave_differentials', 'rox_packet_ld', 'rox_varying_blur', 'rox_image_warp')
+           'rox_wave_differentials', 'rox_packet_ld', 'rox_varying_blur', 'rox_image_warp',
+           'rox_huygens_psf')
 # ... and the measurement / self-test helpers of include/roxtrace_diag.h
 DIAG_EXPORTS = ('rox_time_pupil_grid', 'rox_selftest_fp64', 'rox_diag_pack_launches',
                 'rox_diag_full_tile_map', 'rox_diag_trace_launches')
@@ -419,6 +427,8 @@ def declare(lib):
     lib.rox_varying_blur.argtypes = [i32, i32, i32, vp, i32, i32, i32, vp, vp, vp, vp, C.c_uint32, vp]
     lib.rox_image_warp.restype = C.c_int
     lib.rox_image_warp.argtypes = [i32, i32, i32, vp, i32, i32, vp, vp, vp, vp, vp]
+    lib.rox_huygens_psf.restype = C.c_int
+    lib.rox_huygens_psf.argtypes = [i32, i32, i64, vp, i64, vp, vp, vp, i32, i32, C.c_double, C.c_double, vp, vp, vp, vp]
     lib.rox_packet_ld.restype = i64
     lib.rox_packet_ld.argtypes = [i64]
     lib.rox_time_pupil_grid.restype = C.c_int

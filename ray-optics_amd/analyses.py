@@ -1913,7 +1913,7 @@ def _simulation_nodes(opt_model, nodes, H, W, pitch, what):
 
 def image_simulation(opt_model, scene, pixel_pitch, nodes=(5, 5), flds=None, node_px=None, ideal_pts=None, wvls=None,
                      channels=None, num_rays=128, psf_size=33, check_apertures=True, distortion=True, edge='zero',
-                     on_device=False):
+                     on_device=False, psf='geometric', psf_oversample=3, psf_ref_foc=0.0):
     """What a scene looks like through the lens, on the device: sharp where the lens is sharp,
     soft and darker where it is not, with the colour fringes of lateral colour and the lens's
     distortion.  ``scene`` is [H, W] or [C, H, W]; the image frame's origin is the centre of the
@@ -1942,7 +1942,19 @@ def image_simulation(opt_model, scene, pixel_pitch, nodes=(5, 5), flds=None, nod
     4. rox_varying_blur and, with ``distortion`` where the ideal points are known,
        rox_image_warp by :func:`distortion_displacement`.
 
-    Limits.  Geometric PSFs only: right where the spot, not the aperture, sets the contrast.  A
+    ``psf='huygens'`` takes step 3 from :func:`trace_huygens_rows` and rox_huygens_psf instead:
+    the nodes' diffraction PSFs on the same windows, sampled at ``psf_oversample`` x
+    ``psf_oversample`` points per pixel and summed per pixel, each wavelength's PSF scaled to its
+    share of the node's usable flux (its spectral factor times the pupil share times the rays that
+    arrive), so that a node's PSF sums to its relative transmission as the geometric one does.
+    What a diffraction PSF throws outside the window is not known from inside it:
+    ``window_share`` is then 1 minus twice the share of the window's outermost ring of samples.
+    ``num_rays`` is the pupil sampling (64 is plenty; the default of 128 suits the ray histogram);
+    ``psf_ref_foc`` is the focus at which the reference spheres are set up (the picture is still
+    taken in the image plane).
+
+    Limits.  With the default ``psf='geometric'`` the PSFs are geometric: right where the spot,
+    not the aperture, sets the contrast.  A
     PSF's shape is not stretched by the local distortion.  Vignetting is counted; cos^4 and the
     area change of distortion are not (:func:`relative_illumination` has those).  No coatings.
     A node more than 1 % of whose light misses its window raises a warning: enlarge ``psf_size``.
@@ -1957,6 +1969,10 @@ def image_simulation(opt_model, scene, pixel_pitch, nodes=(5, 5), flds=None, nod
         raise ValueError(f'{what}: pixel_pitch {pixel_pitch!r} is not finite and > 0')
     if edge not in ('zero', 'replicate'):
         raise ValueError(f"{what}: edge is 'zero' or 'replicate', not {edge!r}")
+    if psf not in ('geometric', 'huygens'):
+        raise ValueError(f"{what}: psf is 'geometric' or 'huygens', not {psf!r}")
+    if psf == 'huygens' and not 1 <= int(psf_oversample) <= 16:
+        raise ValueError(f'{what}: psf_oversample {psf_oversample} outside [1, 16]')
     if not hasattr(scene, 'shape'):
         scene = np.asarray(scene, dtype=np.float64)
     shape = tuple(int(n) for n in scene.shape)
@@ -2002,23 +2018,28 @@ def image_simulation(opt_model, scene, pixel_pitch, nodes=(5, 5), flds=None, nod
     # a field's vignetting factors shrink the pupil box its grid covers: a ray stands for less pupil
     area = np.array([(2.0 - getattr(f, 'vlx', 0.0) - getattr(f, 'vux', 0.0)) / 2.0 *
                      ((2.0 - getattr(f, 'vly', 0.0) - getattr(f, 'vuy', 0.0)) / 2.0) for f in flds])
-    results = _trace_packets(eng, fs, wis, opts_list, int(num_rays))
-    psfs = t.empty((C, GY, GX, S, S), dtype=t.float64, device=eng.device)
-    gain, share = np.zeros((C, N)), np.full((C, N), np.nan)
-    for c in range(C):
-        maps, _cnt, exp, item = eng.weighted_maps(results, flags, item_factor=(area[:, None] * factors[c]).reshape(-1),
-                                                  item_map=np.repeat(np.arange(N), Wn), n_maps=N, window=window,
-                                                  bins=S, on_device=True)
-        flux_in, flux = simulation_flux(records_view(item, WMAP_ITEM_DTYPE), exp.cpu().numpy(), N)
-        top = flux.max()
-        if top > 0.0:
-            # x is the maps' first axis; the product with the reciprocal is one IEEE rounding wherever it runs
-            psfs[c] = (maps.transpose(1, 2) * (1.0 / float(top))).reshape(GY, GX, S, S)
-            gain[c] = flux_in / top
-            share[c] = np.where(flux > 0.0, flux_in / np.where(flux > 0.0, flux, 1.0), np.nan)
-        else:
-            psfs[c] = 0.0
-    del results
+    if psf == 'huygens':
+        psfs, gain, share = _huygens_stack(opt_model, flds, wvls, int(num_rays), check_apertures, centre, S, pitch,
+                                           int(psf_oversample), area, factors, (GY, GX), psf_ref_foc, what)
+    else:
+        results = _trace_packets(eng, fs, wis, opts_list, int(num_rays))
+        psfs = t.empty((C, GY, GX, S, S), dtype=t.float64, device=eng.device)
+        gain, share = np.zeros((C, N)), np.full((C, N), np.nan)
+        for c in range(C):
+            maps, _cnt, exp, item = eng.weighted_maps(results, flags,
+                                                      item_factor=(area[:, None] * factors[c]).reshape(-1),
+                                                      item_map=np.repeat(np.arange(N), Wn), n_maps=N, window=window,
+                                                      bins=S, on_device=True)
+            flux_in, flux = simulation_flux(records_view(item, WMAP_ITEM_DTYPE), exp.cpu().numpy(), N)
+            top = flux.max()
+            if top > 0.0:
+                # x is the maps' first axis; the product with the reciprocal is one IEEE rounding wherever it runs
+                psfs[c] = (maps.transpose(1, 2) * (1.0 / float(top))).reshape(GY, GX, S, S)
+                gain[c] = flux_in / top
+                share[c] = np.where(flux > 0.0, flux_in / np.where(flux > 0.0, flux, 1.0), np.nan)
+            else:
+                psfs[c] = 0.0
+        del results
     low = np.argwhere(share < 0.99)
     if len(low):
         c, n = low[np.argmin(share[low[:, 0], low[:, 1]])]
@@ -2041,6 +2062,47 @@ def image_simulation(opt_model, scene, pixel_pitch, nodes=(5, 5), flds=None, nod
     elif disp is None:
         image = blurred
     return SimulatedImage(image, blurred, psfs, (node_y, node_x), image_pts, err, disp, gain, share)
+
+
+def _huygens_stack(opt_model, flds, wvls, num_rays, check_apertures, centre, S, pitch, over, area, factors, nodes,
+                   ref_foc, what):
+    """the PSF stack [C, GY, GX, S, S] of image_simulation(psf='huygens'), its gains and window
+    shares [C, N]: every (node, wavelength) item's Huygens PSF at ``over`` x ``over`` points per
+    pixel of the node's window (bin a of the window spans centre - S pitch / 2 + [a, a + 1] pitch,
+    as the geometric maps' bins do), summed per pixel and divided by its sum over the window, then
+    weighted by the item's share of the usable flux of the channel's brightest node"""
+    hr = trace_huygens_rows(opt_model, flds, wvls, num_rays, check_apertures, ref_foc, what)
+    eng, t = hr.eng, hr.eng.torch
+    GY, GX = nodes
+    N, Wn, C = len(flds), len(wvls), factors.shape[0]
+    n_s, p_s = S * over, pitch / over
+    origins = np.asarray(centre, dtype=np.float64) - S * pitch / 2.0 + p_s / 2.0
+    planes = huygens_planes(hr.centres, origins, [0.0], Wn)
+    fine, _field, stats = eng.huygens_psf(hr.rows, hr.status, planes, n_s, n_s, p_s, p_s, n_rays=hr.n_rays)
+    fine = fine.reshape(N, Wn, n_s, n_s)
+    ring = fine[:, :, 0, :].sum(-1) + fine[:, :, -1, :].sum(-1) + fine[:, :, 1:-1, 0].sum(-1) + fine[:, :, 1:-1, -1].sum(-1)
+    pix = fine.reshape(N, Wn, S, over, S, over).sum(dim=(3, 5))
+    total = pix.sum(dim=(2, 3))
+    unit = t.where(total > 0.0, 1.0 / t.where(total > 0.0, total, t.ones_like(total)), t.zeros_like(total))
+    pix = (pix * unit[:, :, None, None]).transpose(2, 3)             # rows along y, columns along x
+    n_ok = stats['n'].reshape(N, Wn).astype(np.float64)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        ring_share = np.where(stats['sum'].reshape(N, Wn) > 0.0,
+                              ring.cpu().numpy() / stats['sum'].reshape(N, Wn), 0.0)
+    psfs = t.zeros((C, GY, GX, S, S), dtype=t.float64, device=eng.device)
+    gain, share = np.zeros((C, N)), np.full((C, N), np.nan)
+    for c in range(C):
+        flux_w = area[:, None] * factors[c][None, :] * n_ok                      # [N, Wn]
+        flux = flux_w.sum(axis=1)
+        top = flux.max()
+        if not top > 0.0:
+            continue
+        w = t.from_numpy(flux_w / top).to(eng.device)
+        psfs[c] = (pix * w[:, :, None, None]).sum(dim=1).reshape(GY, GX, S, S)
+        gain[c] = flux / top
+        with np.errstate(invalid='ignore', divide='ignore'):
+            share[c] = np.where(flux > 0.0, 1.0 - 2.0 * (flux_w * ring_share).sum(axis=1) / flux, np.nan)
+    return psfs, gain, share
 
 
 def simulation_flux(item, scale_exp, n_nodes):
@@ -2965,6 +3027,202 @@ def wavefront_zernike(opt_model, fld, wvl, foc=0., num_rays=64, terms='fringe', 
                               n_terms=n_terms, circle=circle, field_wts=[1.0], spectral_wts=[1.0],
                               ref_wvl=wvl, **kwargs)
     return r.coef[0, 0, 0], r.stats[0, 0, 0], r.terms
+
+
+# ---- Huygens point spread functions on the detector's pixel grid --------------------------------
+# rayoptics/raytr/waveabr.py:305 forms an OPD as ... - ray_op ... + cr_op ...: the chief ray's
+# optical path to the reference sphere minus the ray's.  The ray's own path is minus that.
+HUYGENS_OPD_SIGN = -1.0
+
+
+def huygens_rows(seg, opd, centre, radius, n_img, wvl_sys):
+    """The rows of rox_huygens_psf from the rays at the image: ``seg`` [10, R] the ROX_OUT_LAST
+    packet (p in rows 0-2, d in rows 3-5), ``opd`` [R] the ROX_OUT_OPD row (system units) about the
+    reference sphere of centre ``centre`` (x, y, z in image coordinates) and radius ``radius``;
+    torch tensors, float64.  Ray r is a plane wavelet that arrives along d_r.  Its optical path at
+    the centre c, up to a constant common to all rays, is its path to the reference sphere plus
+    n times what lies between the sphere and the plane through c normal to d_r: with TA = p - c
+    and q = |TA|^2 - (d.TA)^2 the ray meets the sphere sqrt(R^2 - q) before that plane, so
+        Phi_r = HUYGENS_OPD_SIGN * W_r - n q / (sqrt(R^2 - q) + |R|)
+    (the second term is n (sqrt(R^2 - q) - |R|), written without cancellation).  n is |n_img|: d is
+    the direction the light travels in, also where an odd number of mirrors has turned it towards
+    -z and the reference's index carries a sign, and a path grows along it.  Returns [4, R] =
+    (Phi / lambda, n d / lambda): cycles, and cycles per system unit about c."""
+    t = __import__('torch')
+    ta = [seg[i] - float(centre[i]) for i in range(3)]
+    d = [seg[3 + i] for i in range(3)]
+    dta = d[0] * ta[0] + d[1] * ta[1] + d[2] * ta[2]
+    q = ta[0] * ta[0] + ta[1] * ta[1] + ta[2] * ta[2] - dta * dta
+    R = abs(float(radius))
+    n = abs(float(n_img))
+    phi = HUYGENS_OPD_SIGN * opd - n * q / (t.sqrt(R * R - q) + R)
+    k = n / float(wvl_sys)
+    return t.stack([phi / float(wvl_sys), k * d[0], k * d[1], k * d[2]])
+
+
+class HuygensRows:
+    """the traced items of :func:`huygens_psf`, still on the engine's device: ``rows`` [F*W, 4, ld],
+    ``status`` [F*W, ld], ``n_rays``; ``centres`` [F*W, 3] the reference spheres' centres (image
+    coordinates), ``radii`` [F*W]; the fields, wavelengths, spectral weights and the index of the
+    reference wavelength"""
+
+    def __init__(self, eng, rows, status, n_rays, centres, radii, flds, wvls, spectral_wts, ref):
+        self.eng, self.rows, self.status, self.n_rays = eng, rows, status, n_rays
+        self.centres, self.radii, self.flds, self.wvls = centres, radii, flds, wvls
+        self.spectral_wts, self.ref = spectral_wts, ref
+
+
+def trace_huygens_rows(opt_model, flds=None, wvls=None, num_rays=64, check_apertures=True, ref_foc=0.0,
+                       what='huygens_psf'):
+    """Every (field, wavelength) item's ``num_rays`` x ``num_rays`` pupil grid in two launches of
+    rox_trace_pupil_grids -- ROX_OUT_LAST for p and d at the image, ROX_OUT_OPD for W about the
+    item's reference sphere at focus ``ref_foc`` -- and :func:`huygens_rows` on them where they
+    lie -> :class:`HuygensRows`.  An infinite reference sphere raises ValueError."""
+    from .table import wavefront_from_model
+    ref_first = wvls is not None and len(wvls) > 0
+    eng, flds, wvls, spectral_wts, fs, wis, opts_last, _flags = _packet_items(opt_model, flds, wvls, int(num_rays),
+                                                                             check_apertures, what, abi.OUT_LAST)
+    ref = 0 if ref_first else wvls.index(float(opt_model['osp']['wvls'].central_wvl))
+    opts_opd, centres, radii, n_img = [], [], [], []
+    for fld in flds:
+        for wvl in wvls:
+            ref_sphere, cr_pkg = _setup_pupil_coords(opt_model, fld, wvl, float(ref_foc))
+            own = getattr(fld, 'rox_wavefront', None)
+            wf = own if own is not None else wavefront_from_model(opt_model, fld, cr_pkg, ref_sphere)
+            wf = abi.Wavefront.from_buffer_copy(bytes(wf))
+            if wf.kind != abi.WF_FINITE or not np.isfinite(wf.ref_radius) or abs(wf.ref_radius) > 1e8 \
+                    or wf.ref_radius == 0.0:
+                raise ValueError(f'{what}: the reference sphere of a field at {wvl} nm is infinite (radius '
+                                 f'{wf.ref_radius!r}): a Huygens PSF needs a finite exit pupil')
+            kw = dict(check_apertures=bool(check_apertures), apply_vignetting=True)
+            _e, _f, _wi, o = _launch_setup(opt_model, fld, wvl, kw, abi.OUT_OPD, wf=wf)
+            opts_opd.append(o)
+            ip = ref_sphere[0]
+            centres.append((float(ip[0]), float(ip[1]), float(ref_foc)))
+            radii.append(float(wf.ref_radius))
+            n_img.append(float(wf.n_img))
+    grid = make_grid((-1., -1.), (1., 1.), int(num_rays))
+    last = eng.trace_pupil_grids(fs, wis, grid, opts_last, want_pupil=False)
+    opd = eng.trace_pupil_grids(fs, wis, grid, opts_opd, want_pupil=False)
+    t = getattr(eng, 'torch', None) or __import__('torch')
+    from .engine import padded_ld
+    R = int(num_rays) * int(num_rays)
+    ld = padded_ld(R)
+    n_items = len(fs)
+    rows = t.zeros((n_items, 4, ld), dtype=t.float64, device=eng.device)
+    status = t.full((n_items, ld), abi.BLOCKED, dtype=t.uint8, device=eng.device)
+    W = len(wvls)
+    for i in range(n_items):
+        lam = opt_model.nm_to_sys_units(wvls[i % W])
+        rows[i, :, :R] = huygens_rows(last[i].seg, opd[i].seg[0], centres[i], radii[i], n_img[i], lam)
+        s_last, s_opd = last[i].status, opd[i].status
+        status[i, :R] = t.where(s_last == abi.OK, s_opd, s_last)
+    return HuygensRows(eng, rows, status, R, np.array(centres), np.array(radii), flds, wvls,
+                       [float(w) for w in spectral_wts], ref)
+
+
+class HuygensPSF:
+    """What :func:`huygens_psf` returns.  F fields, W wavelengths, K focus planes, S x S pixels.
+
+    ``psf``           [F, W, K, S, S] |U|^2 of every item and plane, first pixel axis along x; NumPy,
+                      or with ``on_device`` a torch tensor in HBM
+    ``poly``          [F, K, S, S] sum over w of spectral_wts[w] * psf[f, w, k] / norm[f, w, k]: all
+                      wavelengths of a field lie on one window, so lateral colour is in it
+    ``strehl``        [F, W, K] psf at the pixel nearest the reference sphere's centre over ``norm``
+                      (the reference wavelength's centre is a pixel; the others lie up to half a
+                      pixel off)
+    ``norm``, ``sum`` [F, W, K] (sum of the amplitudes)^2 -- the peak of a perfect wavefront -- and
+                      the sum of psf over the window
+    ``border_share``  [F, W, K] the share of ``sum`` in the window's outermost ring of pixels: the
+                      handle on a window that is too small
+    ``peak``, ``peak_px``  [F, W, K] and [F, W, K, 2] the largest value and its pixel
+    ``n``             [F, W] the rays that reached the image
+    ``origins``       [F, 2] image coordinates (x, y) of pixel (0, 0); pixel (a, b) lies at origin +
+                      (a, b) * pixel_pitch
+    ``centres``       [F, W, 3] the reference spheres' centres
+    ``poly_strehl``   [F, K] the spectrally weighted mean of ``strehl``;
+    ``best_focus`` / ``best_focus_kind``  [F] :func:`best_focus` of its negative"""
+
+    def __init__(self, focs, wvls, spectral_wts, pixel_pitch, psf, poly, stats, border_share, origins, centres):
+        self.focs = np.asarray(focs, dtype=np.float64)
+        self.wvls, self.spectral_wts, self.pixel_pitch = wvls, np.asarray(spectral_wts, dtype=np.float64), pixel_pitch
+        self.psf, self.poly, self.stats = psf, poly, stats
+        self.strehl, self.norm, self.sum, self.peak = stats['strehl'], stats['norm'], stats['sum'], stats['peak']
+        self.peak_px = np.stack([stats['peak_ix'], stats['peak_iy']], axis=-1)
+        self.n = stats['n'][:, :, 0]
+        self.border_share, self.origins, self.centres = border_share, origins, centres
+        w = self.spectral_wts / self.spectral_wts.sum()
+        self.poly_strehl = np.einsum('w,fwk->fk', w, np.nan_to_num(self.strehl, nan=0.0))
+        bf = [best_focus(self.focs, -s) for s in self.poly_strehl]
+        self.best_focus = np.array([b[0] for b in bf])
+        self.best_focus_kind = [b[1] for b in bf]
+
+
+def huygens_window(centre_xy, size, pixel_pitch):
+    """the origin -- image coordinates of pixel (0, 0) -- of a window of ``size`` pixels whose
+    pixel size // 2 lies on ``centre_xy``"""
+    return np.asarray(centre_xy, dtype=np.float64) - (int(size) // 2) * float(pixel_pitch)
+
+
+def huygens_planes(centres, origins, focs, n_wvls):
+    """[F*W, K, 3] the (x0, y0, dz) of rox_huygens_psf: field f's window origin and the focus
+    planes about item (f, w)'s reference-sphere centre"""
+    centres = np.asarray(centres, dtype=np.float64)
+    focs = np.asarray(focs, dtype=np.float64)
+    planes = np.empty((centres.shape[0], len(focs), 3))
+    for i, c in enumerate(centres):
+        planes[i, :, 0:2] = np.asarray(origins[i // n_wvls]) - c[0:2]
+        planes[i, :, 2] = focs - c[2]
+    return planes
+
+
+def huygens_psf(opt_model, pixel_pitch, size=64, focs=(0.,), flds=None, wvls=None, num_rays=64,
+                check_apertures=True, on_device=False, ref_foc=0.0):
+    """Huygens point spread functions on the detector's pixel grid, through focus, on the device.
+    Every traced ray is a plane wavelet with its own phase and real direction of arrival; their
+    complex sum is taken at ``size`` x ``size`` pixels of ``pixel_pitch`` (system units) on every
+    focus plane ``focs`` (image shifted along z) and squared -- pupil distortion, an anamorphic
+    off-axis pupil and vignetting come with the rays, and pitch, window and defocus are free.
+
+    Two launches of rox_trace_pupil_grids over every (field, wavelength) item (:func:`trace_huygens_rows`:
+    ``num_rays`` x ``num_rays`` rays over the field's vignetted pupil box, the reference spheres set
+    up at focus ``ref_foc``), then one rox_huygens_psf call: a complex GEMM on the fp64 matrix
+    cores.  All wavelengths of a field share one window, its pixel size // 2 on the chief ray of
+    the reference wavelength (the first given, else the central one).  Amplitudes are 1: no
+    apodization, no coatings.  Sampling: the pupil grid aliases the PSF with a period of
+    lambda * (rays across) / (2 NA); keep size * pixel_pitch well below it.
+    Defaults as :func:`through_focus_map`; a workloads.TableModel passes ``flds`` and ``wvls``.
+    An infinite reference sphere raises ValueError.  Returns :class:`HuygensPSF`."""
+    from .engine import records_view, HUYGENS_STATS_DTYPE
+    what = 'huygens_psf'
+    focs = _check_focs(focs, what)
+    S, pitch = int(size), float(pixel_pitch)
+    if not 1 <= S <= abi.MAX_HUYGENS_PIXELS:
+        raise ValueError(f'{what}: size {size} outside [1, {abi.MAX_HUYGENS_PIXELS}]')
+    if not (np.isfinite(pitch) and pitch > 0.0):
+        raise ValueError(f'{what}: pixel_pitch {pixel_pitch!r} is not finite and > 0')
+    hr = trace_huygens_rows(opt_model, flds, wvls, num_rays, check_apertures, ref_foc, what)
+    eng, t = hr.eng, hr.eng.torch
+    F, W, K = len(hr.flds), len(hr.wvls), len(focs)
+    centres = hr.centres.reshape(F, W, 3)
+    origins = np.stack([huygens_window(centres[f, hr.ref, 0:2], S, pitch) for f in range(F)])
+    planes = huygens_planes(hr.centres, origins, focs, W)
+    psf, _field, raw = eng.huygens_psf(hr.rows, hr.status, planes, S, S, pitch, pitch, n_rays=hr.n_rays,
+                                       stats_on_device=True)
+    psf = psf.reshape(F, W, K, S, S)
+    ring = psf[..., 0, :].sum(-1) + psf[..., -1, :].sum(-1) if S > 1 else psf[..., 0, :].sum(-1)
+    if S > 2:
+        ring = ring + psf[..., 1:-1, 0].sum(-1) + psf[..., 1:-1, -1].sum(-1)
+    stats = records_view(raw, HUYGENS_STATS_DTYPE).reshape(F, W, K)
+    norm = t.from_numpy(np.ascontiguousarray(stats['norm'])).to(eng.device)
+    wts = t.tensor(hr.spectral_wts, dtype=t.float64, device=eng.device)
+    scaled = psf * (wts.reshape(1, W, 1) / norm).reshape(F, W, K, 1, 1)
+    poly = t.nan_to_num(scaled, nan=0.0).sum(dim=1)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        border = ring.cpu().numpy() / stats['sum']
+    if not on_device:
+        psf, poly = psf.cpu().numpy(), poly.cpu().numpy()
+    return HuygensPSF(focs, hr.wvls, hr.spectral_wts, pitch, psf, poly, stats, border, origins, centres)
 
 
 # ---- point spread function ------------------------------------------------------

@@ -1,7 +1,7 @@
 // rox_host.hpp -- host-side helpers shared by the translation units that define C entry points
 // (roxtrace.hip and the units its header lists, selftest.hip, spotstats.hip, the analyses psf.hip,
 // mtf.hip, ee.hip, gmtf.hip and zernike.hip, and through rox_packets.hpp footprint.hip, fresnel.hip,
-// solidangle.hip, segfoci.hip, wmaps.hip and wavediff.hip; imgsim.hip):
+// solidangle.hip, segfoci.hip, wmaps.hip and wavediff.hip; imgsim.hip and huygens.hip):
 // the error path and the argument checks, the environment switches, grow-only scratch blocks,
 // scratch kept per (device, stream), the pinned staging of host inputs, the carving of one
 // workspace block and an entry's turn on its per-stream state.

@@ -151,6 +151,12 @@ FOCUS_PSF_STATS_DTYPE = np.dtype([(name, np.int64 if name == 'n' else np.float64
 assert FOCUS_PSF_STATS_DTYPE.itemsize == C.sizeof(abi.FocusPsfStats)
 
 
+# rox_huygens_stats: what huygens_psf returns
+HUYGENS_STATS_DTYPE = np.dtype([('n', np.int64), ('norm', np.float64), ('sum', np.float64), ('peak', np.float64),
+                                ('strehl', np.float64), ('peak_ix', np.int32), ('peak_iy', np.int32)])
+assert HUYGENS_STATS_DTYPE.itemsize == C.sizeof(abi.HuygensStats)
+
+
 # rox_footprint: what surface_footprints returns
 FOOTPRINT_DTYPE = np.dtype([('n', np.int64), ('n_fail', np.int64, (5,)), ('n_inc', np.int64),
                             ('min', np.float64, (2,)), ('max', np.float64, (2,)), ('r2_max', np.float64),
@@ -1601,6 +1607,56 @@ class TraceEngine:
             _check(self.lib.rox_image_warp(C, H, W, p_in, ny.shape[0], nx.shape[0], ny.ctypes.data, nx.ctypes.data,
                                            d.ctypes.data, p_out, self._stream()), 'rox_image_warp')
         return out[0] if bare else out
+
+    @_in_flight
+    def huygens_psf(self, rows, status, planes, nx, ny, pitch_x, pitch_y, n_rays=None, amp=None, want_psf=True,
+                    want_field=False, stats_on_device=False):
+        """rox_huygens_psf: the complex sum of the OK rays' plane wavelets at the pixels of a product
+        grid, squared.  ``rows`` [n_items, 4, ld] = (phi, xi, eta, zeta) -- cycles, and cycles per
+        system unit -- ``status`` [n_items, ld] and the optional amplitudes ``amp`` [n_items, ld]
+        are contiguous tensors on this engine's device (float64, uint8, float64); ``planes``
+        [n_items, K, 3] = (x0, y0, dz) on the host: pixel (a, b) of a plane is the image point
+        (x0 + a pitch_x, y0 + b pitch_y), displaced dz along z.  Only the first ``n_rays`` (default
+        ld) rays count.  Returns ``(psf, field, stats)``: float64 tensors in HBM [n_items, K, nx, ny]
+        and [n_items, K, nx, ny, 2] (None unless wanted) and a HUYGENS_STATS_DTYPE array
+        [n_items, K] (n, norm, sum, peak, strehl, peak_ix, peak_iy) -- with ``stats_on_device`` its
+        bytes as a uint8 tensor (``records_view`` reads it).  include/roxtrace.h states the
+        arithmetic; tests/huygens_ref.py restates it."""
+        t = self.torch
+        what = 'huygens_psf'
+
+        def dev(x, name, dtype, shape):
+            if not isinstance(x, t.Tensor) or x.dtype != dtype or not x.is_contiguous() or not x.is_cuda or \
+                    x.device != self.device or (shape is not None and tuple(x.shape) != shape):
+                raise EngineError(f'{what}: {name} is a contiguous {dtype} tensor on {self.device}'
+                                  + (f' of shape {shape}' if shape else ''))
+            return x
+        rows = dev(rows, 'rows', t.float64, None)
+        if rows.dim() != 3 or int(rows.shape[1]) != 4:
+            raise EngineError(f'{what}: rows are [n_items, 4, ld], not {tuple(rows.shape)}')
+        n_items, ld = int(rows.shape[0]), int(rows.shape[2])
+        status = dev(status, 'status', t.uint8, (n_items, ld))
+        if amp is not None:
+            amp = dev(amp, 'amp', t.float64, (n_items, ld))
+        pl = np.ascontiguousarray(planes, dtype=np.float64)
+        if pl.ndim != 3 or pl.shape[0] != n_items or pl.shape[2] != 3:
+            raise EngineError(f'{what}: planes are [{n_items}, K, 3], not {pl.shape}')
+        K = int(pl.shape[1])
+        nx, ny = int(nx), int(ny)
+        n_rays = ld if n_rays is None else int(n_rays)
+        if not (1 <= nx <= abi.MAX_HUYGENS_PIXELS and 1 <= ny <= abi.MAX_HUYGENS_PIXELS):
+            raise EngineError(f'{what}: nx, ny in [1, {abi.MAX_HUYGENS_PIXELS}], got {nx}, {ny}')
+        psf = t.empty((n_items, K, nx, ny), dtype=t.float64, device=self.device) if want_psf else None
+        field = t.empty((n_items, K, nx, ny, 2), dtype=t.float64, device=self.device) if want_field else None
+        stats, p_stats = self._records_out(stats_on_device, (n_items, K), HUYGENS_STATS_DTYPE)
+        with t.cuda.device(self.device):
+            _check(self.lib.rox_huygens_psf(n_items, K, n_rays, rows.data_ptr(), ld,
+                                            amp.data_ptr() if amp is not None else None, status.data_ptr(),
+                                            pl.ctypes.data, nx, ny, float(pitch_x), float(pitch_y),
+                                            psf.data_ptr() if psf is not None else None,
+                                            field.data_ptr() if field is not None else None, p_stats,
+                                            self._stream()), 'rox_huygens_psf')
+        return psf, field, stats
 
     @_in_flight
     def wave_differentials(self, results, trace_flags, wvl_idxs, slots=None, aux=None, want_cols=False,
